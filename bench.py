@@ -48,6 +48,15 @@ samples are re-evaluated by the CPU oracle (the checker, never the thing measure
 wrote (marginal entries: three q-hat cells against torch.sort as well); above 1e-5 the process exits 3.  The LAST key of the
 line, `summary`, repeats [ms per step, roofline fraction, parity] of every config in ~0.7 KB.
 
+--dump-outputs DIR: after the timed steps, rank 0 writes what the LAST timed step computed - the arrays its caller receives -
+as DIR/<name>.npy (float32; float64 for other dtypes): c3 `qhat` (joint [10]; marginal the last slab's [10, *cells]), joint
+`scores` (per sample) and `modulation_slab<s>` (per slab, over the cells it scales: the crop), and `residual_last_slab` (the
+buffer after the step); c1/c2/c4/c5 `qhat`, joint `scores` and `modulation` (cropped alike), and `residual`.  A file holds
+at most 2^20 elements and an equal share of 64 MB; a larger array is sampled at fixed seeded indices (the same in every
+run).  The inputs are seeded and, with --slab 0, the c3 slab plan is then chosen from the device's whole memory instead
+of its free memory (a run that cannot have it exits 2), so two builds run with the same arguments can be compared output
+for output.  The line then carries `dump_outputs` (each array's full shape and the elements written).
+
 Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (fused
 residual kernel, HIP events on its stream; `achieved` = SURVEY 8(d) bytes: 16 B x the interior
 cells one launch computes, halo planes NOT counted) and `cpu_baseline` (the CPU oracle = the
@@ -161,7 +170,12 @@ def parse():
     ap.add_argument("--no-prune", action="store_true",
                     help="joint mode: read the whole residual in the score pass instead of the branch-and-bound form")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; "
+                         "a large array as a fixed seeded sample of it, 64 MB in all, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config]
     shp = cfg["shape"]
     args.mode = args.mode or cfg["mode"]
@@ -348,6 +362,45 @@ def oracle_parity(kind, eq, inputs, res, samples, absolute):
     return worst
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements written per array at most
+DUMP_MAX_BYTES = 64 * 10 ** 6  # ... and bytes in all, .npy headers included: an equal share per array
+NPY_HEADER_MAX = 1024          # bytes of a 1-D .npy header, with room to spare (numpy writes 128)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor of ``arrays`` (name -> tensor, what the last timed step handed its caller) as
+    ``out_dir/<name>.npy``, float32 kept, every other dtype as float64.  Each file holds at most DUMP_SAMPLE elements
+    and at most an equal share of DUMP_MAX_BYTES, so the budget holds however many arrays there are (a C3 plan of many
+    thin slabs has one modulation per slab).  A tensor with more elements than that is written as a sample of them,
+    gathered on the device at flat indices (sorted, row-major over its logical shape) drawn from a generator of fixed
+    seed: the same cells in every run with the same arguments, so that two builds compare output for output.
+    Returns {name: [logical shape, elements written]} for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) - NPY_HEADER_MAX         # data bytes per file
+    index = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dtype = np.float32 if t.dtype == torch.float32 else np.float64
+        n, k = t.numel(), min(t.numel(), DUMP_SAMPLE, share // np.dtype(dtype).itemsize)
+        if n > k:
+            g = torch.Generator().manual_seed(0)
+            flat = torch.randint(0, n, (k,), generator=g).sort().values.to(t.device)
+            v = t[torch.unravel_index(flat, t.shape)]
+        else:
+            v = t.reshape(-1)
+        a = v.cpu().numpy().astype(dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        index[name] = [list(t.shape), int(a.size)]
+    return index
+
+
+def scored(mod, crop):
+    """A slab's modulation over the cells it scales, i.e. inside ``crop`` (cells per side of each cell axis): the rim
+    planes outside it are NaN by construction (pipeline.JointCalibration) and carry no value."""
+    return mod[tuple(slice(c, n - c) for c, n in zip(crop, mod.shape))]
+
+
 def surrogate_layout(B, F, T, X, Y, dev):
     """Fields as the reference's callers hand them over (Marginal/NS_Residuals_CP.py:282-287, MHD_Residuals_CP.py:326-346):
     the surrogate's output [BS,F,Nx,Ny,Nt] seen through permute(0,1,4,2,3) - a [BS,F,Nt,Nx,Ny] view whose FASTEST axis is
@@ -392,13 +445,16 @@ def run_secondary(args, cfg, dev, group, rank, world, par):
     ev = []
     pruned = [False]
     last_jc = [None]
+    last_res = [None]
 
-    def step():
+    def step(keep=False):
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         e0.record()
         res = evaluate()
         e1.record()
         ev.append((e0, e1, e2))
+        if keep:                                            # --dump-outputs: the last timed step's residual
+            last_res[0] = res
         if args.mode == "joint":
             jc = pipeline.JointCalibration(B, dev, group=group, prune=not args.no_prune)
             last_jc[0] = jc
@@ -420,15 +476,25 @@ def run_secondary(args, cfg, dev, group, rank, world, par):
         step()
     sync()
     ev.clear()
+    dumping = bool(getattr(args, "dump_outputs", None)) and rank == 0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        q = step()
+    for i in range(args.steps):
+        q = step(keep=dumping and i == args.steps - 1)
     sync()
     elapsed = time.perf_counter() - t0
     if group is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX, group=group)
         elapsed = float(tt.item())
+    dumped = None
+    if dumping:                                             # (before the parity check re-evaluates)
+        arrays = {"qhat": q}
+        if args.mode == "joint":
+            arrays["scores"] = last_jc[0].all_scores
+            arrays["modulation"] = scored(last_jc[0].modulation[0], crop)
+        arrays["residual"] = last_res[0]
+        dumped = dump_outputs(args.dump_outputs, arrays)
+    last_res[0] = None
     if rank == 0:
         # (this function also serves `--config c1|c2|c4|c5` as a line of its own: the mean there, the median as a secondary)
         avg = med if getattr(args, "median", False) else (lambda xs: sum(xs) / len(xs))
@@ -464,7 +530,7 @@ def run_secondary(args, cfg, dev, group, rank, world, par):
                          "frac": achieved / HBM_PEAK_GBS, "traffic": pmc["traffic_bytes_per_launch"] if pmc else None,
                          "traffic_source": pmc["source"] if pmc else None, "avg_launch_ms": kms,
                          "algorithmic_bytes_per_launch": launch_bytes},
-            **calib}
+            **calib, **({"dump_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {})}
     return None
 
 
@@ -1029,8 +1095,12 @@ def main():
     # The grid does not fit the HBM next to its residual (C3: 3 x 275 GB of fields), so the job streams SLABS of it, all
     # samples of a slab at a time (a per-cell std / quantile needs every sample of its cell): see C3Stream.
     n_axis, other = (X - 2, T * Y) if xs else (T, X * Y)
-    free = torch.cuda.mem_get_info(dev)[0]
+    free, total = torch.cuda.mem_get_info(dev)
     if not args.slab:
+        # --dump-outputs: planned for the device's whole memory, not for what happens to be free, so that the same
+        # arguments give the same slab plan - and so the same inputs - in every run (memory held elsewhere then stops the
+        # run below, exit 2, instead of changing the inputs)
+        room = total if args.dump_outputs else free
         # fewer, thicker slabs re-read fewer halo rows / planes; the resident set must fit the free HBM (t-slabs of 16
         # planes at the full batch: 301 GB of the 309 GB the device reports; x-slabs of 128 rows: 279 GB).
         # Smaller per-rank batches (--scaling strong, --batch) afford thicker slabs, up to the whole axis (no halo).
@@ -1044,7 +1114,7 @@ def main():
         else:
             div = [n_axis, (n_axis + 1) // 2, (n_axis + 2) // 3, (n_axis + 3) // 4, 16, 13, 8]
         cands = sorted(set(c for c in div if 0 < c <= n_axis), reverse=True)
-        idx = next((i for i, c in enumerate(cands) if resident_bytes(B, n_axis, c, other) + extra <= free - (4 << 30)),
+        idx = next((i for i, c in enumerate(cands) if resident_bytes(B, n_axis, c, other) + extra <= room - (4 << 30)),
                    len(cands) - 1)
         if group is not None:
             # the ranks must stream the SAME slabs (the per-slab collectives carry one slab's cells): free memory differs
@@ -1116,6 +1186,18 @@ def main():
     cells_per_step = B * sum(slabs) * other * world                   # the cells the launches compute, all ranks
     value = cells_per_step * args.steps / elapsed
 
+    # --dump-outputs, before anything else touches the buffers: the last timed step's q-hat (joint: [10]; marginal: the
+    # last slab's [10, *cells]), joint: the per-sample scores and every slab's modulation over its scored cells, and the
+    # last slab's residual (what the buffer holds after the step; the earlier slabs' were overwritten by it within the step)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {"qhat": qhat}
+        if args.mode == "joint":
+            arrays["scores"] = last_jc[0].all_scores
+            arrays.update((f"modulation_slab{s}", scored(m, crop)) for s, m in enumerate(last_jc[0].modulation))
+        arrays["residual_last_slab"] = res_main[slabs[-1]]
+        dumped = dump_outputs(args.dump_outputs, arrays)
+
     # The branch-and-bound score pass makes `value` depend on the data (how much of the residual the bounds let it
     # skip).  Say by how much: the share of the pass that was read, and the same step with the full pass - one more
     # step, timed apart, not part of `value`.
@@ -1183,6 +1265,8 @@ def main():
                          "launches_timed": len(timed)},
             "qhat_first_last": [float(qhat.reshape(len(alphas), -1)[0, 0]), float(qhat.reshape(len(alphas), -1)[-1, 0])],
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if args.mode == "marginal":
             sel = [e1.elapsed_time(e2) for (k, sl, _, e1, e2) in ev_used if args.warmup <= k < args.warmup + args.steps]
             out["select_ms_per_slab"] = sum(sel) / len(sel)

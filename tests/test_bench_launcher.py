@@ -115,3 +115,91 @@ def test_c3_interior_row_slabs_and_c4_equations():
         assert cfg["bpc"] == 4 * (f + 1) and cfg["equation"] == eq and cfg["shape"] == (1024, 64, 256, 256)
         functor = cfg["kernel"].split("<")[1].split("<")[0].split(",")[0]
         assert f"struct {functor} " in src or f"struct {functor}\n" in src, functor
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: small arrays whole, large ones as the same seeded sample of cells in every run (strided views
+    gathered by their logical index), float32 kept and other dtypes as float64, at most 64 MB in all."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(5)
+    base = torch.rand(3, 700, 1000, generator=g)
+    big = base[:, :, ::2]                                          # 1.05 M elements > DUMP_SAMPLE, not contiguous
+    small = torch.arange(10, dtype=torch.int64)
+    index = bench.dump_outputs(str(tmp_path / "a"), {"big": big, "small": small, "q": base[0, 0, :10]})
+    assert index == {"big": [[3, 700, 500], bench.DUMP_SAMPLE], "small": [[10], 10], "q": [[10], 10]}
+    a = np.load(tmp_path / "a" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,)
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "q.npy"), base[0, 0, :10].numpy())
+    # the sample is the values at sorted flat indices of the logical shape, and the same ones again
+    flat = torch.randint(0, big.numel(), (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(a, big.reshape(-1)[flat].numpy())
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big.contiguous()})
+    assert np.array_equal(a, np.load(tmp_path / "b" / "big.npy"))
+    # many large float64 arrays share the budget: every file is written, 64 MB in all
+    idx = bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": big.double() for i in range(9)})
+    assert len(idx) == 9 and sum(os.path.getsize(tmp_path / "c" / f"x{i}.npy") for i in range(9)) <= 64 * 10 ** 6
+    # a modulation is dumped over the cells it scales: the NaN rim planes JointCalibration leaves outside the crop go
+    mod = torch.full((6, 5, 4), float("nan"))
+    mod[1:-1, :, 1:-1] = 2.0
+    inner = bench.scored(mod, (1, 0, 1))
+    assert inner.shape == (4, 5, 2) and bool(torch.isfinite(inner).all())
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0", "--plumbing-check"])
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+@pytest.mark.parametrize("rows", [32, 16])
+def test_dump_outputs_of_a_many_slab_c3_plan_stay_within_64_mb(tmp_path, rows):
+    """What main() hands dump_outputs for C3 joint x-slabs of `rows` rows (16 / 32 slabs: one cropped modulation of up to
+    62 x rows x 510 cells each, the q-hat, the scores and a 4096 x 64 x rows x 512 residual - a broadcast stand-in, not
+    allocated): every file is written, the modulations as samples, and the files total at most 64 MB."""
+    import torch
+    slabs = bench.split_slabs(510, rows)
+    arrays = {"qhat": torch.rand(10), "scores": torch.rand(4096)}
+    arrays.update((f"modulation_slab{s}", bench.scored(torch.rand(64, sl, 512), (1, 0, 1))) for s, sl in enumerate(slabs))
+    arrays["residual_last_slab"] = torch.rand(1).expand(4096, 64, slabs[-1], 512)
+    index = bench.dump_outputs(str(tmp_path), arrays)
+    files = sorted(os.listdir(tmp_path))
+    assert files == sorted(n + ".npy" for n in arrays) and list(index) == list(arrays)
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 * 10 ** 6
+    m0 = index["modulation_slab0"]
+    assert m0[0] == [62, slabs[0], 510] and m0[1] < 62 * slabs[0] * 510
+    assert index["qhat"][1] == 10 and index["scores"][1] == 4096
+
+
+def _dump_run(out, *argv):
+    r = _run([*argv, "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(out)],
+             timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_end_to_end(tmp_path):
+    """bench.py --dump-outputs on the MI355X, both timed paths: C3 joint x-slabs at a small size (main(): q-hat, scores,
+    one cropped modulation per slab, the last slab's residual) twice - the same files, bit for bit - and C5 joint
+    (run_secondary).  The files are the line's `dump_outputs` index, of the shapes and sizes it states, all finite."""
+    import numpy as np
+    c3 = ["--batch", "40", "--nt", "9", "--nx", "34", "--ny", "64", "--slab", "16", "--no-secondary"]
+    expect = {
+        "a": {"qhat": [10], "scores": [40], "modulation_slab0": [7, 16, 62], "modulation_slab1": [7, 16, 62],
+              "residual_last_slab": [40, 9, 16, 64]},
+        "c5": {"qhat": [10], "scores": [256], "modulation": [1, 18, 62], "residual": [256, 1, 20, 64]}}
+    lines = {"a": _dump_run(tmp_path / "a", *c3), "b": _dump_run(tmp_path / "b", *c3),
+             "c5": _dump_run(tmp_path / "c5", "--config", "c5", "--batch", "256", "--nt", "20", "--nx", "64")}
+    for run, line in lines.items():
+        index = line["dump_outputs"]["arrays"]
+        assert {k: v[0] for k, v in index.items()} == expect["a" if run == "b" else run], run
+        assert sorted(os.listdir(tmp_path / run)) == sorted(n + ".npy" for n in index)
+        for name, (shape, written) in index.items():
+            a = np.load(tmp_path / run / (name + ".npy"))
+            assert a.dtype == np.float32 and a.shape == (written,) == (min(int(np.prod(shape)), bench.DUMP_SAMPLE),)
+            assert np.isfinite(a).all(), (run, name)
+            if run == "b":
+                assert np.array_equal(a, np.load(tmp_path / "a" / (name + ".npy"))), name
+    q = np.load(tmp_path / "a" / "qhat.npy")                       # the q-hat the line reports is the one dumped
+    assert [float(q[0]), float(q[-1])] == lines["a"]["qhat_first_last"]
