@@ -84,8 +84,42 @@ FFT_SIGNATURES = {
                                c_void_p, c_void_p],
 }
 
+# libcp_pre_dist.so (include/cp_pre_dist.h): the sweeps of the sharded marginal calibration by histogram exchange
+DIST_SO_PATH = os.path.join(_HERE, "libcp_pre_dist.so")
+PRE_DIST_ABI_VERSION = 1
+PRE_DIST_NB, PRE_DIST_PICK_CAP, PRE_DIST_MAX_SLOTS = 256, 2048, 64
+_src = [_fp, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64]     # scores .. W, Co
+DIST_SIGNATURES = {
+    "pre_dist_abi_version": [],
+    "pre_dist_window_f32": _src + [_fp, c_void_p],
+    "pre_dist_hist_f32": _src + [_fp, c_int, _fp, c_void_p],
+    "pre_dist_collect_f32": _src + [_fp, _fp, c_int, _fp, _fp, _fp, c_void_p],
+    "pre_dist_pick_f32": [_fp, _fp, _fp, c_int64, c_int64, c_int, _fp, _fp, c_int, _fp, c_void_p],
+}
+
 _lib = None
 _fft = None
+_dist = None
+
+
+def load_dist():
+    """ctypes handle of libcp_pre_dist.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
+    global _dist
+    if _dist is None:
+        if not os.path.exists(DIST_SO_PATH):
+            raise ImportError(f"{DIST_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = ctypes.CDLL(DIST_SO_PATH)
+        lib.pre_dist_abi_version.argtypes, lib.pre_dist_abi_version.restype = [], c_int
+        have = lib.pre_dist_abi_version()
+        if have != PRE_DIST_ABI_VERSION:
+            raise ImportError(f"{DIST_SO_PATH} has ABI version {have}, this binding was written for {PRE_DIST_ABI_VERSION}: "
+                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        for name, argtypes in DIST_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        _dist = lib
+    return _dist
 
 
 def load_fft():

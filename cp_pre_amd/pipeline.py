@@ -202,6 +202,40 @@ class HipOps:
                                                             out_rank_stride, out_plane_stride, _lib.stream()),
                        "pre_kth_axis0_planes_f32")
 
+    # ---- the sharded marginal calibration by histogram exchange (libcp_pre_dist.so, include/cp_pre_dist.h) ----
+    # ``src`` = (base, plane_stride, row_stride, planes, n, per): ``planes`` score matrices [n, per] addressed like
+    # ``kth_planes``; a run is the cells [c0, c0 + C) of their flattened [planes * per] cells, padded to W * Co.
+
+    @staticmethod
+    def _dist_call(name, dev, *args):
+        with torch.cuda.device(dev):
+            _lib.check(getattr(_lib.load_dist(), name)(*[_lib.ptr(a) if isinstance(a, torch.Tensor) or a is None else a
+                                                          for a in args], _lib.stream()), name)
+
+    @staticmethod
+    def dist_window(src, c0, C, W, Co, win):
+        """win [3, W*Co] int32: per cell (min key, ~max key) of its non-NaN scores and 1 - has-NaN, MIN-reducible."""
+        HipOps._dist_call("pre_dist_window_f32", win.device, *src, c0, C, W, Co, win)
+
+    @staticmethod
+    def dist_hist(src, c0, C, W, Co, params, packed, hist):
+        """hist [W, words, Co] int32: the run's bucket counts per cell under the map ``params`` [3, W*Co]."""
+        HipOps._dist_call("pre_dist_hist_f32", hist.device, *src, c0, C, W, Co, params, int(bool(packed)), hist)
+
+    @staticmethod
+    def dist_collect(src, c0, C, W, Co, params, want, cnt, off, send):
+        """Every score in bucket want[c, s] ([W*Co, S]) to send[off[c, s] + i], i < cnt[c, s] (order inside a list free)."""
+        HipOps._dist_call("pre_dist_collect_f32", want.device, *src, c0, C, W, Co, params, want, int(want.shape[1]), cnt, off,
+                          send if send.numel() else None)
+
+    @staticmethod
+    def dist_pick(vals, cnt, off, slot, rnk, out):
+        """out[j, co] = the rnk[co, j]-th smallest score of list (co, slot[co, j]): W segments vals[off[w, co, s] + i],
+        i < cnt[w, co, s]."""
+        W, Co, S = cnt.shape
+        HipOps._dist_call("pre_dist_pick_f32", out.device, vals if vals.numel() else None, cnt, off, W, Co, S, slot, rnk,
+                          int(slot.shape[1]), out)
+
 
 def _ranks(n_total, alphas):
     return [icp.kth_index(n_total, n_total, a) for a in alphas]
@@ -501,7 +535,7 @@ def _marginal_planes(scores, alphas, group, ops, overlap, stage_bytes):
     return q.transpose(0, 1).reshape((nk, T) + rest)
 
 
-def marginal_qhat(scores, alphas, group=None, ops=None, stage_bytes=4 << 30, overlap=False):
+def marginal_qhat(scores, alphas, group=None, ops=None, stage_bytes=4 << 30, overlap=False, exchange="transpose", stats=None):
     """Per-cell q-hat [len(alphas), *cells] of |residual| scores [n_local, *cells].
 
     Single rank (no group, or a group of one: the exchange is the identity): one multi-rank select per tensor, or per
@@ -520,10 +554,25 @@ def marginal_qhat(scores, alphas, group=None, ops=None, stage_bytes=4 << 30, ove
     behind the select of the previous one; nothing else is ordered differently, the result is identical.  Off by
     default: the stream ordering it relies on (RCCL's stream against the compute stream, reuse of the staging
     buffers) has run under gloo at 2-3 ranks (whose collectives block the host) and on real RCCL at world size ONE only
-    (tests/test_gpu_parity.py::test_marginal_exchange_overlap_on_rccl_at_world_size_one) - never across GPUs."""
+    (tests/test_gpu_parity.py::test_marginal_exchange_overlap_on_rccl_at_world_size_one) - never across GPUs.
+
+    ``exchange`` (sharded only; a single rank selects locally either way): "transpose" (default) is the all-to-all above;
+    "histogram" (``_marginal_histogram``) lets the scores stay on their rank - the ranks agree on each cell's window,
+    reduce 256-bucket histograms and send only the scores in the buckets that hold a wanted rank (a few % of them on
+    typical data), so the traffic no longer grows with n_local.  The same q-hat bit for bit.  It reads split sizes on the
+    host once per run, so it cannot be captured in a HIP graph (RuntimeError under stream capture); ``overlap`` does not
+    apply to it.  ``stats``: a dict to fill with ``exchange``, ``runs``, ``fallback_runs`` (histogram runs that took the
+    transpose route), ``candidates`` (scores this rank received as owner) and ``wire_bytes`` (bytes this rank sends per
+    collective kind; ring all-reduce / reduce-scatter assumed)."""
+    if exchange not in _EXCHANGES:
+        raise ValueError(f"exchange={exchange!r}: 'transpose' or 'histogram'")
     ops = ops or HipOps
     n_local, cells = scores.shape[0], tuple(scores.shape[1:])
     world = torch.distributed.get_world_size(group) if group is not None else 1
+    if stats is not None and (world == 1 or exchange == "transpose"):
+        stats.update(_transpose_stats(scores, len(alphas), group, world, stage_bytes, exchange))
+    if world > 1 and exchange == "histogram":
+        return _marginal_histogram(scores, alphas, group, ops, stage_bytes, stats)
     tmajor = _is_time_major(scores) and not scores.is_contiguous() and cells[0] > 1
     if world == 1:
         ks = _ranks(n_local, alphas)
@@ -537,6 +586,29 @@ def marginal_qhat(scores, alphas, group=None, ops=None, stage_bytes=4 << 30, ove
     if tmajor:
         return _marginal_planes(scores, alphas, group, ops, overlap, stage_bytes)
     return _marginal_cells(scores, alphas, group, ops, overlap, stage_bytes)
+
+
+def _transpose_stats(scores, nk, group, world, stage_bytes, exchange):
+    """``marginal_qhat``'s ``stats`` for the routes that move every score: what the cell-run / plane form sends per rank
+    (nothing at world size one)."""
+    wire = {"all_to_all": 0, "all_gather": 0}
+    runs = 0
+    if world > 1:
+        n_local, cells = scores.shape[0], tuple(scores.shape[1:])
+        M = scores[0].numel()
+        if _is_time_major(scores) and not scores.is_contiguous() and cells[0] > 1:
+            T, per = cells[0], scores[0, 0].numel()
+            blk = n_local * (scores.stride(0) if n_local > 1 else per)
+            own = -(-T // world)
+            runs = -(-own // max(1, min(own, int(stage_bytes) // (4 * world * blk))))
+            wire["all_to_all"] = 4 * blk * (T - len(range(torch.distributed.get_rank(group), T, world)))
+            wire["all_gather"] = 4 * (world - 1) * own * nk * per
+        else:
+            per = max(1, min(-(-M // world), int(stage_bytes) // (4 * n_local * world)))
+            runs = -(-M // (per * world))
+            wire["all_to_all"] = 4 * runs * (world - 1) * n_local * per
+            wire["all_gather"] = 4 * (world - 1) * runs * nk * per
+    return dict(exchange=exchange, runs=runs, fallback_runs=0, candidates=0, wire_bytes=wire)
 
 
 def _marginal_cells(scores, alphas, group, ops, overlap, stage_bytes):
@@ -595,4 +667,221 @@ def _marginal_cells(scores, alphas, group, ops, overlap, stage_bytes):
     torch.distributed.all_gather(parts, q_own, group=group)                  # RCCL: nk * M / world floats per rank
     # parts[r][k, j, i] is the q-hat j of cell k*run + r*per + i
     q = torch.stack(parts, dim=2).permute(1, 0, 2, 3).reshape(nk, runs * run)[:, :M]
+    return q.reshape((nk,) + cells)
+
+
+# ---- sharded marginal q-hat by histogram exchange ----------------------------------------------------------------------
+
+DIST_NB = _lib.PRE_DIST_NB                  # buckets per cell
+DIST_PICK_CAP = _lib.PRE_DIST_PICK_CAP      # longest candidate list (one cell and slot, all ranks) the pick holds
+DIST_MAX_OWNED = (1 << 31) // (4 * DIST_NB) - 1     # cells an owner narrows per run (see _marginal_histogram)
+_EXCHANGES = ("transpose", "histogram")
+
+
+def _f2key(v):
+    """fp32 tensor -> its order-preserving uint32 keys, as int64 (common.h f2key)."""
+    u = v.view(torch.int32).long() & 0xFFFFFFFF
+    return torch.where(u >= 1 << 31, 0xFFFFFFFF - u, u | (1 << 31))
+
+
+def _key2f(k):
+    """int64 keys in [0, 2^32) -> fp32 (common.h key2f)."""
+    u = torch.where(k >= 1 << 31, k - (1 << 31), 0xFFFFFFFF - k)
+    return torch.where(u >= 1 << 31, u - (1 << 32), u).to(torch.int32).view(torch.float32)
+
+
+def _dist_source(scores):
+    """(src, cell order or None) for the sweeps: ``src`` = (base, plane_stride, row_stride, planes, n, per) addresses the
+    scores where they lie when they are time-major, dense or row-padded (in any cell order); anything else is copied
+    once.  The sweeps' flattened cells are in memory order; ``order`` undoes it (``icp.uncanon``)."""
+    n, cells = scores.shape[0], tuple(scores.shape[1:])
+    if _is_time_major(scores) and not scores.is_contiguous() and cells[0] > 1:
+        per = scores[0, 0].numel()
+        return (scores, scores.stride(1), scores.stride(0) if n > 1 else per, cells[0], n, per), None
+    lie = icp.rows_where_they_lie(scores)
+    if lie is None:
+        scores, lie = scores.contiguous(), (scores.contiguous(), None, None)
+    v, pitch, order = lie
+    M = v[0].numel()
+    return (v, M, pitch or M, 1, n, M), order
+
+
+def _dist_rows(src, c0, C):
+    """The run's scores as one [n, C] tensor (the transpose route of a run that falls back)."""
+    base, PS, RS, _, n, per = src
+    parts, g = [], c0
+    while g < c0 + C:
+        p, i = divmod(g, per)
+        L = min(per - i, c0 + C - g)
+        parts.append(torch.as_strided(base, (n, L), (RS, 1), base.storage_offset() + p * PS + i))
+        g += L
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+
+
+def _dist_params(win):
+    """The group's window [3, Cp] (MIN-reduced ``dist_window``) -> (params [3, Cp] int32 for the sweeps, NaN cells,
+    constant cells, their value).  A cell takes the value-linear map when its window and scale are finite, else the
+    key-linear one; the choice depends on the agreed window alone, so it is the same on every rank."""
+    lo = win[0].long() + (1 << 31)
+    hi = 0xFFFFFFFF - (win[1].long() + (1 << 31))
+    nan = win[2] == 0
+    const = (lo == hi) & ~nan
+    vlo, vhi = _key2f(lo.clamp_max(0xFFFFFFFF)), _key2f(hi.clamp_min(0))
+    sf = DIST_NB / (vhi - vlo)
+    lin = torch.isfinite(vlo) & torch.isfinite(vhi) & torch.isfinite(sf) & (sf > 0)
+    span = (hi - lo).clamp_min(0)
+    sh = torch.zeros_like(span)
+    for j in range(24):                                     # the least s with span >> s <= NB - 1
+        sh += (span >> (8 + j)) > 0
+    out = torch.empty_like(win)
+    out[0] = torch.where(lo >= 1 << 31, lo - (1 << 32), lo).to(torch.int32)
+    out[1] = torch.where(lin, sf, torch.zeros_like(sf)).view(torch.int32)
+    out[2] = torch.where(nan | const, -1, torch.where(lin, 0, sh)).to(torch.int32)
+    return out, nan, const, vlo
+
+
+def _dist_unpack(h, packed):
+    """Counts [words, Co] int32 -> [Co, NB] int32 (bucket b of a packed word: low half b, high half b + NB/2)."""
+    t = h.t()
+    return torch.cat([t & 0xFFFF, t >> 16], 1) if packed else t.contiguous()
+
+
+def _marginal_histogram(scores, alphas, group, ops, stage_bytes, stats=None):
+    """The histogram-exchange form of the sharded per-cell q-hat: only the scores in the buckets that hold a wanted rank
+    leave their rank, so the traffic follows the histogram (fixed per cell) and the candidates (a few % of the scores on
+    typical data), not n_local.  Any world size (a group of one exchanges with itself: the tests run it on RCCL so).
+
+    Runs of Cp = W * Co cells (rank r owns cells [r*Co, (r+1)*Co) of each) sized so that the run's histogram and the
+    owner's narrowing temporaries fit in ``stage_bytes`` (and Co <= DIST_MAX_OWNED).  Per run, on every rank, in this order:
+      1. window sweep; all_reduce(MIN) of [3, Cp] int32 (min key, ~max key, 1 - has-NaN).  NaN cells give NaN, constant
+         cells their value; neither takes part further;
+      2. histogram sweep (NB = 256 buckets per cell, two 15-bit counts per int32 when N = n_local * W <= 32767);
+         reduce_scatter(SUM): the owner gets the group's histogram of its cells;
+      3. narrow (torch): each (cell, rank k) -> (bucket, rank inside it); equal buckets form one slot; all_gather of the
+         wanted buckets [Co, S]; all_reduce(MAX) of [longest list, owner's candidates];
+      4. all_to_all of the fixed-size local counts [W, Co, S] of the wanted buckets; ONE host read (split sizes and the
+         decision).  If the longest list exceeds DIST_PICK_CAP or the candidates exceed half the run's scores on some
+         owner, the run takes the transpose route instead (all_to_all of its scores, local select) - the group's
+         decision, identical on every rank: heavy ties and quantised data land there, exact either way;
+      5. collect sweep into per-(owner, cell, slot) lists; all_to_all with the splits read in 4;
+      6. pick: the owner selects each rank among the W segments of its list, by key.
+    Then ONE all_gather of the owned q-hats.  Every fixed-size collective has the same size on every rank whatever the
+    data; the two variable ones get their sizes from the counts exchanged before them.  The host read per run makes
+    the protocol impossible to capture in a HIP graph: under stream capture it raises."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("exchange='histogram' reads split sizes on the host once per run: it cannot be captured in a "
+                           "HIP graph (use exchange='transpose')")
+    dist = torch.distributed
+    W, rank = dist.get_world_size(group), dist.get_rank(group)
+    n_local, cells = scores.shape[0], tuple(scores.shape[1:])
+    N = n_local * W
+    if N > 0x7fffffff:
+        raise ValueError(f"{n_local} x {W} calibration samples exceed the select's 32-bit sample count")
+    ks = _ranks(N, alphas)                     # raises before any collective if a level exceeds 1
+    nk = S = len(ks)
+    if nk > _lib.PRE_DIST_MAX_SLOTS:
+        raise ValueError(f"{nk} levels: the histogram exchange takes at most {_lib.PRE_DIST_MAX_SLOTS}")
+    src, order = _dist_source(scores)
+    M = src[3] * src[5]
+    packed = N <= 32767
+    words = DIST_NB // 2 if packed else DIST_NB
+    # per owned cell: the run's local histogram (W cells' words) + the owner's unpacked counts, cumulative counts and
+    # their int64 working copies (~4 x NB x 4 B)
+    # their int32 [Co, NB] tables stay below 2^31 bytes whatever ``stage_bytes`` allows (one 4M-cell run at world size one
+    # gave wrong buckets past that point on the MI355X: torch ops on such tables are not relied on)
+    Co = max(1, min(-(-M // W), int(stage_bytes) // (4 * words * W + 16 * DIST_NB), DIST_MAX_OWNED))
+    Cp = Co * W
+    runs = -(-M // Cp)
+    uk = sorted(set(ks))
+    kpos = torch.tensor([uk.index(k) for k in ks])
+    dev = scores.device
+    wire = {"all_reduce": 0, "reduce_scatter": 0, "all_gather": 0, "all_to_all": 0}
+    fallback, candidates = 0, 0
+    q_own = torch.empty(runs, nk, Co, dtype=torch.float32, device=dev)
+    mine = slice(rank * Co, (rank + 1) * Co)
+    for k in range(runs):
+        c0 = k * Cp
+        C = min(Cp, M - c0)
+        win = torch.empty(3, Cp, dtype=torch.int32, device=dev)
+        ops.dist_window(src, c0, C, W, Co, win)
+        dist.all_reduce(win, op=dist.ReduceOp.MIN, group=group)
+        wire["all_reduce"] += 2 * (W - 1) * win.numel() * 4 // W
+        params, nan, const, vconst = _dist_params(win)
+        hist = torch.empty(W, words, Co, dtype=torch.int32, device=dev)
+        ops.dist_hist(src, c0, C, W, Co, params, packed, hist)
+        own = torch.empty(words, Co, dtype=torch.int32, device=dev)
+        dist.reduce_scatter_tensor(own.view(-1), hist.view(-1), group=group)
+        wire["reduce_scatter"] += (W - 1) * own.numel() * 4
+        # 3. narrow: bucket of each rank = number of buckets whose cumulative count is <= the rank
+        cnt = _dist_unpack(own, packed)                                          # [Co, NB]
+        cum = cnt.cumsum(1, dtype=torch.int32)
+        excl = params[2, mine] < 0
+        b = torch.searchsorted(cum, torch.tensor(uk, dtype=torch.int32, device=dev).expand(Co, len(uk)).contiguous(),
+                               right=True).clamp_max(DIST_NB - 1)              # [Co, U]
+        below = torch.where(b > 0, cum.gather(1, (b - 1).clamp_min(0)), 0)
+        inner = torch.tensor(uk, device=dev).view(1, -1) - below                # rank inside its bucket
+        size = cnt.gather(1, b).long()
+        new = torch.ones_like(b, dtype=torch.bool)
+        new[:, 1:] = b[:, 1:] != b[:, :-1]
+        su = new.long().cumsum(1) - 1                                           # slot of each distinct rank
+        want_own = torch.full((Co, S), -1, dtype=torch.int32, device=dev)
+        want_own.scatter_(1, su, b.to(torch.int32))
+        lens = torch.zeros(Co, S, dtype=torch.int64, device=dev)
+        lens.scatter_(1, su, size)
+        want_own[excl] = -1
+        lens[excl] = 0
+        slot = torch.where(excl.view(-1, 1), -1, su[:, kpos.to(dev)]).to(torch.int32).contiguous()
+        rnk = inner[:, kpos.to(dev)].to(torch.int32).contiguous()
+        want = torch.empty(Cp, S, dtype=torch.int32, device=dev)
+        dist.all_gather_into_tensor(want, want_own, group=group)
+        wire["all_gather"] += (W - 1) * want_own.numel() * 4
+        dec = torch.stack([lens.max(), lens.sum()])
+        dist.all_reduce(dec, op=dist.ReduceOp.MAX, group=group)
+        wire["all_reduce"] += 2 * (W - 1) * dec.numel() * 8 // W
+        # 4. local counts of the wanted buckets, read off this rank's histogram [W, words, Co]
+        c = torch.arange(Cp, device=dev).view(-1, 1)
+        wb = want.long().clamp_min(0)
+        idx = (c // Co) * (words * Co) + (wb % words) * Co + c % Co
+        got = hist.view(-1).take(idx)
+        if packed:
+            got = torch.where(wb >= DIST_NB // 2, got >> 16, got & 0xFFFF)
+        cnt_out = torch.where(want >= 0, got, 0).to(torch.int32).contiguous()   # [Cp, S] = [W, Co, S] by owner
+        cnt_in = torch.empty_like(cnt_out)
+        dist.all_to_all_single(cnt_in, cnt_out, group=group)
+        wire["all_to_all"] += (W - 1) * Co * S * 4
+        host = torch.cat([dec, cnt_out.view(W, -1).sum(1, dtype=torch.int64),
+                          cnt_in.view(W, -1).sum(1, dtype=torch.int64)]).tolist()     # the run's one host read
+        longest, total, out_split, in_split = host[0], host[1], host[2:2 + W], host[2 + W:]
+        if longest > DIST_PICK_CAP or 2 * total > N * Co:
+            fallback += 1                                                       # the transpose route for this run
+            send = torch.zeros(W, n_local, Co, dtype=torch.float32, device=dev)        # [owner, sample, cell]
+            rows = _dist_rows(src, c0, C)
+            for r in range(W):
+                if r * Co < C:
+                    send[r, :, :min(Co, C - r * Co)] = rows[:, r * Co:(r + 1) * Co]
+            recv = torch.empty_like(send)
+            dist.all_to_all_single(recv, send, group=group)
+            wire["all_to_all"] += (W - 1) * n_local * Co * 4
+            q = ops.kth(recv.reshape(W * n_local, Co), ks)
+        else:
+            candidates += sum(in_split)                                         # this rank's lists, as owner
+            off_out = (cnt_out.view(-1).long().cumsum(0) - cnt_out.view(-1)).view(Cp, S)
+            sendv = torch.empty(sum(out_split), dtype=torch.float32, device=dev)
+            ops.dist_collect(src, c0, C, W, Co, params, want, cnt_out, off_out, sendv)
+            recv = torch.empty(sum(in_split), dtype=torch.float32, device=dev)
+            dist.all_to_all_single(recv, sendv, in_split, out_split, group=group)
+            wire["all_to_all"] += 4 * (sum(out_split) - out_split[rank])
+            off_in = (cnt_in.view(-1).long().cumsum(0) - cnt_in.view(-1)).view(W, Co, S)
+            q = torch.full((nk, Co), float("nan"), dtype=torch.float32, device=dev)
+            ops.dist_pick(recv, cnt_in.view(W, Co, S), off_in.contiguous(), slot, rnk, q)
+        q = torch.where(const[mine].view(1, -1), vconst[mine].view(1, -1), q)
+        q_own[k] = torch.where(nan[mine].view(1, -1), float("nan"), q)
+    parts = [torch.empty_like(q_own) for _ in range(W)]
+    dist.all_gather(parts, q_own, group=group)
+    wire["all_gather"] += (W - 1) * q_own.numel() * 4
+    q = torch.stack(parts, dim=2).permute(1, 0, 2, 3).reshape(nk, runs * Cp)[:, :M]
+    if stats is not None:
+        stats.update(exchange="histogram", runs=runs, fallback_runs=fallback, candidates=candidates, wire_bytes=wire)
+    if order is not None:
+        q = icp.uncanon(q.reshape((nk,) + tuple(src[0].shape[1:])), order, 1)
     return q.reshape((nk,) + cells)
