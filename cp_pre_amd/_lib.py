@@ -97,9 +97,40 @@ DIST_SIGNATURES = {
     "pre_dist_pick_f32": [_fp, _fp, _fp, c_int64, c_int64, c_int, _fp, _fp, c_int, _fp, c_void_p],
 }
 
+# libcp_pre_cov.so (include/cp_pre_cov.h): coverage at several calibration levels in one pass over the test residual
+COV_SO_PATH = os.path.join(_HERE, "libcp_pre_cov.so")
+PRE_COV_ABI_VERSION = 1
+PRE_COV_MAX_LEVELS = 16
+_opnd = [_fp, c_int64, c_int64, c_int64]                 # ptr, sample stride, strides of the two outer cell axes
+COV_SIGNATURES = {
+    "pre_cov_abi_version": [],
+    "pre_cov_levels_f32": _opnd + _opnd + [c_int64] * 4 + [_fp, c_int64, _fp, c_int, _fp, _fp, c_int64, c_void_p],
+}
+
 _lib = None
 _fft = None
 _dist = None
+_cov = None
+
+
+def load_cov():
+    """ctypes handle of libcp_pre_cov.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
+    global _cov
+    if _cov is None:
+        if not os.path.exists(COV_SO_PATH):
+            raise ImportError(f"{COV_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = ctypes.CDLL(COV_SO_PATH)
+        lib.pre_cov_abi_version.argtypes, lib.pre_cov_abi_version.restype = [], c_int
+        have = lib.pre_cov_abi_version()
+        if have != PRE_COV_ABI_VERSION:
+            raise ImportError(f"{COV_SO_PATH} has ABI version {have}, this binding was written for {PRE_COV_ABI_VERSION}: "
+                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        for name, argtypes in COV_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        _cov = lib
+    return _cov
 
 
 def load_dist():

@@ -345,3 +345,146 @@ def emp_cov_joint(pred_sets, y):
 
 
 ALPHA_LEVELS = np.arange(0.05, 0.95 + 0.1, 0.1)     # Marginal/Wave_Residuals_CP.py:284
+
+
+# ------------------------------------------------------------------ coverage at every level in one pass
+# The reference's `for alpha in alphas: qhat = calibrate(...); emp_cov(...)` loop (Marginal/Wave_Residuals_CP.py:284-290)
+# reads the test residual once per level; libcp_pre_cov.so (include/cp_pre_cov.h) reads it once for all of them, where it
+# lies.  fp32 levels (what calibrate_multi returns) take that pass; float64 ones (Python floats, np.float64) make numpy
+# compute float64 bounds and take the per-level functions above, which round those bounds exactly (_directed_f32).
+
+def _merge_cells(shape, strides_list):
+    """Cell axes (memory order) of one or two strided operands merged where every operand allows it and padded to three:
+    ([A, B, C], [[sA, sB, sC] per operand]) or None when the innermost axis is not dense or more than three remain."""
+    axes = [(d, [s[i] for s in strides_list]) for i, d in enumerate(shape) if d != 1]
+    merged = []
+    for d, st in axes:
+        if merged and all(ps == s * d for ps, s in zip(merged[-1][1], st)):
+            merged[-1] = (merged[-1][0] * d, st)
+        else:
+            merged.append((d, st))
+    if not merged:
+        merged = [(1, [1] * len(strides_list))]
+    if len(merged) > 3 or any(s != 1 for s in merged[-1][1]):
+        return None
+    merged = [(1, [0] * len(strides_list))] * (3 - len(merged)) + merged
+    return [d for d, _ in merged], [[st[i] for _, st in merged] for i in range(len(strides_list))]
+
+
+def cov_operands(y, centre=None):
+    """How ``libcp_pre_cov.so`` reads a device test residual ``y`` [n, *cells] and a centre laid out like it: (y view, centre
+    view or None, (A, B, C), strides of y, strides of the centre, cell order).  The cell axes are relabelled into y's memory
+    order (``canon``'s order, a view) and adjacent ones merged, so a cropped view (``res[:, 1:-1, 1:-1, 1:-1]``), the
+    surrogate's Nt-fastest layout and ``pipeline.row_padded`` / ``time_major`` buffers are read where they lie; y is copied
+    only if its innermost memory axis is not dense or more than three cell axes remain.  A centre that does not fit y's
+    cell order is copied into it (``_same_layout``).  Strides: (sample, A, B) in elements.  The per-cell operands (q, m)
+    follow the flat cell order of the result: ``cov_cells``."""
+    d = y.dim()
+    order = sorted(range(1, d), key=lambda k: (-y.stride(k), k)) if d > 1 else []
+    yv = y.permute(0, *order)
+    cv = centre.permute(0, *order) if centre is not None else None
+    ops = [yv] + ([cv] if cv is not None else [])
+    got = _merge_cells(tuple(yv.shape[1:]), [t.stride()[1:] for t in ops])
+    if got is None and cv is not None and _merge_cells(tuple(yv.shape[1:]), [yv.stride()[1:]]) is not None:
+        cv = _same_layout(centre, order)                 # the centre alone does not fit: into y's order
+        ops[1] = cv
+        got = _merge_cells(tuple(yv.shape[1:]), [t.stride()[1:] for t in ops])
+    if got is None:                                      # y itself is not streamable: a dense copy in logical order
+        order = list(range(1, d))
+        yv = y.contiguous()
+        cv = centre.contiguous() if centre is not None else None
+        ops = [yv] + ([cv] if cv is not None else [])
+        got = _merge_cells(tuple(yv.shape[1:]), [t.stride()[1:] for t in ops])
+    ext, st = got
+    ys = (yv.stride(0), st[0][0], st[0][1])
+    cs = (cv.stride(0), st[1][0], st[1][1]) if cv is not None else (0, 0, 0)
+    return yv, cv, tuple(ext), ys, cs, order
+
+
+def cov_cells(t, order, lead):
+    """A per-cell operand (``lead`` leading non-cell axes) as a dense tensor in the cell order ``order`` of
+    :func:`cov_operands`, cells flattened."""
+    v = t.permute(*range(lead), *[lead + o - 1 for o in order])
+    return v.reshape(*t.shape[:lead], -1).contiguous()
+
+
+def cov_levels_launch(y, q, centre=None, modulation=None, count=None, inside=None):
+    """One pass of ``pre_cov_levels_f32`` over device fp32 ``y`` [n, *cells]: ``q`` [nk] (one half-width per level) or
+    [nk, *cells], optional ``centre`` [n, *cells] and ``modulation`` [*cells].  Marginal: ``count`` int64 [nk] += cells
+    inside; joint: ``inside`` bool [nk, >= n] cleared where a sample has a cell outside.  Asynchronous, no host sync."""
+    n = y.shape[0]
+    nk = q.shape[0]
+    yv, cv, (A, B, C), ys, cs, order = cov_operands(y, centre)
+    per_cell = q.dim() > 1
+    qd = cov_cells(q, order, 1) if per_cell else q.contiguous()
+    md = cov_cells(modulation, order, 0) if modulation is not None else None
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load_cov().pre_cov_levels_f32(
+            _lib.ptr(yv), ys[0], ys[1], ys[2], _lib.ptr(cv), cs[0], cs[1], cs[2], n, A, B, C,
+            _lib.ptr(qd), A * B * C if per_cell else 0, _lib.ptr(md), nk, _lib.ptr(count), _lib.ptr(inside),
+            inside.stride(0) if inside is not None else 0, _lib.stream()), "pre_cov_levels_f32")
+
+
+def _f64(x):
+    """Would numpy (or torch) compute the bounds in float64?  (np.float64 is a Python float.)"""
+    if isinstance(x, torch.Tensor):
+        return x.dtype == torch.float64
+    return isinstance(x, float) or (isinstance(x, np.ndarray) and x.dtype == np.float64)
+
+
+def _levels(qhats):
+    """The levels as given (a list / tuple / array / tensor with the level axis first)."""
+    if isinstance(qhats, (list, tuple)):
+        if any(_f64(q) for q in qhats):
+            return list(qhats), True
+        qhats = np.stack([np.asarray(q, np.float32) for q in qhats])
+    return qhats, _f64(qhats)
+
+
+def _loop_sets(q, centre, modulation):
+    hw = q if modulation is None else q * modulation
+    return [-hw, hw] if centre is None else [centre - hw, centre + hw]
+
+
+def _levels_pass(qhats, y, centre, modulation, joint):
+    """CoverageLevels over the whole of ``y`` on its device: (curve, inside or None, device)."""
+    from . import pipeline
+    ydev, back = _dev(y)
+    if ydev.dim() < 1 or ydev.numel() == 0:
+        raise ValueError("coverage of an empty test set")
+    q = _dev(qhats)[0]
+    c = _dev(centre)[0] if centre is not None else None
+    m = _dev(modulation)[0] if modulation is not None else None
+    cov = pipeline.CoverageLevels(ydev.shape[0], q.shape[0], ydev.device, joint=joint)
+    cov.add_slab(ydev, q, centre=c, modulation=m)
+    return cov, back
+
+
+def emp_cov_levels(qhats, y, centre=None):
+    """``[emp_cov([c - q[k], c + q[k]], y) for k]`` (no centre: ``[-q[k], q[k]]``) -> np.float64 [nk], in ONE pass over
+    ``y`` and one device-to-host copy.  ``qhats``: ``calibrate_multi``'s [nk, *cells] (or [nk])."""
+    qs, wide = _levels(qhats)
+    if wide or _f64(centre):
+        return np.array([emp_cov(_loop_sets(q, centre, None), y) for q in qs], np.float64)
+    cov, _ = _levels_pass(qs, y, centre, None, joint=False)
+    return cov.finish()
+
+
+def emp_cov_joint_levels(qhats, y, modulation, centre=None):
+    """``[emp_cov_joint([c - q[k]*m, c + q[k]*m], y) for k]`` (no centre: ``[-q[k]*m, q[k]*m]``) -> np.float64 [nk], in
+    ONE pass over ``y``.  ``qhats``: the joint q-hats [nk] (fp32, as ``calibrate`` returns them)."""
+    qs, wide = _levels(qhats)
+    if wide or _f64(centre) or _f64(modulation):
+        return np.array([emp_cov_joint(_loop_sets(q, centre, modulation), y) for q in qs], np.float64)
+    cov, _ = _levels_pass(qs, y, centre, modulation, joint=True)
+    return cov.finish()
+
+
+def filter_sims_joint_levels(qhats, y, modulation, centre=None):
+    """``filter_sims_joint`` at every level: bool [nk, n] (torch in -> torch out on y's device, numpy in -> numpy out)."""
+    qs, wide = _levels(qhats)
+    if wide or _f64(centre) or _f64(modulation):
+        rows = [filter_sims_joint(_loop_sets(q, centre, modulation), y) for q in qs]
+        return torch.stack(rows) if isinstance(y, torch.Tensor) else np.stack(rows)
+    cov, back = _levels_pass(qs, y, centre, modulation, joint=True)
+    return back(cov.inside) if isinstance(y, torch.Tensor) else cov.inside.cpu().numpy()

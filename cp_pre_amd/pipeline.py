@@ -21,6 +21,7 @@ process group over RCCL/xGMI):
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -236,6 +237,22 @@ class HipOps:
         HipOps._dist_call("pre_dist_pick_f32", out.device, vals if vals.numel() else None, cnt, off, W, Co, S, slot, rnk,
                           int(slot.shape[1]), out)
 
+    # ---- coverage at several levels in one pass (libcp_pre_cov.so, include/cp_pre_cov.h) ----
+
+    @staticmethod
+    def zeros_coverage(nk, n_local, joint, device):
+        """Marginal: int64 [nk] counts (0); joint: bool [nk, n_local] 'every cell inside so far' (True)."""
+        if joint:
+            return torch.ones(nk, n_local, dtype=torch.bool, device=device)
+        return torch.zeros(nk, dtype=torch.int64, device=device)
+
+    @staticmethod
+    def cov_levels(y, q, centre, modulation, acc):
+        """One pass over ``y`` [n, *cells] for every level of ``q`` ([nk] or [nk, *cells]): ``acc`` (``zeros_coverage``)
+        += cells inside (marginal) / &= every cell inside (joint), with hw = q * modulation and the bounds c -+ hw."""
+        joint = acc.dtype == torch.bool
+        icp.cov_levels_launch(y, q, centre, modulation, count=None if joint else acc, inside=acc if joint else None)
+
 
 def _ranks(n_total, alphas):
     return [icp.kth_index(n_total, n_total, a) for a in alphas]
@@ -400,6 +417,62 @@ class JointCalibration:
             scores = torch.cat(gathered)
         self.all_scores = scores
         return self.ops.kth(scores, _ranks(self.n_total, alphas))
+
+
+class CoverageLevels:
+    """Empirical coverage of a test set at nk calibration levels, streamed and sharded like :class:`JointCalibration`:
+    ``add_slab`` takes the cells of a slab (all local samples; slabs split the cells, as the C3 x-slab job streams them),
+    the ranks of ``group`` split the samples.  ``finish`` returns the group's curve np.float64 [nk], the same on every
+    rank: marginal ``[emp_cov([c - q_k, c + q_k], y) for k]`` over the concatenated set, joint
+    ``[emp_cov_joint([c - q_k*m, c + q_k*m], y) for k]`` (no centre: ``[-hw, hw]``).  fp32 operands only.
+
+    ``add_slab`` launches one pass (``ops.cov_levels``) and neither synchronises nor communicates: it can be captured in
+    a HIP graph.  ``finish`` issues exactly one collective, an all-reduce (SUM) of int64 [nk + 1] - the counts and the
+    local denominator - whose size follows from nk alone, so ranks with unequal ``n_local`` agree; then one host read.
+    ``inside`` (joint): device bool [nk, n_local], the local samples whose every cell so far is inside."""
+
+    def __init__(self, n_local, nk, device, joint=False, group=None, ops=None):
+        if n_local < 1 or nk < 1:
+            raise ValueError(f"CoverageLevels needs n_local >= 1 and nk >= 1 (got {n_local}, {nk})")
+        self.ops = ops or HipOps
+        self.n_local, self.nk, self.device, self.joint, self.group = n_local, nk, device, joint, group
+        self.acc = self.ops.zeros_coverage(nk, n_local, joint, device)
+        self.cells = 0                 # cells of one sample seen so far (host arithmetic on shapes)
+
+    @property
+    def inside(self):
+        return self.acc if self.joint else None
+
+    def add_slab(self, y_slab, qhats_slab, centre=None, modulation=None):
+        """``y_slab`` [n_local, *slab cells]; ``qhats_slab`` [nk] (one half-width per level) or [nk, *slab cells]; the
+        optional ``centre`` is laid out like ``y_slab`` (any strides), ``modulation`` [*slab cells]."""
+        if y_slab.shape[0] != self.n_local:
+            raise ValueError(f"slab of {y_slab.shape[0]} samples, expected n_local = {self.n_local}")
+        if y_slab.numel() == 0:
+            raise ValueError("coverage of an empty slab")
+        if qhats_slab.shape[0] != self.nk or (qhats_slab.dim() > 1 and tuple(qhats_slab.shape[1:]) != tuple(y_slab.shape[1:])):
+            raise ValueError(f"q-hats of shape {tuple(qhats_slab.shape)} for {self.nk} levels of a {tuple(y_slab.shape)} slab")
+        if centre is not None and tuple(centre.shape) != tuple(y_slab.shape):
+            raise ValueError("the centre is laid out like the slab")
+        if modulation is not None and tuple(modulation.shape) != tuple(y_slab.shape[1:]):
+            raise ValueError("the modulation has the slab's cell shape")
+        self.ops.cov_levels(y_slab, qhats_slab, centre, modulation, self.acc)
+        self.cells += y_slab[0].numel()
+
+    def finish(self):
+        if self.cells == 0:
+            raise ValueError("CoverageLevels.finish() before any slab")
+        buf = torch.empty(self.nk + 1, dtype=torch.int64, device=self.acc.device)
+        if self.joint:
+            torch.sum(self.acc, dim=1, out=buf[:self.nk])
+        else:
+            buf[:self.nk].copy_(self.acc)
+        buf[self.nk] = self.n_local if self.joint else self.n_local * self.cells
+        if self.group is not None:
+            torch.distributed.all_reduce(buf, group=self.group)        # the one collective: int64 [nk + 1]
+        host = buf.cpu().numpy()                                         # the one host read
+        # count / total in float64: numpy's mean of a bool array
+        return np.array([float(c) / float(host[self.nk]) for c in host[:self.nk]], np.float64)
 
 
 def time_major(n_local, cells, pad=0, dtype=torch.float32, device=None):
