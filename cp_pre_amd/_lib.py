@@ -107,10 +107,50 @@ COV_SIGNATURES = {
     "pre_cov_levels_f32": _opnd + _opnd + [c_int64] * 4 + [_fp, c_int64, _fp, c_int, _fp, _fp, c_int64, c_void_p],
 }
 
+# libcp_pre_ode.so (include/cp_pre_ode.h): the ODE operators of Utils/ConvOps_0d.py and the fused ODE residuals
+ODE_SO_PATH = os.path.join(_HERE, "libcp_pre_ode.so")
+PRE_ODE_ABI_VERSION = 1
+PRE_ODE_MAX_TAPS, PRE_ODE_MAX_TERMS, PRE_ODE_FLAG_ABS, PRE_ODE_WGRAD_BLOCKS = 7, 6, 1, 1024
+
+
+class PreOdeTerm(ctypes.Structure):
+    """``pre_ode_term_t``: one residual term c[t] * (K * x)[b, t] (field pointer, element strides, coefficient row, taps)."""
+    _fields_ = [("x", c_void_p), ("sB", c_int64), ("sT", c_int64), ("c", c_void_p), ("k", c_int),
+                ("taps", c_float * PRE_ODE_MAX_TAPS)]
+
+
+ODE_SIGNATURES = {
+    "pre_ode_abi_version": [],
+    "pre_ode_stencil_f32": [_fp, _i64p, _fp, _i64p, c_int64, c_int64, POINTER(c_float), c_int, c_int, c_void_p],
+    "pre_ode_residual_f32": [POINTER(PreOdeTerm), c_int, _fp, _i64p, c_int64, c_int64, c_int, c_void_p],
+    "pre_ode_wgrad_f32": [_fp, _i64p, _fp, _i64p, c_int64, c_int64, c_int, _fp, _fp, c_void_p],
+}
+
 _lib = None
 _fft = None
 _dist = None
 _cov = None
+_ode = None
+
+
+def load_ode():
+    """ctypes handle of libcp_pre_ode.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
+    global _ode
+    if _ode is None:
+        if not os.path.exists(ODE_SO_PATH):
+            raise ImportError(f"{ODE_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = ctypes.CDLL(ODE_SO_PATH)
+        lib.pre_ode_abi_version.argtypes, lib.pre_ode_abi_version.restype = [], c_int
+        have = lib.pre_ode_abi_version()
+        if have != PRE_ODE_ABI_VERSION:
+            raise ImportError(f"{ODE_SO_PATH} has ABI version {have}, this binding was written for {PRE_ODE_ABI_VERSION}: "
+                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        for name, argtypes in ODE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        _ode = lib
+    return _ode
 
 
 def load_cov():
