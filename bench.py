@@ -36,7 +36,12 @@ process is one rank; launched bare with N > 1 it SPAWNS the N ranks itself (a fr
 the child's code; WORLD_SIZE != N is an error (exit 2).  --scaling weak (default): --batch samples per
 rank; strong: the --batch samples are split over the ranks.
 
-The default line (--config c3, joint, one GPU) also carries `secondary`: the other BASELINE configurations measured in
+A plain run does what `value` needs and nothing more: it sets up, warms up, times --steps steps, writes --dump-outputs
+if asked and prints the line.  --full adds everything else the benchmark measures or checks, after the timed steps and
+outside `value`: the joint step once more with the full score pass (`ms_per_step_full_score_pass`), the oracle parity
+checks, `secondary` and `cpu_baseline` below (--no-parity, --no-secondary and --no-cpu-baseline trim a --full run).
+
+With --full, the C3 joint line on one GPU also carries `secondary`: the other BASELINE configurations measured in
 the same process after the C3 joint job (whose number stays `value`) - C3 marginal on the same resident slab, the per-rank
 job of the strong-scaled 8-GPU curve ([512,64,512,512] x3 whole grid, joint and marginal, through a one-rank RCCL group) in
 the reference layout and in the reference callers' Nt-fastest layout (`c3_rank8_ntfast`), C4 the way its script runs it
@@ -59,8 +64,8 @@ for output.  The line then carries `dump_outputs` (each array's full shape and t
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (fused
 residual kernel, HIP events on its stream; `achieved` = SURVEY 8(d) bytes: 16 B x the interior
-cells one launch computes, halo planes NOT counted) and `cpu_baseline` (the CPU oracle = the
-reference's own F.conv3d arithmetic, timed on this box's host cores; N=1 only).
+cells one launch computes, halo planes NOT counted) and, with --full, `cpu_baseline` (the CPU oracle = the
+reference's own F.conv3d arithmetic, timed on the host's cores; N=1 only).
 """
 import argparse
 import json
@@ -162,11 +167,14 @@ def parse():
                     help="weak: --batch samples per rank; strong: --batch samples in total, split over the ranks")
     ap.add_argument("--plumbing-check", action="store_true",
                     help="initialise the process group, run one all-reduce, print the rank count and exit (no compute)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what `value` does not need: the full-score-pass step, the oracle "
+                         "parity checks, the other BASELINE configs (c3 joint, one GPU) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default c3 joint line only: do not measure the other BASELINE configs after it")
+                    help="--full, c3 joint line only: do not measure the other BASELINE configs after it")
     ap.add_argument("--no-parity", action="store_true",
-                    help="c3: skip the post-timing oracle check of two samples of the last slab (profiling passes)")
+                    help="--full: skip the post-timing oracle checks (profiling passes)")
     ap.add_argument("--no-prune", action="store_true",
                     help="joint mode: read the whole residual in the score pass instead of the branch-and-bound form")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration")
@@ -176,6 +184,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                   # a plain run: what `value` needs only
+        args.no_cpu_baseline = args.no_secondary = args.no_parity = True
     cfg = CONFIGS[args.config]
     shp = cfg["shape"]
     args.mode = args.mode or cfg["mode"]
@@ -1199,11 +1209,12 @@ def main():
         dumped = dump_outputs(args.dump_outputs, arrays)
 
     # The branch-and-bound score pass makes `value` depend on the data (how much of the residual the bounds let it
-    # skip).  Say by how much: the share of the pass that was read, and the same step with the full pass - one more
-    # step, timed apart, not part of `value`.
+    # skip).  Say by how much: the share of the pass that was read, and (--full) the same step with the full pass - one
+    # more step, timed apart, not part of `value`.
     read_frac = ms_full = qhat_full = None
     if args.mode == "joint" and not args.no_prune:
         read_frac = last_jc[0].score_pass_read_frac()
+    if args.full and args.mode == "joint" and not args.no_prune:
         step(args.warmup + args.steps, res_main, prune=False)         # (untimed: first use of the full-pass kernels)
         sync()
         t1 = time.perf_counter()
@@ -1254,7 +1265,7 @@ def main():
                            if not args.no_prune and pipeline.HipOps.can_prune(res_main[slabs[0]], crop) else "full"}
                           if args.mode == "joint" else {})},
             # data dependence of `value`: share of the score pass's segments that were read (the synthetic residuals are
-            # noise-like: tight bounds), and the same step with the full score pass (--no-prune)
+            # noise-like: tight bounds), and (--full; null otherwise) the same step with the full score pass (--no-prune)
             "score_pass_read_frac": read_frac, "ms_per_step_full_score_pass": ms_full,
             "roofline": {"bound": "hbm", "kernel": "march_kernel<NSMomentum<0>,8,64>",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,

@@ -203,3 +203,39 @@ def test_dump_outputs_end_to_end(tmp_path):
                 assert np.array_equal(a, np.load(tmp_path / "a" / (name + ".npy"))), name
     q = np.load(tmp_path / "a" / "qhat.npy")                       # the q-hat the line reports is the one dumped
     assert [float(q[0]), float(q[-1])] == lines["a"]["qhat_first_last"]
+
+
+def test_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """A plain run does what `value` needs: the oracle checks, the other configs and the CPU baseline are --full's, which
+    --no-parity / --no-secondary / --no-cpu-baseline still trim."""
+    extras = ("no_cpu_baseline", "no_secondary", "no_parity")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not any(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-secondary"])
+    a = bench.parse()
+    assert a.no_secondary and not a.no_parity and not a.no_cpu_baseline
+
+
+@pytest.mark.gpu
+def test_plain_and_full_lines():
+    """On the MI355X, C3 joint at a small size: the plain line has the contract fields and none of --full's extras; the
+    --full line adds the full-score-pass step, the oracle parity (within 1e-5) and the CPU baseline."""
+    c3 = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "40", "--nt", "9", "--nx", "34", "--ny", "64",
+          "--slab", "16"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-secondary", "--cpu-seconds", "0.5"])):
+        r = _run([*c3, *extra], timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["metric"] == "residual-cells/s (PRE eval+calibrate)" and line["unit"] == "cells/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not any(k in plain for k in ("parity", "secondary", "cpu_baseline"))
+    assert plain["ms_per_step_full_score_pass"] is None
+    assert full["parity"]["residual_rel_err"] <= 1e-5 and full["parity"]["qhat_pruned_vs_full_pass_rel"] <= 1e-6
+    assert full["ms_per_step_full_score_pass"] > 0 and full["cpu_baseline"]["value"] > 0 and "secondary" not in full

@@ -45,7 +45,7 @@ for src, (tag, cmd) in CMDS.items():
         continue
     shutil.copy(f, f"{out}/bench_{tag}_kernel_stats.csv")
     with open(f"{out}/bench_{tag}_summary.txt", "w") as o:
-        o.write(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline {cmd}   (MI355X)\n")
+        o.write(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline {cmd}   (MI355X)\n")
         o.write(bench_line(f"gpurun_out/prof/bench_{src}.log") + "\n\n")
         o.write(f"{'kernel':70s} {'calls':>6s} {'avg_ms':>10s} {'total_ms':>10s} {'%':>7s}\n")
         for r in csv.DictReader(open(f)):
@@ -87,7 +87,7 @@ def hbm_report(tag, fetch_src, write_src, kernel, cmd, workload, alg_bytes, halo
         return
     with open(f"{out}/pmc_hbm_{tag}.txt", "w") as o:
         o.write("rocprofv3 --pmc FETCH_SIZE --kernel-trace / --pmc WRITE_SIZE --kernel-trace (separate passes)\n"
-                f"   -- python3 bench.py {cmd}   (MI355X)\n")
+                f"   -- python3 bench.py --full {cmd}   (MI355X)\n")
         o.write("counter unit KiB.  gfx950 corrections (MI355X_MICROARCH.md, HBM): FETCH_SIZE reports 1/2 of the bytes of a 16 B/lane\n"
                 "coalesced streaming read -> x2; WRITE_SIZE is exact for 16 B/lane streaming stores.\n\n")
         for (name, k), (n, avg) in sorted(pm.items(), key=lambda x: (x[0][1], x[0][0])):
@@ -174,7 +174,7 @@ for tag, srcs, mode in (("pmc_sq_c3.txt", ("sq1", "sq2"), "joint"), ("pmc_sq_c3_
     if not sq:
         continue
     with open(f"{out}/{tag}", "w") as o:
-        o.write(f"rocprofv3 --pmc <counters, one group per pass> --kernel-trace -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --batch 1024"
+        o.write(f"rocprofv3 --pmc <counters, one group per pass> --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --batch 1024"
                 f"{' --mode marginal' if mode == 'marginal' else ''}\n"
                 f"(C3 {mode}, quarter batch: 1024 samples per launch, the slab plan of the run; per-dispatch sums over all SEs/XCDs, averaged over dispatches;\n"
                 f" FETCH_SIZE in KiB, x2 for bytes on gfx950)\n\n")
@@ -199,7 +199,7 @@ for e in ("momentum", "energy"):
     if not sq:
         continue
     with open(f"{out}/pmc_sq_c4_{e}.txt", "w") as o:
-        o.write(f"rocprofv3 --pmc <counters, one group per pass> --kernel-trace -- python3 bench.py --config c4 --equation {e} --steps 1 --warmup 0 --no-cpu-baseline\n"
+        o.write(f"rocprofv3 --pmc <counters, one group per pass> --kernel-trace -- python3 bench.py --full --config c4 --equation {e} --steps 1 --warmup 0 --no-cpu-baseline\n"
                 f"(per-dispatch sums over all SEs/XCDs, averaged over dispatches)\n\n")
         for k in sorted({k for (_, k) in sq if k.startswith(OURS)}):
             o.write(k + "\n")

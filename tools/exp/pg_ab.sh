@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1
 for tag in nogroup group nogroup2 group2; do
   if [[ $tag == group* ]]; then export PRE_BENCH_FORCE_GROUP=1; else unset PRE_BENCH_FORCE_GROUP; fi
-  timeout -k 10 300 python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > "$P/$tag.log" 2>&1
+  timeout -k 10 300 python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > "$P/$tag.log" 2>&1
   tail -1 "$P/$tag.log" | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', 'ms_per_step', round(d['ms_per_step'],2), 'eval launch ms', round(d['roofline']['avg_launch_ms'],2), 'full-pass step', round(d['ms_per_step_full_score_pass'],1))"
 done
 export PRE_BENCH_FORCE_GROUP=1

@@ -15,7 +15,7 @@ run() {  # tag, rocprof args..., -- bench args
     echo "== $tag" >&2
     timeout -k 10 500 rocprofv3 "$@" > "$P/bench_$tag.log" 2>&1
 }
-B="python3 $R/bench.py --no-cpu-baseline --no-secondary --no-parity"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-secondary --no-parity"
 if [ "$PART" != "b" ]; then
 run trace    --kernel-trace --stats --output-format csv -d "$P/trace"   -- $B --steps 3 --warmup 1
 run trace_m  --kernel-trace --stats --output-format csv -d "$P/trace_m" -- $B --steps 2 --warmup 1 --mode marginal
