@@ -126,11 +126,43 @@ ODE_SIGNATURES = {
     "pre_ode_wgrad_f32": [_fp, _i64p, _fp, _i64p, c_int64, c_int64, c_int, _fp, _fp, c_void_p],
 }
 
+# libcp_pre_setprop.so (include/cp_pre_setprop.h): PRE set propagation, residual-space intervals to solution bounds
+SETPROP_SO_PATH = os.path.join(_HERE, "libcp_pre_setprop.so")
+PRE_SETPROP_ABI_VERSION = 1
+PRE_SETPROP_MAX_TAPS, PRE_SETPROP_FLAG_F64, PRE_SETPROP_FLAG_CORRELATION = 7, 1, 2
+SETPROP_SIGNATURES = {
+    "pre_setprop_abi_version": [],
+    "pre_setprop_bounds_f64": [_fp, _i64p, _fp, _i64p, c_int64, c_int64, _fp, _fp, _fp, _fp, c_int, c_void_p],
+    "pre_setprop_recipe_f32": [_fp, _i64p, c_int64, c_int64, POINTER(c_double), c_int, _fp, _i64p, _fp, _fp, _fp, _fp, c_int,
+                               c_void_p],
+}
+
 _lib = None
 _fft = None
 _dist = None
 _cov = None
 _ode = None
+_setprop = None
+
+
+def load_setprop():
+    """ctypes handle of libcp_pre_setprop.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
+    global _setprop
+    if _setprop is None:
+        if not os.path.exists(SETPROP_SO_PATH):
+            raise ImportError(f"{SETPROP_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = ctypes.CDLL(SETPROP_SO_PATH)
+        lib.pre_setprop_abi_version.argtypes, lib.pre_setprop_abi_version.restype = [], c_int
+        have = lib.pre_setprop_abi_version()
+        if have != PRE_SETPROP_ABI_VERSION:
+            raise ImportError(f"{SETPROP_SO_PATH} has ABI version {have}, this binding was written for {PRE_SETPROP_ABI_VERSION}: "
+                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        for name, argtypes in SETPROP_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        _setprop = lib
+    return _setprop
 
 
 def load_ode():
