@@ -238,6 +238,54 @@ def _xcorr_impl(field, kernel, nd, flags=0, out=None):
     return from_device(out, origin)
 
 
+def xcorr_pair(a, b, kernel, nd, flags=0, out=None):
+    """``xcorr(a) - xcorr(b)`` (``|.|`` under PRE_FLAG_ABS) in ONE pass over both fields (``pre_pair_stencil3d_f32`` /
+    ``pre_pair_stencil2d_f32``, include/cp_pre_pair.h); None if the library declines (taps off the 7-point star, no
+    unit-stride axis the two fields and the output share): the caller then runs two single-field passes.  Not
+    differentiable: the caller composes when a gradient is wanted."""
+    _check_field(a)
+    _check_field(b)
+    karr = host_kernel(kernel)
+    if karr.ndim != nd:
+        raise RuntimeError(f"expected a {nd}-D kernel, got shape {tuple(karr.shape)}")
+    w, off = taps_of(karr)
+    if nd == 2 and a.dim() == 4:                # [BS,1,Nt,Nx]: the reference squeezes the channel after conv2d
+        a, b = a[:, 0], b[:, 0]
+    if a.dim() != nd + 1 or a.shape != b.shape:
+        raise RuntimeError(f"expected two {nd + 1}-D fields of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    da, origin = to_device(a)
+    db, _ = to_device(b)
+    if not _lib.streamable(da, db):
+        da, db = da.contiguous(), db.contiguous()
+    # PRE_FLAG_HALO_X reads the rows beyond the views: only the caller's own Ny-contiguous device views have them (a staged
+    # copy would be read before its first and past its last byte)
+    if flags & _lib.PRE_FLAG_HALO_X and (da.data_ptr() != a.data_ptr() or db.data_ptr() != b.data_ptr() or
+                                         da.stride(-1) != 1 or db.stride(-1) != 1 or da.stride() != a.stride() or
+                                         db.stride() != b.stride()):
+        raise ValueError("halo_x needs both fields as Ny-contiguous device views of larger grids (no staging copy)")
+    if out is None:
+        out = _lib.empty_like_layout(da, score_rows=bool(flags & _lib.PRE_FLAG_ABS) and origin is None)
+    elif not (out.is_cuda and out.shape == da.shape and out.dtype == torch.float32):
+        raise ValueError("out must be an fp32 device tensor of the field's shape")
+    if out.numel() == 0:
+        return from_device(out, origin)
+    wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
+    ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
+    lib = _lib.load_pair()
+    with torch.cuda.device(da.device):
+        if nd == 3:
+            fa, fb, o = _lib.field(da), _lib.field(db), _lib.field(out)
+            rc = lib.pre_pair_stencil3d_f32(ctypes.byref(fa), ctypes.byref(fb), ctypes.byref(o), wv, ov, len(w), *da.shape, flags,
+                                            _lib.stream())
+        else:
+            rc = lib.pre_pair_stencil2d_f32(_lib.ptr(da), _lib.iarr64(da.stride()), _lib.ptr(db), _lib.iarr64(db.stride()),
+                                            _lib.ptr(out), _lib.iarr64(out.stride()), wv, ov, len(w), *da.shape, flags, _lib.stream())
+    if rc == _lib.PRE_E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "pre_pair_stencil%dd_f32" % nd)
+    return from_device(out, origin)
+
+
 def dense27(kernel):
     """27 host floats of a 3x3x3 operator kernel, or None if it has another shape."""
     k = host_kernel(kernel)

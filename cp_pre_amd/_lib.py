@@ -137,12 +137,51 @@ SETPROP_SIGNATURES = {
                                c_void_p],
 }
 
+# libcp_pre_pair.so (include/cp_pre_pair.h): data-driven residual scores r(a) - r(b) of two field sets in one pass
+PAIR_SO_PATH = os.path.join(_HERE, "libcp_pre_pair.so")
+PRE_PAIR_ABI_VERSION = 1
+PAIR_SIGNATURES = {
+    "pre_pair_abi_version": [],
+    "pre_pair_stencil3d_f32": [_fld, _fld, _fld, POINTER(c_float), POINTER(c_int32), c_int] + [c_int64] * 4 + [c_int, c_void_p],
+    "pre_pair_stencil2d_f32": [_fp, _i64p, _fp, _i64p, _fp, _i64p, POINTER(c_float), POINTER(c_int32), c_int] + [c_int64] * 3 +
+                              [c_int, c_void_p],
+    "pre_pair_linear2_f32": [POINTER(PreField), POINTER(PreField), _fld, POINTER(c_float), POINTER(c_float), c_float] +
+                            [c_int64] * 4 + [c_int, c_void_p],
+    "pre_pair_ns_momentum_f32": [POINTER(PreField), POINTER(PreField), _fld] + [POINTER(c_float)] * 4 + [c_float] * 4 +
+                                [c_int64] * 4 + [c_int, c_void_p],
+    "pre_pair_mhd_continuity_f32": [POINTER(PreField), POINTER(PreField), _fld] + [POINTER(c_float)] * 3 + [c_double] +
+                                   [c_int64] * 4 + [c_int, c_void_p],
+    "pre_pair_burgers_f32": [_fp, _i64p, _fp, _i64p, _fp, _i64p] + [POINTER(c_float)] * 3 + [c_float] * 4 + [c_int64] * 3 +
+                            [c_int, c_void_p],
+}
+
 _lib = None
+_pair = None
 _fft = None
 _dist = None
 _cov = None
 _ode = None
 _setprop = None
+
+
+def load_pair():
+    """ctypes handle of libcp_pre_pair.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
+    global _pair
+    if _pair is None:
+        if not os.path.exists(PAIR_SO_PATH):
+            raise ImportError(f"{PAIR_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = ctypes.CDLL(PAIR_SO_PATH)
+        lib.pre_pair_abi_version.argtypes, lib.pre_pair_abi_version.restype = [], c_int
+        have = lib.pre_pair_abi_version()
+        if have != PRE_PAIR_ABI_VERSION:
+            raise ImportError(f"{PAIR_SO_PATH} has ABI version {have}, this binding was written for {PRE_PAIR_ABI_VERSION}: "
+                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        for name, argtypes in PAIR_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        _pair = lib
+    return _pair
 
 
 def load_setprop():

@@ -1133,6 +1133,10 @@ int launch_mode(int mode, Geom &g, const P &prm, hipStream_t st)
 
 }  // namespace
 
+// pair_march.hip (libcp_pre_pair.so) includes this file for the march and the functors above, defining
+// PRE_STAR_MARCH_TEMPLATES_ONLY: the entry points below belong to libcp_pre_hip.so alone.
+#ifndef PRE_STAR_MARCH_TEMPLATES_ONLY
+
 // Internal: called by stencil_generic.hip when a tap list is star-shaped and the layout allows it.
 // On success *tail_axis / *tail_from describe the columns the streaming kernel did NOT compute (the last
 // extent % 4 cells of the contiguous axis, given as the caller's axis 0=T,1=X,2=Y and first index), or
@@ -1389,3 +1393,5 @@ int pre_spatial2d_linear2_bc_f32(const float *in0, const int64_t s0[3], const fl
 }
 
 }  // extern "C"
+
+#endif  // PRE_STAR_MARCH_TEMPLATES_ONLY

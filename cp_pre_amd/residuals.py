@@ -16,6 +16,19 @@ Two evaluation routes, same numbers:
 
 ``vars`` is [BS,F,Nt,Nx,Ny]; ``boundary=False`` crops one cell per side like the reference
 (a view of the full residual).  ``absolute=True`` returns |residual| (the marginal score).
+
+Data-driven scores (every ``Marginal/`` and ``Joint/`` script, e.g. ``Marginal/NS_Residuals_CP.py:284-289``): every
+``residual*`` method takes ``minus=`` - a second field set of ``vars``' shape (any strides) - and returns
+``r(vars) - r(minus)`` (``|r(vars) - r(minus)|`` with ``absolute=True``), the script's
+``cal_out_residual - cal_pred_residual``.  NS momentum / continuity, MHD continuity / gauss, the wave and advection
+kernels and Burgers read both sets in ONE streaming pass (``libcp_pre_pair.so``, ``include/cp_pre_pair.h``); MHD
+momentum / energy / induction (8-12 views) and JOREK are TWO-PASS: r(vars) into the result, r(minus) into one scratch
+buffer, then an in-place subtract (or |.|).  Where the one-pass kernel declines (a kernel off the star, a layout
+without a shared unit-stride axis) the same two-pass route runs.  The result feeds the existing calibration unchanged:
+``JointCalibration.add_slab(d)``, ``calibrate(|d|)`` / ``marginal_qhat``, ``emp_cov_levels(qhats, d)`` (``centre=None``).
+These equal the scripts' ``modulation_func(a, b)``, ``ncf_metric_joint(a, b, mod)`` and ``emp_cov([c - q*m, c + q*m], y)``
+up to the fp32 rounding of the residuals; coverage in ``d`` form is not bit-identical to the bounds form (a value on
+``c +- q*m`` can round to the other side), the ``centre=`` path stays the exact one.
 """
 from __future__ import annotations
 
@@ -96,6 +109,80 @@ def _attach(res, fields, composed, absolute):
     return _dispatch._Recompute.apply(res, fn, *fields)
 
 
+def _check_minus(vars, minus, device_view=False):
+    """Validate ``minus=`` before any device work: a tensor of ``vars``' shape and dtype on ``vars``' device.
+    ``device_view`` (halo_x, an interior-plane out): both sets must be Ny-contiguous device views, like the x-slab views
+    the flag reads past - views that staging never copies, so the halo rows read are those of the caller's grid."""
+    if not isinstance(minus, torch.Tensor):
+        raise TypeError("minus must be a torch.Tensor of the shape of vars")
+    if minus.dtype != vars.dtype:
+        raise TypeError(f"minus has dtype {minus.dtype}, vars {vars.dtype}")
+    if tuple(minus.shape) != tuple(vars.shape):
+        raise ValueError(f"minus has shape {tuple(minus.shape)}, vars {tuple(vars.shape)}: the two field sets must match")
+    if minus.device != vars.device:
+        raise ValueError(f"minus is on {minus.device}, vars on {vars.device}")
+    if device_view and not (minus.is_cuda and vars.is_cuda and minus.stride(-1) == 1 and vars.stride(-1) == 1):
+        raise ValueError("halo_x / an interior-plane out with minus= need both field sets as Ny-contiguous device views "
+                         "of the same geometry")
+
+
+def _pair_attach(res, fa, fb, composed, absolute):
+    """``_attach`` for a fused r(a) - r(b): a backward recomputes ``composed(*a) - composed(*b)`` and differentiates it,
+    so gradients reach both sets."""
+    if res is None or not _dispatch.needs_grad(*fa, *fb):
+        return res
+    k = len(fa)
+
+    def fn(*f):
+        d = _on_device(f[:k], composed) - _on_device(f[k:], composed)
+        return d.abs() if absolute else d
+    return _dispatch._Recompute.apply(res, fn, *fa, *fb)
+
+
+def _pair_stage(fa, fb):
+    """Device views of both sets, made contiguous together when they share no unit-stride axis."""
+    devs, origin = _stage(list(fa) + list(fb))
+    return devs[:len(fa)], devs[len(fa):], origin
+
+
+def _pair_fused(name, fa, fb, absolute, call):
+    """One paired pass: ``call(da, db, out)`` launches a ``pre_pair_*`` entry; None means 'two-pass instead'."""
+    with torch.no_grad():
+        da, db, origin = _pair_stage(fa, fb)
+        out = _lib.empty_like_layout(da[0], score_rows=absolute and origin is None)
+        with torch.cuda.device(out.device):
+            ok = _fused_call(name, lambda: call(da, db, out))
+    return _dispatch.from_device(out, origin) if ok else None
+
+
+def _two_pass(run, fa, fb, absolute):
+    """The two-pass route: ``run(fields)`` (a single-set fused pass on device tensors, or None) for each set, then an
+    in-place subtract / |.| on the first result.  None if the single-set pass declines too."""
+    with torch.no_grad():
+        da, db = [_dispatch.to_device(f) for f in fa], [_dispatch.to_device(f) for f in fb]
+        origin = next((o for _, o in da + db if o is not None), None)
+        a = run([d for d, _ in da])
+        if a is None:
+            return None
+        b = run([d for d, _ in db])
+        if b is None:
+            return None
+        a.sub_(b)
+        if absolute:
+            a.abs_()
+    return _dispatch.from_device(a, origin)
+
+
+def _pair_composed(method, vars, minus, boundary, crop, absolute):
+    """``method(vars) - method(minus)`` on device (each a single-set route of its own, autograd included), returned
+    where ``vars`` lives: what runs when neither pass can be fused."""
+    dv, origin = _dispatch.to_device(vars)
+    dm, _ = _dispatch.to_device(minus)
+    d = method(dv, True) - method(dm, True)
+    d = _dispatch.from_device(d.abs() if absolute else d, origin)
+    return d if boundary else d[crop]
+
+
 def _finish(res, boundary, crop, absolute, already_abs):
     if absolute and not already_abs:
         res = res.abs()
@@ -110,9 +197,24 @@ class NavierStokes(_Residual2D):
         super().__init__(**kw)
         self.dt, self.dx, self.dy, self.nu = dt, dx, dy, nu
 
-    def residual_continuity(self, vars, boundary=False, absolute=False):
+    def residual_continuity(self, vars, boundary=False, absolute=False, minus=None):
+        """``minus``: r(vars) - r(minus) in one pass (``pre_pair_linear2_f32``; see the module docstring)."""
         u, v = vars[:, 0], vars[:, 1]
         ratio = self.dx / self.dy
+        if minus is not None:
+            _check_minus(vars, minus)
+            fa, fb = (u, v), (minus[:, 0], minus[:, 1])
+            res = None
+            ks = self._k27(self.D_x, self.D_y) if self._want_fused(vars, minus) else None
+            if ks is not None:
+                flags = _lib.PRE_FLAG_ABS if absolute else 0
+                res = _pair_fused("pre_pair_linear2_f32", fa, fb, absolute, lambda da, db, out: _lib.load_pair().pre_pair_linear2_f32(
+                    (_lib.PreField * 2)(*map(_lib.field, da)), (_lib.PreField * 2)(*map(_lib.field, db)),
+                    ctypes.byref(_lib.field(out)), *ks, float(ratio), *out.shape, flags, _lib.stream()))
+            if res is None:
+                return _pair_composed(self.residual_continuity, vars, minus, boundary, _CROP3, absolute)
+            res = _pair_attach(res, fa, fb, lambda u, v: self.D_x(u) + ratio * self.D_y(v), absolute)
+            return _finish(res, boundary, _CROP3, absolute, True)
         res = None
         if self._want_fused(vars):
             from .vector_convops import linear2
@@ -122,7 +224,7 @@ class NavierStokes(_Residual2D):
             res = _on_device((u, v), lambda u, v: self.D_x(u) + ratio * self.D_y(v))
         return _finish(res, boundary, _CROP3, absolute, done_abs)
 
-    def residual_momentum(self, vars, boundary=False, absolute=False, out=None, skip_t_rim=False, halo_x=False):
+    def residual_momentum(self, vars, boundary=False, absolute=False, out=None, skip_t_rim=False, halo_x=False, minus=None):
         """``out``: optional preallocated device tensor [BS,Nt,Nx,Ny] for the uncropped residual
         (fused route only; lets a streaming driver reuse one buffer).  ``skip_t_rim``: the caller
         crops the first and last time plane anyway, so they need not be computed or stored
@@ -135,7 +237,9 @@ class NavierStokes(_Residual2D):
         x0 - 1 and x1 lie in the same memory: they are read as the x-neighbours of the slab's first and last row instead
         of the zero padding (``PRE_FLAG_HALO_X``), so the slab's residual rows are those of the whole grid.  What an
         x-slab driver wants: the T axis stays whole and a slab re-reads 2 rows of Nx_slab instead of 2 planes of
-        Nt_slab.  Fused route only (raises otherwise)."""
+        Nt_slab.  Fused route only (raises otherwise).
+        ``minus``: r(vars) - r(minus) (the data-driven score) in one pass of both sets (``pre_pair_ns_momentum_f32``);
+        ``out``, ``skip_t_rim`` and ``halo_x`` apply to both sets with the same validation."""
         u, v, p = vars[:, 0], vars[:, 1], vars[:, 2]
         dt, dx, dy, nu = self.dt, self.dx, self.dy, self.nu
         D_t, D_x, D_y, D_xx_yy = self.D_t, self.D_x, self.D_y, self.D_xx_yy
@@ -144,6 +248,8 @@ class NavierStokes(_Residual2D):
             res_x = D_t(u)*dx*dy + u*D_x(u)*dt*dy + v*D_y(u)*dt*dx - nu*D_xx_yy(u)*dt + D_x(p)*dt*dy
             res_y = D_t(v)*dx*dy + u*D_x(v)*dt*dx + v*D_y(v)*dt*dy - nu*D_xx_yy(v)*dt + D_y(p)*dt*dx
             return res_x + res_y
+        if minus is not None:
+            return self._momentum_minus(vars, minus, boundary, absolute, out, skip_t_rim, halo_x, composed)
         ks = self._k27(self.D_t, self.D_x, self.D_y, self.D_xx_yy) if self._want_fused(vars) else None
         if ks is not None:
             with torch.no_grad():
@@ -183,6 +289,58 @@ class NavierStokes(_Residual2D):
             raise RuntimeError("halo_x: only the fused route reads the halo rows")
         return _finish(_on_device((u, v, p), composed), boundary, _CROP3, absolute, False)
 
+    def _momentum_minus(self, vars, minus, boundary, absolute, out, skip_t_rim, halo_x, composed):
+        out_given = out
+        interior_out = skip_t_rim and out is not None and out.dim() == 4 and vars.dim() == 5 and out.shape[1] == vars.shape[2] - 2
+        _check_minus(vars, minus, device_view=halo_x or interior_out)
+        fa, fb = (vars[:, 0], vars[:, 1], vars[:, 2]), (minus[:, 0], minus[:, 1], minus[:, 2])
+        ks = self._k27(self.D_t, self.D_x, self.D_y, self.D_xx_yy) if self._want_fused(vars, minus) else None
+        ok = False
+        if ks is not None:
+            with torch.no_grad():
+                da, db, origin = _pair_stage(fa, fb)
+                du = da[0]
+                if out is None:
+                    out = _lib.empty_like_layout(du, score_rows=absolute and origin is None)
+                interior = (skip_t_rim and out.dim() == 4 and du.shape[1] >= 3 and
+                            tuple(out.shape) == (du.shape[0], du.shape[1] - 2, du.shape[2], du.shape[3]))
+                if not (out.is_cuda and out.dtype == torch.float32 and (out.shape == du.shape or interior)):
+                    raise ValueError("out must be an fp32 device tensor of the field shape "
+                                     "(or, with skip_t_rim, of its interior planes [BS,Nt-2,Nx,Ny])")
+                dense_planes = out.dim() == 4 and out.stride(3) == 1 and out.stride(2) == out.shape[3]
+                if interior and not (dense_planes and origin is None and not _dispatch.needs_grad(*fa, *fb)):
+                    raise ValueError("an interior-plane out needs device-resident fields, dense [Nx,Ny] planes and no autograd")
+                if halo_x and (origin is not None or _dispatch.needs_grad(*fa, *fb) or
+                               any(d.data_ptr() != f.data_ptr() or d.stride(3) != 1 for d, f in zip(da + db, fa + fb))):
+                    raise ValueError("halo_x needs device-resident, Ny-contiguous views of a larger grid and no autograd")
+                flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_INTERIOR_T if skip_t_rim else 0) | \
+                        (_lib.PRE_FLAG_OUT_INTERIOR_T if interior else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
+                a3, b3, fo = (_lib.PreField * 3)(*map(_lib.field, da)), (_lib.PreField * 3)(*map(_lib.field, db)), _lib.field(out)
+                with torch.cuda.device(du.device):
+                    ok = _fused_call("pre_pair_ns_momentum_f32", lambda: _lib.load_pair().pre_pair_ns_momentum_f32(
+                        a3, b3, ctypes.byref(fo), *ks, float(self.dt), float(self.dx), float(self.dy), float(self.nu),
+                        *du.shape, flags, _lib.stream()))
+                if interior and ok:
+                    return out if boundary else out[..., 1:-1, 1:-1]
+            if ok:
+                res = _pair_attach(_dispatch.from_device(out, origin), fa, fb, composed, absolute)
+                return _finish(res, boundary, _CROP3, absolute, True)
+            if not _dispatch.needs_grad(*fa, *fb):
+                # TWO-PASS (the general-star tap structure, whose paired kernel does not fit the registers): the single-set
+                # fused pass of each set, then an in-place subtract / |.|
+                with torch.no_grad():
+                    (dv, origin), (dm, _) = _dispatch.to_device(vars), _dispatch.to_device(minus)
+                    a = self.residual_momentum(dv, True, out=out_given, skip_t_rim=skip_t_rim, halo_x=halo_x)
+                    scratch = torch.empty_like(out_given) if interior_out and out_given is not None else None
+                    a.sub_(self.residual_momentum(dm, True, out=scratch, skip_t_rim=skip_t_rim, halo_x=halo_x))
+                    if absolute:
+                        a.abs_()
+                a = _dispatch.from_device(a, origin)
+                return a if boundary else (a[..., 1:-1, 1:-1] if a.shape[1] == vars.shape[2] - 2 else a[_CROP3])
+        if halo_x:
+            raise RuntimeError("halo_x: only the fused route reads the halo rows")
+        return _pair_composed(self.residual_momentum, vars, minus, boundary, _CROP3, absolute)
+
     _WALLS = {'top': 0, 'bottom': 1, 'left': 2, 'right': 3}
 
     def periodic_bc_residual(self, u, wall='right'):
@@ -213,8 +371,8 @@ class PRE_NS(NavierStokes):
     def __init__(self, dt, dx, dy, **kw):
         super().__init__(dt, dx, dy, nu=0.001, **kw)
 
-    def residual(self, vars, boundary=False):
-        return self.residual_momentum(vars, boundary)
+    def residual(self, vars, boundary=False, minus=None):
+        return self.residual_momentum(vars, boundary, minus=minus)
 
 
 # ======================================================================= MHD
@@ -262,18 +420,65 @@ class MHD(_Residual2D):
                                "and star-shaped operator kernels")
         return _dispatch.from_device(out, origin) if ok else None
 
-    def residual_continuity(self, vars, boundary=False, absolute=False, halo_x=False, out=None):
+    def _pair_continuity(self, vars, minus, absolute, halo_x, out):
+        """r(vars) - r(minus) of the continuity equation in one pass (``pre_pair_mhd_continuity_f32``); None -> two-pass."""
+        ks = self._k27(self.D_t, self.D_x, self.D_y) if self._want_fused(vars, minus) else None
+        if ks is None or vars.shape[1] < 3:
+            return None
+        fa, fb = [vars[:, i] for i in range(3)], [minus[:, i] for i in range(3)]
+        with torch.no_grad():
+            da, db, origin = _pair_stage(fa, fb)
+        if halo_x and (origin is not None or _dispatch.needs_grad(vars, minus) or
+                       any(d.data_ptr() != f.data_ptr() or d.stride(3) != 1 for d, f in zip(da + db, fa + fb))):
+            raise ValueError("halo_x needs device-resident, Ny-contiguous views of a larger grid and no autograd")
+        given = out is not None
+        if given and not (out.is_cuda and out.dtype == torch.float32 and out.shape == da[0].shape and origin is None
+                          and not _dispatch.needs_grad(vars, minus)):
+            raise ValueError("out must be an fp32 device tensor of the field shape, the fields device-resident, no autograd")
+        if not given:
+            out = _lib.empty_like_layout(da[0], score_rows=absolute and origin is None)
+        a3, b3, fo = (_lib.PreField * 3)(*map(_lib.field, da)), (_lib.PreField * 3)(*map(_lib.field, db)), _lib.field(out)
+        flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
+        with torch.cuda.device(out.device):
+            ok = _fused_call("pre_pair_mhd_continuity_f32", lambda: _lib.load_pair().pre_pair_mhd_continuity_f32(
+                a3, b3, ctypes.byref(fo), *ks, float(self.gamma), *out.shape, flags, _lib.stream()))
+        return _dispatch.from_device(out, origin) if ok else None
+
+    def _minus(self, eq, vars, minus, boundary, absolute, halo_x, out, fields_of, composed):
+        """``residual_<eq>(..., minus=)``: one pass (continuity), else TWO-PASS - the single-set fused pass of ``vars``
+        into the result (``out`` if given), that of ``minus`` into one scratch buffer, an in-place subtract (or |.|) -
+        else the composed difference."""
+        _check_minus(vars, minus, device_view=halo_x)
+        res = self._pair_continuity(vars, minus, absolute, halo_x, out) if eq == 'continuity' else None
+        if res is None:
+            first = [out]
+
+            def run(f):
+                o, first[0] = first[0], None
+                return self._fused(eq, f[0], False, halo_x, o)
+            res = _two_pass(run, (vars,), (minus,), absolute)
+        if res is None:
+            return _pair_composed(getattr(self, 'residual_' + eq), vars, minus, boundary, _CROP3, absolute)
+        res = _pair_attach(res, fields_of(vars), fields_of(minus), composed, absolute)
+        return _finish(res, boundary, _CROP3, absolute, True)
+
+    def residual_continuity(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
+        """``minus``: r(vars) - r(minus) in one pass (``pre_pair_mhd_continuity_f32``)."""
         D_t, D_x, D_y = self.D_t, self.D_x, self.D_y
         fields = (vars[:, 0], vars[:, 1], vars[:, 2])
 
         def composed(rho, u, v):
             return D_t(rho) + u*D_x(rho) + rho*D_x(u) + v*D_y(rho) + rho*D_y(v)
+        if minus is not None:
+            return self._minus('continuity', vars, minus, boundary, absolute, halo_x, out,
+                               lambda x: (x[:, 0], x[:, 1], x[:, 2]), composed)
         res = _attach(self._fused('continuity', vars, absolute, halo_x, out), fields, composed, absolute)
         if res is None:
             return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
         return _finish(res, boundary, _CROP3, absolute, True)
 
-    def residual_momentum(self, vars, boundary=False, absolute=False, halo_x=False, out=None):
+    def residual_momentum(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
+        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_minus``)."""
         D_t, D_x, D_y = self.D_t, self.D_x, self.D_y
         fields = tuple(vars[:, i] for i in range(6))
 
@@ -281,12 +486,15 @@ class MHD(_Residual2D):
             res_x = D_t(u) + u*D_x(u) + (1/rho)*D_x(p) - 2*(Bx/rho)*D_x(Bx) + v*D_y(u) - (By/rho)*D_y(Bx) - (Bx/rho)*D_y(By)
             res_y = D_t(v) + u*D_x(v) + (1/rho)*D_y(p) - 2*(By/rho)*D_y(By) + v*D_y(v) - (By/rho)*D_x(Bx) - (Bx/rho)*D_x(By)
             return res_x + res_y
+        if minus is not None:
+            return self._minus('momentum', vars, minus, boundary, absolute, halo_x, out, lambda x: tuple(x[:, i] for i in range(6)), composed)
         res = _attach(self._fused('momentum', vars, absolute, halo_x, out), fields, composed, absolute)
         if res is None:
             return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
         return _finish(res, boundary, _CROP3, absolute, True)
 
-    def residual_energy(self, vars, boundary=False, absolute=False, halo_x=False, out=None):
+    def residual_energy(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
+        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_minus``)."""
         D_t, D_x, D_y, gamma = self.D_t, self.D_x, self.D_y, self.gamma
         fields = tuple(vars[:, i] for i in range(6))
 
@@ -294,12 +502,15 @@ class MHD(_Residual2D):
             p_gas = p - 0.5*(Bx**2 + By**2)
             return (D_t(rho) + u*D_x(p) + v*D_y(p) + (gamma-2)*(u*Bx+v*By)*(D_x(Bx) + D_y(By))
                     + (gamma*p_gas+By**2)*D_x(u) + (gamma*p_gas+Bx**2)*D_y(v) - Bx*By*(D_y(u) + D_x(v)))
+        if minus is not None:
+            return self._minus('energy', vars, minus, boundary, absolute, halo_x, out, lambda x: tuple(x[:, i] for i in range(6)), composed)
         res = _attach(self._fused('energy', vars, absolute, halo_x, out), fields, composed, absolute)
         if res is None:
             return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
         return _finish(res, boundary, _CROP3, absolute, True)
 
-    def residual_induction(self, vars, boundary=False, absolute=False, halo_x=False, out=None):
+    def residual_induction(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
+        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_minus``)."""
         D_t, D_x, D_y = self.D_t, self.D_x, self.D_y
         fields = (vars[:, 1], vars[:, 2], vars[:, 4], vars[:, 5])
 
@@ -307,13 +518,30 @@ class MHD(_Residual2D):
             res_x = D_t(Bx) - By*D_y(u) + Bx*D_y(v) - v*D_y(Bx) + u*D_y(By)
             res_y = D_t(By) + By*D_x(u) - Bx*D_x(v) - v*D_x(Bx) + u*D_x(By)
             return res_x + res_y
+        if minus is not None:
+            return self._minus('induction', vars, minus, boundary, absolute, halo_x, out, lambda x: (x[:, 1], x[:, 2], x[:, 4], x[:, 5]), composed)
         res = _attach(self._fused('induction', vars, absolute, halo_x, out), fields, composed, absolute)
         if res is None:
             return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
         return _finish(res, boundary, _CROP3, absolute, True)
 
-    def residual_gauss(self, vars, boundary=False, absolute=False):
+    def residual_gauss(self, vars, boundary=False, absolute=False, minus=None):
+        """``minus``: r(vars) - r(minus) in one pass (``pre_pair_linear2_f32``)."""
         Bx, By = vars[:, 4], vars[:, 5]
+        if minus is not None:
+            _check_minus(vars, minus)
+            fa, fb = (Bx, By), (minus[:, 4], minus[:, 5])
+            res = None
+            ks = self._k27(self.D_x, self.D_y) if self._want_fused(vars, minus) else None
+            if ks is not None:
+                flags = _lib.PRE_FLAG_ABS if absolute else 0
+                res = _pair_fused("pre_pair_linear2_f32", fa, fb, absolute, lambda da, db, out: _lib.load_pair().pre_pair_linear2_f32(
+                    (_lib.PreField * 2)(*map(_lib.field, da)), (_lib.PreField * 2)(*map(_lib.field, db)),
+                    ctypes.byref(_lib.field(out)), *ks, 1.0, *out.shape, flags, _lib.stream()))
+            if res is None:
+                return _pair_composed(self.residual_gauss, vars, minus, boundary, _CROP3, absolute)
+            res = _pair_attach(res, fa, fb, lambda Bx, By: self.D_x(Bx) + self.D_y(By), absolute)
+            return _finish(res, boundary, _CROP3, absolute, True)
         res = None
         if self._want_fused(vars):
             from .vector_convops import linear2
@@ -393,8 +621,19 @@ class JOREK:
                 _lib.PRE_FLAG_ABS if absolute else 0, _lib.stream()))
         return _dispatch.from_device(out, origin) if ok else None
 
-    def residual_continuity(self, vars, boundary=False, norms=False, absolute=False):
-        """:207-221."""
+    def _minus(self, eq, vars, minus, boundary, absolute, composed, coef, method):
+        """r(vars) - r(minus), TWO-PASS: the single-set fused pass of each set, then an in-place subtract (or |.|)."""
+        _check_minus(vars, minus)
+        k = 2 if eq == 0 else 3
+        fa, fb = self.unstack_fields(vars)[:k], self.unstack_fields(minus)[:k]
+        res = _two_pass(lambda f: self._fused(eq, tuple(f), coef, False), fa, fb, absolute)
+        if res is None:
+            return _pair_composed(method, vars, minus, boundary, _CROP3, absolute)
+        res = _pair_attach(res, fa, fb, composed, absolute)
+        return _finish(res, boundary, _CROP3, absolute, True)
+
+    def residual_continuity(self, vars, boundary=False, norms=False, absolute=False, minus=None):
+        """:207-221.  ``minus``: r(vars) - r(minus), two-pass (``_minus``)."""
         D_t, D_R, D_Z, D_RR, D_ZZ = self._ops()
         rho, phi, _ = self.unstack_fields(vars)
         if norms and (self.dx is None or self.dy is None or self.dt is None):
@@ -414,13 +653,16 @@ class JOREK:
             coef = [float(2*dx*dy), float(dt), float((2*dt*dy)*2), float((4*dt)*D)]
         else:
             coef = [1.0, 1.0, 2.0, float(torch.tensor(self.D, dtype=torch.float32))]
+        if minus is not None:
+            return self._minus(0, vars, minus, boundary, absolute, composed, coef,
+                               lambda x, b: self.residual_continuity(x, b, norms))
         res = _attach(self._fused(0, (rho, phi), coef, absolute), (rho, phi), composed, absolute)
         if res is None:
             return _finish(_on_device((rho, phi), composed), boundary, _CROP3, absolute, False)
         return _finish(res, boundary, _CROP3, absolute, True)
 
-    def residual_temperature(self, vars, boundary=False, norms=False, absolute=False):
-        """:224-243."""
+    def residual_temperature(self, vars, boundary=False, norms=False, absolute=False, minus=None):
+        """:224-243.  ``minus``: r(vars) - r(minus), two-pass (``_minus``)."""
         if norms:
             raise Exception("Norm not implemented yet")              # (as the reference, :230)
         D_t, D_R, D_Z, D_RR, D_ZZ = self._ops()
@@ -434,6 +676,8 @@ class JOREK:
                 K * (D_RR(T) + (1/R)*D_R(T) + D_ZZ(T))
         t = lambda v: torch.tensor(v, dtype=torch.float32)
         coef = [float(2 * t(self.gamma)), 0.0, 0.0, float(t(self.K))]
+        if minus is not None:
+            return self._minus(1, vars, minus, boundary, absolute, composed, coef, self.residual_temperature)
         res = _attach(self._fused(1, (rho, phi, T), coef, absolute), (rho, phi, T), composed, absolute)
         if res is None:
             return _finish(_on_device((rho, phi, T), composed), boundary, _CROP3, absolute, False)
@@ -447,8 +691,8 @@ class PRE_MHD(MHD):
         super().__init__(gamma=5 / 3, **kw)
         self.dt, self.dx, self.dy = dt, dx, dy
 
-    def residual(self, vars, boundary=False):
-        return self.residual_energy(vars, boundary)
+    def residual(self, vars, boundary=False, minus=None):
+        return self.residual_energy(vars, boundary, minus=minus)
 
 
 # ======================================================================= linear: wave / advection
@@ -463,13 +707,20 @@ class PRE_Wave:
         c = torch.tensor(c, dtype=torch.float32)
         self.D.kernel = D_tt.kernel - ((c * dt / dx) ** 2).to(device) * D_xx_yy.kernel
 
-    def residual(self, uu, boundary=False, absolute=False, halo_x=False, out=None):
-        """``out``: optional fp32 device tensor of the field's shape for the uncropped residual (any batch stride over dense
+    def residual(self, uu, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
+        """``minus``: r(uu) - r(minus) in one pass of both fields (``pre_pair_stencil3d_f32``); ``halo_x`` / ``out`` apply
+        to both (two single-field passes and an in-place subtract where the paired pass declines).
+        ``out``: optional fp32 device tensor of the field's shape for the uncropped residual (any batch stride over dense
         [Nt,Nx,Ny] blocks: ``pipeline.row_padded`` - the per-cell select that follows is 4 % faster on rows that are not
         a power of two apart).  ``halo_x``: ``uu`` is an x-slab ``full[..., x0:x1, :]`` whose rows x0 - 1 and x1 lie in the same device memory and
         are read instead of the zero padding (``PRE_FLAG_HALO_X``, see ``NavierStokes.residual_momentum``)."""
+        if minus is not None:
+            _check_minus(uu, minus, device_view=halo_x)
+            minus = minus[:, 0] if minus.dim() == 5 else minus
         uu = uu[:, 0] if uu.dim() == 5 else uu
         flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
+        if minus is not None:
+            return self._minus(uu, minus, boundary, absolute, halo_x, out, flags)
         if halo_x and not (uu.is_cuda and uu.stride(-1) == 1 and not _dispatch.needs_grad(uu, self.D.kernel)):
             raise ValueError("halo_x needs a device-resident, Ny-contiguous view of a larger grid and no autograd")
         if out is not None:
@@ -478,6 +729,24 @@ class PRE_Wave:
             res = _dispatch._xcorr_impl(uu, self.D.kernel, 3, flags, out=out)
         else:
             res = _dispatch.xcorr(uu, self.D.kernel, nd=3, flags=flags)  # (raises if no kernel reads the halo rows)
+        return res if boundary else res[_CROP3]
+
+
+    def _minus(self, uu, mm, boundary, absolute, halo_x, out, flags):
+        if _dispatch.needs_grad(uu, mm, self.D.kernel):
+            if halo_x or out is not None:
+                raise ValueError("halo_x / out need device-resident fields and no autograd")
+            return _pair_composed(lambda x, b: self.residual(x, b), uu, mm, boundary, _CROP3, absolute)
+        if (halo_x or out is not None) and not (uu.is_cuda and mm.is_cuda):
+            raise ValueError("halo_x / out need device-resident fields and no autograd")
+        (uu, origin), (mm, _) = _dispatch.to_device(uu), _dispatch.to_device(mm)
+        res = _dispatch.xcorr_pair(uu, mm, self.D.kernel, 3, flags, out=out)
+        if res is None:                       # two-pass: r(uu) into the result, r(mm) into a scratch buffer, subtract
+            res = _dispatch._xcorr_impl(uu, self.D.kernel, 3, flags & _lib.PRE_FLAG_HALO_X, out=out)
+            res.sub_(_dispatch._xcorr_impl(mm, self.D.kernel, 3, flags & _lib.PRE_FLAG_HALO_X))
+            if absolute:
+                res.abs_()
+        res = _dispatch.from_device(res, origin)
         return res if boundary else res[_CROP3]
 
 
@@ -490,7 +759,16 @@ class Advection:
         self.D = ConvOperator1D()
         self.D.kernel = D_t.kernel + (v * disc * dt / dx) * D_x.kernel
 
-    def residual(self, uu, boundary=False, absolute=False):
+    def residual(self, uu, boundary=False, absolute=False, minus=None):
+        """``minus``: r(uu) - r(minus) in one pass of both fields (``pre_pair_stencil2d_f32``)."""
+        if minus is not None:
+            _check_minus(uu, minus)
+            res = None
+            if not _dispatch.needs_grad(uu, minus, self.D.kernel):
+                res = _dispatch.xcorr_pair(uu, minus, self.D.kernel, 2, _lib.PRE_FLAG_ABS if absolute else 0)
+            if res is None:
+                return _pair_composed(lambda x, b: self.residual(x, b), uu, minus, boundary, _CROP2, absolute)
+            return res if boundary else res[_CROP2]
         res = _dispatch.xcorr(uu, self.D.kernel, nd=2, flags=_lib.PRE_FLAG_ABS if absolute else 0)
         return res if boundary else res[_CROP2]
 
@@ -508,13 +786,26 @@ class Burgers:
         # the script turns the three coefficients into fp32 0-d tensors first
         self.dx, self.dt, self.nu = (torch.tensor(v, dtype=torch.float32) for v in (dx, dt, nu))
 
-    def residual(self, uu, boundary=False, absolute=False):
+    def residual(self, uu, boundary=False, absolute=False, minus=None):
+        """``minus``: r(uu) - r(minus) in one pass of both fields (``pre_pair_burgers_f32``)."""
         dx, dt, nu = self.dx, self.dt, self.nu
         def composed(uu):
             dxd, dtd, nud = (c.to(uu.device) for c in (dx, dt, nu))
             return dxd * self.D_t(uu) + dtd * uu * self.D_x(uu) - nud * self.D_xx(uu) * (2 * dtd / dxd)
         fused = self.fused and uu.numel() > 0 and not _dispatch.needs_grad(self.D_t.kernel, self.D_x.kernel, self.D_xx.kernel)
         ks = [_dispatch.dense9(o.kernel) for o in (self.D_t, self.D_x, self.D_xx)] if fused else [None]
+        if minus is not None:
+            _check_minus(uu, minus)
+            res = None
+            if all(k is not None for k in ks) and uu.dim() == 3:
+                c3, flags = float(2 * dt / dx), _lib.PRE_FLAG_ABS if absolute else 0
+                res = _pair_fused("pre_pair_burgers_f32", (uu,), (minus,), absolute, lambda da, db, out: _lib.load_pair().pre_pair_burgers_f32(
+                    _lib.ptr(da[0]), _lib.iarr64(da[0].stride()), _lib.ptr(db[0]), _lib.iarr64(db[0].stride()), _lib.ptr(out),
+                    _lib.iarr64(out.stride()), *ks, float(dx), float(dt), float(nu), c3, *out.shape, flags, _lib.stream()))
+            if res is None:
+                return _pair_composed(lambda x, b: self.residual(x, b), uu, minus, boundary, _CROP2, absolute)
+            res = _pair_attach(res, (uu,), (minus,), composed, absolute)
+            return res if boundary else res[_CROP2]
         if all(k is not None for k in ks) and uu.dim() == 3:
             with torch.no_grad():
                 (du,), origin = _stage((uu,))
