@@ -339,6 +339,158 @@ moments_segmax_kernel(const float *__restrict__ a, long long row_stride, int n, 
         }
 }
 
+// The many-plane pass with 16-byte lanes (replaces <16,1> where X*Y, row_stride and the base allow float4 loads).  A
+// 1024-thread block owns 1024 consecutive cells of one 16-plane chunk: wave w holds planes 4*(w&3) .. +3 of the chunk for
+// the 256 cells (w>>2)*256 .. +255, 4 cells per lane, so a sample costs a wave 4 `buffer_load_dwordx4` of 1 KB instead of
+// 16 dword loads of 256 B, and a lane keeps 4 planes x 4 cells x 2 fp64 sums.  A DPP row (16 lanes = 64 cells) is one
+// segment: row_shr 1/2/4/8 leave its maximum over the wave's 4 planes in the row's last lane, which puts it in LDS; every
+// MS4_US samples one barrier (LDS only: the next samples' loads stay in flight), after which 16 threads per sample take
+// the maximum over the 4 plane groups and store the block's 16 segments as one 64-byte run of segmax.
+// Measured against the alternatives (profiles/moments4/README.md): blocks of 256 or 512 cells (16- and 32-byte segmax runs),
+// 16 samples between barriers and splitting the batch axis for 512 or 1024 such blocks were slower; the stream is read
+// once and its loads are `nt` (aux = 2): 7-12 % less time than default-policy loads on the four A/B shapes.
+constexpr int MS4_US = 8;       // samples between two barriers (even)
+constexpr int MS4_CG = 4;       // groups of 256 cells per block (4 waves each): a block stores 16 * MS4_CG bytes per sample
+constexpr int MS4_NT = 256 * MS4_CG, MS4_NW = 4 * MS4_CG;     // threads and waves per block
+constexpr int MS4_WANT = 256;   // 1024-thread blocks the float4 pass wants at least (more = the batch axis split finer)
+constexpr int MS4_AUX = 2;      // cache policy of the streamed loads: nt
+typedef unsigned int ms4_u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void ms4_barrier()     // orders LDS traffic only: the global prefetches stay in flight
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// the wave's 4 planes of sample i: `au` = plane 0 of the wave's planes in sample 0 (wave-uniform), `cb` the BYTE offset of the
+// lane's first cell.  A plane past the chunk's last (k >= nt) gets a descriptor of 0 bytes: its load returns zeros
+// without touching memory, so the loop has no branch around a load (a branch makes the compiler wait for every load in flight)
+__device__ __forceinline__ void ms4_load(const float *au, unsigned int cb, long long row_stride, long long plane, int i, int nt,
+                                         ms4_u32x4 (&v)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float *>(au + ((long long)i * row_stride + k * plane)), 0, k < nt ? (unsigned int)plane * 4u : 0u, 0x00020000);
+        v[k] = __builtin_amdgcn_raw_buffer_load_b128(r, (int)cb, 0, MS4_AUX);
+    }
+}
+
+// adds one sample to the sums and returns the lane's max |x| over its scored cells (bit patterns, NaN on top, as ms_use;
+// the zeros of a missing plane add +0 to sums that are never stored and nothing to the maximum)
+__device__ __forceinline__ unsigned int ms4_use(const ms4_u32x4 (&v)[4], const bool (&scored)[4], double (&s)[4][4], double (&q)[4][4])
+{
+    unsigned int m = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int mp = 0;
+        unsigned int mn = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned int b = v[k][j];
+            const double d = (double)__uint_as_float(b);
+            s[k][j] += d;
+            q[k][j] = __builtin_fma(d, d, q[k][j]);     // (d * d is exact in fp64 for an fp32 d)
+            mp = max(mp, (int)b);
+            mn = max(mn, b);
+        }
+        const unsigned int mc = max((unsigned int)mp, mn & 0x7fffffffu);
+        m = max(m, scored[j] ? mc : 0u);
+    }
+    return m;
+}
+
+// one sample: sums, then the segment maxima of the wave's 4 planes into LDS (row_shr 1/2/4/8 leave a row's maximum in its
+// last lane; source lanes outside the row read 0)
+__device__ __forceinline__ void ms4_sample(const ms4_u32x4 (&v)[4], const bool (&scored)[4], double (&s)[4][4], double (&q)[4][4],
+                                           unsigned int (&slot)[MS4_NW][4], int w, int lane)
+{
+    unsigned int m = ms4_use(v, scored, s, q);
+    m = max(m, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x111, 0xf, 0xf, true));
+    m = max(m, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x112, 0xf, 0xf, true));
+    m = max(m, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x114, 0xf, 0xf, true));
+    m = max(m, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x118, 0xf, 0xf, true));
+    if ((lane & 15) == 15) slot[w][lane >> 4] = m;
+}
+
+__device__ __forceinline__ void ms4_samples(const float *au, unsigned int cb, long long row_stride, long long plane, int i0, int i1,
+                                            int nt, const bool (&scored)[4], double (&s)[4][4], double (&q)[4][4],
+                                            unsigned int (*stage)[MS4_US][MS4_NW][4], unsigned int *row0, int nseg_left,
+                                            long long seg_stride)
+{
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+    ms4_u32x4 va[4], vb[4];
+    ms4_load(au, cb, row_stride, plane, i0, nt, va);
+    int b = 0;
+    for (int ib = i0; ib < i1; ib += MS4_US, b ^= 1) {
+        const int cnt = min(MS4_US, i1 - ib);
+#pragma unroll
+        for (int u = 0; u < MS4_US; u += 2) {
+            // (the loads past the last sample re-read it; u < cnt is wave-uniform and false only in the last group)
+            ms4_load(au, cb, row_stride, plane, min(ib + u + 1, i1 - 1), nt, vb);
+            if (u < cnt) ms4_sample(va, scored, s, q, stage[b][u], w, lane);
+            ms4_load(au, cb, row_stride, plane, min(ib + u + 2, i1 - 1), nt, va);
+            if (u + 1 < cnt) ms4_sample(vb, scored, s, q, stage[b][u + 1], w, lane);
+        }
+        // stage[b] is complete; it is rewritten two groups on, after the next barrier, which every reader passes only
+        // once its reads of this group are done
+        ms4_barrier();
+        if (threadIdx.x < MS4_US * MS4_NW) {
+            const int smp = (int)(threadIdx.x / MS4_NW), sg = (int)(threadIdx.x % MS4_NW), cg = sg >> 2, r = sg & 3;
+            const unsigned int m = max(max(stage[b][smp][4 * cg][r], stage[b][smp][4 * cg + 1][r]),
+                                       max(stage[b][smp][4 * cg + 2][r], stage[b][smp][4 * cg + 3][r]));
+            if (smp < cnt && sg < nseg_left) row0[(long long)(ib + smp) * seg_stride + sg] = m;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(MS4_NT) moments_segmax4_kernel(const float *__restrict__ a, long long row_stride, int n, int T,
+                                                               int X, int Y, int cx, int cy, int rows_per_split,
+                                                               double *__restrict__ sum, double *__restrict__ sumsq,
+                                                               unsigned int *__restrict__ segmax)
+{
+    // (X * Y % 4 == 0: a lane's 4 cells are all in the plane or all past it; lanes past it re-read the last 4 cells and
+    // count nowhere, but stay for the barriers)
+    const long long plane = (long long)X * Y;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);   // (w: scalar)
+    const long long cl = (long long)blockIdx.x * MS4_NT + (w >> 2) * 256 + lane * 4;
+    const bool live = cl < plane;
+    const long long c = live ? cl : plane - 4;
+    bool scored[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int x = (int)((c + j) / Y), y = (int)(c + j - (long long)x * Y);
+        scored[j] = live && x >= cx && x < X - cx && y >= cy && y < Y - cy;
+    }
+    const long long nseg = (plane + 63) / 64;
+    const int i0 = blockIdx.y * rows_per_split, i1 = min(n, i0 + rows_per_split);
+    const int tc = blockIdx.z, TC = gridDim.z, t0 = tc * MS_TMAX + 4 * (w & 3), nt = min(4, T - t0);     // (nt <= 0: no planes)
+    const float *au = a + (long long)min(t0, T - 1) * plane;                                   // wave-uniform
+    const long long seg_stride = (long long)TC * nseg;                                         // segmax [n][TC][nseg]
+    unsigned int *row0 = segmax + (long long)tc * nseg + (long long)blockIdx.x * MS4_NW;
+    const int nseg_left = (int)min((long long)MS4_NW, nseg - (long long)blockIdx.x * MS4_NW);
+    double s[4][4], q[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[k][j] = q[k][j] = 0.0;
+    __shared__ unsigned int stage[2][MS4_US][MS4_NW][4];
+    const unsigned int cb = (unsigned int)c * 4u;                                               // (X * Y <= 2^30: checked by the host)
+    ms4_samples(au, cb, row_stride, plane, i0, i1, nt, scored, s, q, stage, row0, nseg_left, seg_stride);
+    if (!live) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < nt) {
+            double *ps = sum + (long long)(t0 + k) * plane + c, *pq = sumsq + (long long)(t0 + k) * plane + c;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (gridDim.y == 1) { ps[j] += s[k][j]; pq[j] += q[k][j]; }
+                else { atomicAdd(&ps[j], s[k][j]); atomicAdd(&pq[j], q[k][j]); }
+            }
+        }
+}
+
 __global__ void __launch_bounds__(256) std_from_moments_kernel(const double *__restrict__ sum, const double *__restrict__ sumsq,
                                                                double n_total, long long M, float eps, float *__restrict__ mod)
 {
@@ -962,6 +1114,21 @@ int pre_moments_segmax_f64(const float *a, int64_t row_stride, int64_t n, int64_
     if (!a || !sum || !sumsq || !segmax || n <= 0 || T <= 0 || X <= 0 || Y <= 0) return PRE_E_NULL;
     if (crop_x < 0 || crop_y < 0 || row_stride < T * X * Y) return PRE_E_RANGE;
     const int us = T == 1 ? 16 : T <= 4 ? 4 : 1;
+    if (us == 1 && (X * Y) % 4 == 0 && row_stride % 4 == 0 && !((uintptr_t)a & 15)) {
+        // the float4 form (moments_segmax4_kernel): 1024 cells of a 16-plane chunk per block, one block per CU at a time
+        const long long bx = (X * Y + MS4_NT - 1) / MS4_NT, TC = (T + MS_TMAX - 1) / MS_TMAX;
+        if (n > 0x7fffffff || bx > 0x7fffffffLL || TC > 65535 || T > 0x7fffffff) return PRE_E_SHAPE;
+        if (X * Y >= (1LL << 30)) return PRE_E_SHAPE;                    // (a lane's cell is a 32-bit BYTE offset from the plane's base)
+        long long splits = 1;
+        while (bx * TC * splits < MS4_WANT && splits * 32 < n) splits *= 2;
+        const int rows = (int)((n + splits - 1) / splits);
+        splits = (n + rows - 1) / rows;
+        hipLaunchKernelGGL(moments_segmax4_kernel, dim3((unsigned)bx, (unsigned)splits, (unsigned)TC), dim3(MS4_NT), 0,
+                           as_stream(stream), a, (long long)row_stride, (int)n, (int)T, (int)X, (int)Y, crop_x, crop_y, rows, sum,
+                           sumsq, segmax);
+        PRE_LAUNCH_CHECK();
+        return PRE_OK;
+    }
     const int bt = (us == 16 && MS_STAGE) ? 1024 : 256;                                // (single-plane data: 16 segments per block, see MsStage)
     const long long bx = (X * Y + bt - 1) / bt, TC = (T + MS_TMAX - 1) / MS_TMAX;
     if (n > 0x7fffffff || bx > 0x7fffffffLL || TC > 65535 || T > 0x7fffffff) return PRE_E_SHAPE;
