@@ -155,13 +155,48 @@ PAIR_SIGNATURES = {
                             [c_int, c_void_p],
 }
 
+# libcp_pre_bounds.so (include/cp_pre_bounds.h): solution bounds by sample acceptance (envelope, cellwise, row counts)
+BOUNDS_SO_PATH = os.path.join(_HERE, "libcp_pre_bounds.so")
+PRE_BOUNDS_ABI_VERSION = 1
+PRE_BOUNDS_MAX_LEVELS = 16
+BOUNDS_SIGNATURES = {
+    "pre_bounds_abi_version": [],
+    "pre_bounds_envelope_workspace": [c_int64] * 4 + [c_int, _i64p],
+    "pre_bounds_envelope_f32": _opnd + [c_int64] * 4 + [_fp, c_int64, c_int, _fp, _fp, _fp, _fp, c_int64, c_void_p],
+    "pre_bounds_cellwise_workspace": [c_int64] * 4 + [c_int, _i64p],
+    "pre_bounds_cellwise_f32": _opnd + _opnd + [c_int64] * 4 + [_fp, c_int64, _fp, _fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp,
+                                                                 c_int64, c_void_p],
+    "pre_bounds_rowcount_f32": _opnd + _opnd + [c_int64] * 4 + [_fp, c_int64, _fp, c_int, _fp, c_int64, c_void_p],
+}
+
 _lib = None
+_bounds = None
 _pair = None
 _fft = None
 _dist = None
 _cov = None
 _ode = None
 _setprop = None
+
+
+def load_bounds():
+    """ctypes handle of libcp_pre_bounds.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
+    global _bounds
+    if _bounds is None:
+        if not os.path.exists(BOUNDS_SO_PATH):
+            raise ImportError(f"{BOUNDS_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = ctypes.CDLL(BOUNDS_SO_PATH)
+        lib.pre_bounds_abi_version.argtypes, lib.pre_bounds_abi_version.restype = [], c_int
+        have = lib.pre_bounds_abi_version()
+        if have != PRE_BOUNDS_ABI_VERSION:
+            raise ImportError(f"{BOUNDS_SO_PATH} has ABI version {have}, this binding was written for {PRE_BOUNDS_ABI_VERSION}: "
+                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        for name, argtypes in BOUNDS_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        _bounds = lib
+    return _bounds
 
 
 def load_pair():
