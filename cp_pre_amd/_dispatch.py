@@ -25,12 +25,15 @@ def _dtype_error(dtype):
     return RuntimeError(f"expected scalar type Float but found {_DTYPE_NAMES.get(dtype, str(dtype))}")
 
 
-_kernel_cache = {}   # id(tensor) -> (weakref, version, ndarray); device kernels only
+_kernel_cache = {}   # id(tensor) -> (weakref, ndarray): the taps a stream capture is recorded with; device kernels only
 
 
 def host_kernel(kernel):
-    """fp32 numpy copy of an operator kernel.  Device kernels are cached per tensor object
-    and ``_version`` so the D2H copy (a sync) happens once per distinct kernel value."""
+    """fp32 numpy copy of an operator kernel.  A device kernel (<= 343 floats) is downloaded on EVERY eager call:
+    neither the tensor's identity nor its ``_version`` says that its values are the ones seen last
+    (``D.kernel.data.mul_(2)`` and ``D.kernel.data = other`` move neither), and stale taps are a wrong answer.  Under
+    stream capture no download is possible: the copy of the last eager call on this tensor object is used, so a
+    captured graph replays the taps it was captured with (a kernel never applied eagerly cannot be captured)."""
     if not isinstance(kernel, torch.Tensor):
         raise TypeError("operator kernel must be a torch.Tensor")
     if kernel.dtype != torch.float32:
@@ -38,14 +41,17 @@ def host_kernel(kernel):
     if not kernel.is_cuda:
         return np.ascontiguousarray(kernel.detach().numpy())
     key = id(kernel)
-    hit = _kernel_cache.get(key)
-    if hit is not None and hit[0]() is kernel and hit[1] == kernel._version:
-        return hit[2]
+    if torch.cuda.is_current_stream_capturing():
+        hit = _kernel_cache.get(key)
+        if hit is None or hit[0]() is not kernel:
+            raise RuntimeError("operator kernel on the device under stream capture: apply the operator once eagerly "
+                               "first (the graph then replays the taps it was captured with)")
+        return hit[1]
     arr = kernel.detach().cpu().numpy().copy()
-    if len(_kernel_cache) > 256:
+    if key not in _kernel_cache and len(_kernel_cache) > 256:
         for k in [k for k, v in _kernel_cache.items() if v[0]() is None]:
             del _kernel_cache[k]
-    _kernel_cache[key] = (weakref.ref(kernel), kernel._version, arr)
+    _kernel_cache[key] = (weakref.ref(kernel), arr)
     return arr
 
 

@@ -390,8 +390,10 @@ def empty_like_layout(t, score_rows=False):
     ``score_rows``: the result is a score matrix [n, *cells] (an |residual| output, about to be selected along axis 0):
     its rows are PAD floats further apart than they are long when ``wants_row_pad`` says that pays."""
     order = sorted(range(t.dim()), key=lambda d: (-t.stride(d), d))         # slowest axis first
-    if score_rows and t.dim() >= 2 and order[0] == 0 and wants_row_pad(t.shape[0], t[0].numel()):
-        M = t[0].numel()
+    M = 1
+    for n in t.shape[1:]:                                                    # (from the shape: t[0] does not exist at n == 0)
+        M *= n
+    if score_rows and t.dim() >= 2 and order[0] == 0 and wants_row_pad(t.shape[0], M):
         strides, acc = [0] * t.dim(), 1
         for d in reversed(order[1:]):
             strides[d] = acc

@@ -56,7 +56,12 @@ __device__ __forceinline__ float4 apply(const Star &w, const Nbr &n)
     if (KIND == K_Y3) return w.ym * n.ym + w.c * n.c + w.yp * n.yp;
     if (KIND == K_XY5) return w.xm * n.xm + w.ym * n.ym + w.c * n.c + w.yp * n.yp + w.xp * n.xp;
     if (KIND == K_TX5) return w.tm * n.tm + w.xm * n.xm + w.c * n.c + w.xp * n.xp + w.tp * n.tp;
-    return w.tm * n.tm + w.xm * n.xm + w.ym * n.ym + w.c * n.c + w.yp * n.yp + w.xp * n.xp + w.tp * n.tp;
+    // the general star: a zero weight along the marched axis is not multiplied.  When no operator has such a tap
+    // (Geom::tfree) the neighbouring planes are other samples of a [1,B,T,X] field, or real planes inside a segment and
+    // zeros at its cuts: 0 * inf from there would put NaN outside the operator's extent box (cp_pre_hip.h, non-finite
+    // contract).  The weights are wave-uniform; the order of the sum is unchanged.
+    const float4 tm = w.tm != 0.f ? w.tm * n.tm : f4(0.f), tp = w.tp != 0.f ? w.tp * n.tp : f4(0.f);
+    return tm + w.xm * n.xm + w.ym * n.ym + w.c * n.c + w.yp * n.yp + w.xp * n.xp + tp;
 }
 
 // ------------------------------------------------------------------ residual functors

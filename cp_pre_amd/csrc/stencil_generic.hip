@@ -193,8 +193,9 @@ __device__ __forceinline__ float pt_from_right(float halo, float c)    // lane i
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(halo), __float_as_int(c), 0x130, 0xf, 0xf, false));
 }
 
-// CROSS: rows d1 != 0 hold at most their centre tap (the Taylor Laplacians, any "plus"-shaped set): straight-line code,
-// every weight of the footprint multiplied (zeros included, as the dense F.conv3d does).  Otherwise per-row masks.
+// CROSS: rows d1 != 0 hold at most their centre tap (the Taylor Laplacians, any "plus"-shaped set): no mask lookups off the
+// centre row.  The centre row multiplies the columns of its mask only: a zero weight three columns out would carry a
+// non-finite value beyond the extent box of a radius-1 / radius-2 kernel (the contract of cp_pre_hip.h).  Otherwise per-row masks.
 template <int R, bool CROSS>
 __global__ void __launch_bounds__(256, (R == 1 ? 5 : 4)) plane_taps_kernel(const float *__restrict__ in, long long sB, long long s0,
                                                                            long long s1, float *__restrict__ out, long long oB,
@@ -245,7 +246,7 @@ __global__ void __launch_bounds__(256, (R == 1 ? 5 : 4)) plane_taps_kernel(const
 #pragma unroll
                 for (int d = -R; d <= R; ++d) {
                     const pt_v4 c = C[(i + d + R) % NS];
-                    const int m = CROSS ? (d ? 8 : 0x7f) : taps.mask[d + 3];
+                    const int m = CROSS ? (d ? 8 : taps.mask[3]) : taps.mask[d + 3];
                     if (m == 0) continue;
                     if (m == 8) {                                 // the centre column only
                         const float wd = taps.w[d + 3][3];

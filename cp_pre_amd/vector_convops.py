@@ -75,6 +75,10 @@ class _Pair(ConvOperator):
 
 
 class Divergence(_Pair):
+    def __init__(self, domain=('x', 'y'), order=1, scale=1.0, taylor_order=2, requires_grad=False, require_grad=False):
+        # ``require_grad``: the reference's spelling for this class alone (Utils/VectorConvOps.py:30)
+        super().__init__(domain, order, scale, taylor_order, requires_grad=requires_grad or require_grad)
+
     def __call__(self, input_x, input_y):
         fused = linear2(input_x, self.grad_x.kernel, input_y, self.grad_y.kernel, 1.0)
         return fused if fused is not None else self.grad_x(input_x) + self.grad_y(input_y)

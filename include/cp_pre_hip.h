@@ -48,6 +48,25 @@ extern "C" {
                                   Utils/ConvOps_2d.py:149).  PRE_E_UNSUPPORTED when the views are not Y-contiguous, the
                                   taps are not star-shaped, Y % 4 != 0, or on the 1-D / boundary-condition entries. */
 
+/* What an output depends on, and the non-finite contract (pre_stencil3d_f32, pre_stencil2d_f32, every fused
+ * pre_residual_* entry, the pre_spatial2d_* / pre_edge_residual_f32 family):
+ *   - an output cell depends on the cells of the input views, the zero padding (or the boundary condition's cells, or
+ *     the rows PRE_FLAG_HALO_X declares) and the taps / operator kernels handed to the call - on nothing else.  Memory
+ *     around a view (the neighbouring fields of `vars[:, i]`, pitch gaps, cropped cells, other samples) may hold
+ *     anything, NaN included, without changing a bit of the result, and nothing is written outside the output view.
+ *   - lower bound (a non-finite value is never hidden): an output cell with a NON-ZERO tap on a NaN / +-inf input cell
+ *     is non-finite; a lone NaN arrives as NaN.
+ *   - upper bound (and never leaked): an output cell is finite, and what the finite cells alone give, if no tap of the
+ *     operator's full extent box - |offset| <= k/2 per axis, zero taps included: where the reference's dense F.conv3d
+ *     can produce 0 * inf - lies on a non-finite cell.  The entries that take a tap list take the box of the dense
+ *     kernel the list was made from, (2r+1)^d with r the largest |offset| of any tap on any axis (at least 1): x-taps alone
+ *     may still carry a bad cell at y +- 1.  No box has an extent along the batch.
+ *   - between the two bounds (a ZERO tap of the box on a non-finite cell) the result is unspecified: the dense conv
+ *     gives NaN there, a tap list does not multiply zero taps, and the streaming star kernels multiply the zero taps
+ *     of the axes they march or stage.
+ * For a fused residual the footprint is the union over the operators of its expression, each applied to its field; a
+ * field used pointwise (a product term) counts with the 1x1x1 box. */
+
 /* A strided view of one field [B,T,X,Y] (what `vars[:, i]` or a permuted surrogate
  * output is, Marginal/NS_Residuals_CP.py:282; Other_UQ/Evaluation/PRE_estimations.py:41). */
 typedef struct {

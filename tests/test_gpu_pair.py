@@ -204,15 +204,33 @@ def test_alias_nonfinite_empty_and_repeat(gpu):
         assert torch.count_nonzero(fn(v, v)) == 0                                   # minus aliasing vars: exactly 0
         first = fn(v, v.flip(0))
         assert torch.equal(first, fn(v, v.flip(0)))                                # repeat calls: bitwise equal
-    # NaN / inf in either set reach the cells the two-pass route puts them in
+    # NaN / inf in either set: against the footprint reference (index arithmetic on the operators' dense kernels and the
+    # positions of the bad cells: non-finite wherever a non-zero tap of either set's expression lies on a bad cell, finite
+    # and equal to the float64 oracles' difference wherever no tap of the kernels' extent boxes reaches one) - and, as
+    # before, in the cells the two-pass route puts them in
+    import stencil_guards as sg
+    from test_gpu_footprint import mhd_continuity_terms, ns_momentum_terms
     bad = v.clone()
     bad[0, 0, 3, 4, 10] = float("nan")
     bad[1, 1, 2, 5, 33] = float("inf")
-    for fn, single in ((calls[0], lambda x: ns.residual_momentum(x[:, :3], True)),
-                       (calls[2], lambda x: mhd.residual_continuity(x, True))):
-        for a, m in ((bad, v), (v, bad), (bad, bad)):
+    bad[1, 2, 5, 9, 63] = float("-inf")
+    bad[0, 1, 0, 0, 0] = float("nan")
+    where = ~np.isfinite(bad.cpu().numpy())
+    none = np.zeros_like(where)
+    vc = v.cpu()
+    for fn, single, terms, clean in (
+            (calls[0], lambda x: ns.residual_momentum(x[:, :3], True), lambda w: ns_momentum_terms(ns, w[:, :3]),
+             orr.ns_momentum(vc[:, :3], 0.01, 0.1, 0.1, boundary=True).numpy()),
+            (calls[2], lambda x: mhd.residual_continuity(x, True), lambda w: mhd_continuity_terms(mhd, w),
+             orr.mhd_continuity(vc, boundary=True).numpy())):
+        for a, m, wa, wm in ((bad, v, where, none), (v, bad, none, where), (bad, bad, where, where)):
             d, two = fn(a, m), single(a) - single(m)
             assert torch.equal(torch.isnan(d), torch.isnan(two)) and torch.equal(torch.isinf(d), torch.isinf(two))
+            must, may = sg.footprint_union(terms(wa) + terms(wm))
+            got = d.cpu().numpy()
+            assert (~np.isfinite(got[must])).all() and np.isfinite(got[~may]).all()
+            # off the footprint both sets are the clean field: r(a) - r(b) = 0 within what the paired pass resolves
+            assert np.abs(got[~may]).max() <= RES_TOL * np.abs(clean).max()
     # empty batch
     e = torch.empty(0, 6, 6, 10, 64, device=gpu)
     assert ns.residual_momentum(e[:, :3], minus=e[:, :3]).shape == (0, 4, 8, 62)

@@ -1149,6 +1149,24 @@ def test_empty_batches_through_the_residual_classes(gpu):
     assert R.MHD().residual_induction(v, True).shape == (0, 5, 8, 16)
     assert R.Burgers(0.1, 0.1, 0.01).residual(torch.zeros(0, 6, 16, device=gpu), True).shape == (0, 6, 16)
     assert R.PRE_Wave(0.01, 0.02).residual(v[:, :1], boundary=True).shape == (0, 5, 8, 16)
+    # |residual| (its output is allocated as a score matrix) and r(vars) - r(minus) on an empty device batch, every class
+    ns, mhd, wv, bu = R.NavierStokes(0.01, 0.1, 0.1), R.MHD(), R.PRE_Wave(0.01, 0.02), R.Burgers(0.1, 0.1, 0.01)
+    u1 = torch.zeros(0, 6, 16, device=gpu)
+    jo, j3 = R.JOREK(torch.linspace(1.0, 2.0, 8)), torch.zeros(0, 3, 8, 8, 5, device=gpu)
+    adv, pns, pmhd = R.Advection(1.0, 0.005, 0.01), R.PRE_NS(0.01, 0.1, 0.1), R.PRE_MHD(0.01, 0.1, 0.1)
+    for kw in (dict(absolute=True), dict(minus=None), dict(absolute=True, minus=None)):
+        m = lambda x: {k: (x if k == "minus" else val) for k, val in kw.items()}                     # noqa: E731
+        assert ns.residual_momentum(v[:, :3], True, **m(v[:, :3])).shape == (0, 5, 8, 16)
+        assert ns.residual_continuity(v[:, :2], True, **m(v[:, :2])).shape == (0, 5, 8, 16)
+        for eq in ("continuity", "momentum", "energy", "induction", "gauss"):
+            assert getattr(mhd, "residual_" + eq)(v, True, **m(v)).shape == (0, 5, 8, 16), eq
+        assert wv.residual(v[:, :1], True, **m(v[:, :1])).shape == (0, 5, 8, 16)
+        assert bu.residual(u1, True, **m(u1)).shape == (0, 6, 16)
+        assert adv.residual(u1, True, **m(u1)).shape == (0, 6, 16)
+        assert jo.residual_continuity(j3, True, **m(j3)).shape == (0, 5, 8, 8)
+        assert jo.residual_temperature(j3, True, **m(j3)).shape == (0, 5, 8, 8)
+    assert pns.residual(v[:, :3], True, minus=v[:, :3]).shape == (0, 5, 8, 16)
+    assert pmhd.residual(v, True, minus=v).shape[0] == 0
 
 
 def test_calibration_edge_cases(gpu):

@@ -181,6 +181,18 @@ def test_compat_import_paths_resolve_to_the_product_classes():
             del sys.modules[n]
 
 
+def test_divergence_accepts_the_reference_spelling_require_grad():
+    """``Utils/VectorConvOps.py:30`` spells the argument ``require_grad``; both spellings build the same two operators."""
+    from cp_pre_amd import vector_convops as V
+    a, b, c = V.Divergence(require_grad=True), V.Divergence(requires_grad=True), V.Divergence(("x", "y"), 1, 2.0, 2, require_grad=False)
+    for op in ("grad_x", "grad_y"):
+        assert torch.equal(getattr(a, op).kernel, getattr(b, op).kernel)
+        assert torch.equal(getattr(c, op).kernel, 2.0 * getattr(a, op).kernel)
+        assert vars(getattr(a, op)).keys() == vars(getattr(b, op)).keys()
+    with pytest.raises(TypeError):
+        V.Divergence(require_grads=True)
+
+
 def test_rank_arithmetic_matches_numpy_higher():
     for n in (7, 100, 256, 4096, 8192, 65536):
         for a in oc.ALPHA_LEVELS:

@@ -36,6 +36,10 @@ def test_empty_like_layout_score_rows():
     # few rows / odd row lengths / a batch axis that is not the slowest: dense
     assert _lib.empty_like_layout(torch.empty(200, 8, 64, 64), score_rows=True).is_contiguous()
     assert _lib.empty_like_layout(torch.empty(256, 8, 64, 65), score_rows=True).is_contiguous()
+    # an empty batch: M comes from the shape (there is no t[0]); nothing to pad, the shape is kept
+    for empty in (torch.empty(0, 8, 64, 64), torch.empty(0, 64, 64, 8).permute(0, 3, 1, 2), torch.empty(0, 16), torch.empty(0)):
+        e = _lib.empty_like_layout(empty, score_rows=True)
+        assert e.shape == empty.shape and e.numel() == 0 and e.dtype == torch.float32
     tb = torch.empty(8, 256, 64, 64).permute(1, 0, 2, 3)       # time-major: the batch axis is not the slowest in memory
     assert _lib.empty_like_layout(tb, score_rows=True).stride() == tb.stride()
 
