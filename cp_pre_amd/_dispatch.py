@@ -209,38 +209,62 @@ def needs_grad(*tensors):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
-def _xcorr_impl(field, kernel, nd, flags=0, out=None):
-    """``out``: optional fp32 device tensor of the field's shape to write into (e.g. one slot of a stacked result)."""
-    _check_field(field)
+def _xcorr_run(fields, kernel, nd, flags, out, load, name):
+    """What ``_xcorr_impl`` (one field) and ``xcorr_pair`` (two) are made of: kernel -> taps, the channel squeeze, the shape
+    and ``out`` checks, staging, tap marshalling and the launch of entry ``name`` of library ``load()``.  Returns (return
+    code, out, origin); the code is PRE_OK for an empty field (nothing to launch: ``out`` is the result)."""
+    for f in fields:
+        _check_field(f)
     karr = host_kernel(kernel)
     if karr.ndim != nd:
         raise RuntimeError(f"expected a {nd}-D kernel, got shape {tuple(karr.shape)}")
     w, off = taps_of(karr)
-    if nd == 2 and field.dim() == 4:            # [BS,1,Nt,Nx]: the reference squeezes the channel after conv2d
-        if field.shape[1] != 1:
+    pair = len(fields) == 2
+    if nd == 2 and fields[0].dim() == 4:        # [BS,1,Nt,Nx]: the reference squeezes the channel after conv2d
+        if not pair and fields[0].shape[1] != 1:
             raise RuntimeError("expected a single-channel [BS,1,Nt,Nx] field")
-        field = field[:, 0]
-    if field.dim() != nd + 1:
-        raise RuntimeError(f"expected a {nd + 1}-D field [BS,Nt,Nx{',Ny' if nd == 3 else ''}], got {tuple(field.shape)}")
-    lib = _lib.load()
-    dev, origin = to_device(field)
+        fields = [f[:, 0] for f in fields]
+    a = fields[0]
+    if pair and (a.dim() != nd + 1 or a.shape != fields[1].shape):
+        raise RuntimeError(f"expected two {nd + 1}-D fields of one shape, got {tuple(a.shape)} and {tuple(fields[1].shape)}")
+    if a.dim() != nd + 1:
+        raise RuntimeError(f"expected a {nd + 1}-D field [BS,Nt,Nx{',Ny' if nd == 3 else ''}], got {tuple(a.shape)}")
+    lib = load()
+    dev, origin = to_device(a)
+    views = [dev]
+    if pair:
+        views.append(to_device(fields[1])[0])
+        if not _lib.streamable(*views):
+            views = [d.contiguous() for d in views]
+            dev = views[0]
+        # PRE_FLAG_HALO_X reads the rows beyond the views: only the caller's own Ny-contiguous device views have them (a
+        # staged copy would be read before its first and past its last byte).  Checked for two views, the case staging
+        # copies for want of a shared unit-stride axis; a single view's layout is the library's to accept or decline.
+        if flags & _lib.PRE_FLAG_HALO_X and any(d.data_ptr() != f.data_ptr() or d.stride(-1) != 1 or d.stride() != f.stride()
+                                                for d, f in zip(views, fields)):
+            raise ValueError("halo_x needs both fields as Ny-contiguous device views of larger grids (no staging copy)")
     if out is None:
         out = _lib.empty_like_layout(dev, score_rows=bool(flags & _lib.PRE_FLAG_ABS) and origin is None)
     elif not (out.is_cuda and out.shape == dev.shape and out.dtype == torch.float32):
         raise ValueError("out must be an fp32 device tensor of the field's shape")
     if out.numel() == 0:
-        return from_device(out, origin)
+        return _lib.PRE_OK, out, origin
     wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
     ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
+    views.append(out)
+    if nd == 3:                                 # PreField arguments in 3-D, pointer + stride array in 2-D; the output last
+        args = [ctypes.byref(_lib.field(v)) for v in views]
+    else:
+        args = [x for v in views for x in (_lib.ptr(v), _lib.iarr64(v.stride()))]
     with torch.cuda.device(dev.device):
-        if nd == 3:
-            f, o = _lib.field(dev), _lib.field(out)
-            rc = lib.pre_stencil3d_f32(ctypes.byref(f), ctypes.byref(o), wv, ov, len(w), *dev.shape, flags, _lib.stream())
-            _lib.check(rc, "pre_stencil3d_f32")
-        else:
-            rc = lib.pre_stencil2d_f32(_lib.ptr(dev), _lib.iarr64(dev.stride()), _lib.ptr(out), _lib.iarr64(out.stride()),
-                                       wv, ov, len(w), *dev.shape, flags, _lib.stream())
-            _lib.check(rc, "pre_stencil2d_f32")
+        return getattr(lib, name)(*args, wv, ov, len(w), *dev.shape, flags, _lib.stream()), out, origin
+
+
+def _xcorr_impl(field, kernel, nd, flags=0, out=None):
+    """``out``: optional fp32 device tensor of the field's shape to write into (e.g. one slot of a stacked result)."""
+    name = "pre_stencil3d_f32" if nd == 3 else "pre_stencil2d_f32"
+    rc, out, origin = _xcorr_run((field,), kernel, nd, flags, out, _lib.load, name)
+    _lib.check(rc, name)
     return from_device(out, origin)
 
 
@@ -249,46 +273,11 @@ def xcorr_pair(a, b, kernel, nd, flags=0, out=None):
     ``pre_pair_stencil2d_f32``, include/cp_pre_pair.h); None if the library declines (taps off the 7-point star, no
     unit-stride axis the two fields and the output share): the caller then runs two single-field passes.  Not
     differentiable: the caller composes when a gradient is wanted."""
-    _check_field(a)
-    _check_field(b)
-    karr = host_kernel(kernel)
-    if karr.ndim != nd:
-        raise RuntimeError(f"expected a {nd}-D kernel, got shape {tuple(karr.shape)}")
-    w, off = taps_of(karr)
-    if nd == 2 and a.dim() == 4:                # [BS,1,Nt,Nx]: the reference squeezes the channel after conv2d
-        a, b = a[:, 0], b[:, 0]
-    if a.dim() != nd + 1 or a.shape != b.shape:
-        raise RuntimeError(f"expected two {nd + 1}-D fields of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
-    da, origin = to_device(a)
-    db, _ = to_device(b)
-    if not _lib.streamable(da, db):
-        da, db = da.contiguous(), db.contiguous()
-    # PRE_FLAG_HALO_X reads the rows beyond the views: only the caller's own Ny-contiguous device views have them (a staged
-    # copy would be read before its first and past its last byte)
-    if flags & _lib.PRE_FLAG_HALO_X and (da.data_ptr() != a.data_ptr() or db.data_ptr() != b.data_ptr() or
-                                         da.stride(-1) != 1 or db.stride(-1) != 1 or da.stride() != a.stride() or
-                                         db.stride() != b.stride()):
-        raise ValueError("halo_x needs both fields as Ny-contiguous device views of larger grids (no staging copy)")
-    if out is None:
-        out = _lib.empty_like_layout(da, score_rows=bool(flags & _lib.PRE_FLAG_ABS) and origin is None)
-    elif not (out.is_cuda and out.shape == da.shape and out.dtype == torch.float32):
-        raise ValueError("out must be an fp32 device tensor of the field's shape")
-    if out.numel() == 0:
-        return from_device(out, origin)
-    wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
-    ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
-    lib = _lib.load_pair()
-    with torch.cuda.device(da.device):
-        if nd == 3:
-            fa, fb, o = _lib.field(da), _lib.field(db), _lib.field(out)
-            rc = lib.pre_pair_stencil3d_f32(ctypes.byref(fa), ctypes.byref(fb), ctypes.byref(o), wv, ov, len(w), *da.shape, flags,
-                                            _lib.stream())
-        else:
-            rc = lib.pre_pair_stencil2d_f32(_lib.ptr(da), _lib.iarr64(da.stride()), _lib.ptr(db), _lib.iarr64(db.stride()),
-                                            _lib.ptr(out), _lib.iarr64(out.stride()), wv, ov, len(w), *da.shape, flags, _lib.stream())
+    name = "pre_pair_stencil3d_f32" if nd == 3 else "pre_pair_stencil2d_f32"
+    rc, out, origin = _xcorr_run((a, b), kernel, nd, flags, out, _lib.load_pair, name)
     if rc == _lib.PRE_E_UNSUPPORTED:
         return None
-    _lib.check(rc, "pre_pair_stencil%dd_f32" % nd)
+    _lib.check(rc, name)
     return from_device(out, origin)
 
 

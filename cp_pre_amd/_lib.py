@@ -169,174 +169,83 @@ BOUNDS_SIGNATURES = {
     "pre_bounds_rowcount_f32": _opnd + _opnd + [c_int64] * 4 + [_fp, c_int64, _fp, c_int, _fp, c_int64, c_void_p],
 }
 
-_lib = None
-_bounds = None
-_pair = None
-_fft = None
-_dist = None
-_cov = None
-_ode = None
-_setprop = None
+PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
+
+# One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
+# symbol, module attribute with the version the signatures were written for, entry points that return int64_t - stated
+# by name: pre_fft_work_bytes, for one, returns int).  Paths, signatures and versions are read from the module at call
+# time, so a tool or a test may point a library elsewhere and reset its cache attribute.
+_LIBS = {
+    "hip": ("_lib", "", "pre_abi_version", "PRE_ABI_VERSION", ("pre_joint_score_pruned_max_segments",)),
+    "fft": ("_fft", "FFT_", "pre_fft_abi_version", "PRE_FFT_ABI_VERSION", ()),
+    "dist": ("_dist", "DIST_", "pre_dist_abi_version", "PRE_DIST_ABI_VERSION", ()),
+    "cov": ("_cov", "COV_", "pre_cov_abi_version", "PRE_COV_ABI_VERSION", ()),
+    "ode": ("_ode", "ODE_", "pre_ode_abi_version", "PRE_ODE_ABI_VERSION", ()),
+    "setprop": ("_setprop", "SETPROP_", "pre_setprop_abi_version", "PRE_SETPROP_ABI_VERSION", ()),
+    "pair": ("_pair", "PAIR_", "pre_pair_abi_version", "PRE_PAIR_ABI_VERSION", ()),
+    "bounds": ("_bounds", "BOUNDS_", "pre_bounds_abi_version", "PRE_BOUNDS_ABI_VERSION", ()),
+}
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = None
+_BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
-def load_bounds():
-    """ctypes handle of libcp_pre_bounds.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
-    global _bounds
-    if _bounds is None:
-        if not os.path.exists(BOUNDS_SO_PATH):
-            raise ImportError(f"{BOUNDS_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = ctypes.CDLL(BOUNDS_SO_PATH)
-        lib.pre_bounds_abi_version.argtypes, lib.pre_bounds_abi_version.restype = [], c_int
-        have = lib.pre_bounds_abi_version()
-        if have != PRE_BOUNDS_ABI_VERSION:
-            raise ImportError(f"{BOUNDS_SO_PATH} has ABI version {have}, this binding was written for {PRE_BOUNDS_ABI_VERSION}: "
-                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for name, argtypes in BOUNDS_SIGNATURES.items():
-            fn = getattr(lib, name)
+def _load(key):
+    """ctypes handle of one library (loaded once, after torch, so that it binds to the HIP / hipFFT runtime torch already
+    loaded); raises ImportError loudly if the file is absent or of another ABI version."""
+    g = globals()
+    cache, prefix, version_fn, version, int64_returns = _LIBS[key]
+    if g[cache] is None:
+        path, want = g[prefix + "SO_PATH"], g[version]
+        if not os.path.exists(path):
+            raise ImportError(f"{path} is missing: build it with {_BUILD_HINT}" +
+                              (" (hipcc --offload-arch=gfx950).  cp_pre_amd has no CPU fallback." if key == "hip" else ""))
+        lib = ctypes.CDLL(path)
+        # first: a stale .so with the same symbol names but other signatures would pass misaligned arguments into a
+        # kernel launch
+        fn = getattr(lib, version_fn)
+        fn.argtypes, fn.restype = [], c_int
+        have = fn()
+        if have != want:
+            raise ImportError(f"{path} has ABI version {have}, this binding was written for {want}: rebuild it ({_BUILD_HINT})")
+        for name, argtypes in g[prefix + "SIGNATURES"].items():
+            fn = getattr(lib, name)        # AttributeError here = header / library out of sync
             fn.argtypes = argtypes
-            fn.restype = c_int
-        _bounds = lib
-    return _bounds
-
-
-def load_pair():
-    """ctypes handle of libcp_pre_pair.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
-    global _pair
-    if _pair is None:
-        if not os.path.exists(PAIR_SO_PATH):
-            raise ImportError(f"{PAIR_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = ctypes.CDLL(PAIR_SO_PATH)
-        lib.pre_pair_abi_version.argtypes, lib.pre_pair_abi_version.restype = [], c_int
-        have = lib.pre_pair_abi_version()
-        if have != PRE_PAIR_ABI_VERSION:
-            raise ImportError(f"{PAIR_SO_PATH} has ABI version {have}, this binding was written for {PRE_PAIR_ABI_VERSION}: "
-                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for name, argtypes in PAIR_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-        _pair = lib
-    return _pair
-
-
-def load_setprop():
-    """ctypes handle of libcp_pre_setprop.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
-    global _setprop
-    if _setprop is None:
-        if not os.path.exists(SETPROP_SO_PATH):
-            raise ImportError(f"{SETPROP_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = ctypes.CDLL(SETPROP_SO_PATH)
-        lib.pre_setprop_abi_version.argtypes, lib.pre_setprop_abi_version.restype = [], c_int
-        have = lib.pre_setprop_abi_version()
-        if have != PRE_SETPROP_ABI_VERSION:
-            raise ImportError(f"{SETPROP_SO_PATH} has ABI version {have}, this binding was written for {PRE_SETPROP_ABI_VERSION}: "
-                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for name, argtypes in SETPROP_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-        _setprop = lib
-    return _setprop
-
-
-def load_ode():
-    """ctypes handle of libcp_pre_ode.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
-    global _ode
-    if _ode is None:
-        if not os.path.exists(ODE_SO_PATH):
-            raise ImportError(f"{ODE_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = ctypes.CDLL(ODE_SO_PATH)
-        lib.pre_ode_abi_version.argtypes, lib.pre_ode_abi_version.restype = [], c_int
-        have = lib.pre_ode_abi_version()
-        if have != PRE_ODE_ABI_VERSION:
-            raise ImportError(f"{ODE_SO_PATH} has ABI version {have}, this binding was written for {PRE_ODE_ABI_VERSION}: "
-                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for name, argtypes in ODE_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-        _ode = lib
-    return _ode
-
-
-def load_cov():
-    """ctypes handle of libcp_pre_cov.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
-    global _cov
-    if _cov is None:
-        if not os.path.exists(COV_SO_PATH):
-            raise ImportError(f"{COV_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = ctypes.CDLL(COV_SO_PATH)
-        lib.pre_cov_abi_version.argtypes, lib.pre_cov_abi_version.restype = [], c_int
-        have = lib.pre_cov_abi_version()
-        if have != PRE_COV_ABI_VERSION:
-            raise ImportError(f"{COV_SO_PATH} has ABI version {have}, this binding was written for {PRE_COV_ABI_VERSION}: "
-                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for name, argtypes in COV_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-        _cov = lib
-    return _cov
-
-
-def load_dist():
-    """ctypes handle of libcp_pre_dist.so (loaded once, after torch); raises loudly if absent or of another ABI version."""
-    global _dist
-    if _dist is None:
-        if not os.path.exists(DIST_SO_PATH):
-            raise ImportError(f"{DIST_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = ctypes.CDLL(DIST_SO_PATH)
-        lib.pre_dist_abi_version.argtypes, lib.pre_dist_abi_version.restype = [], c_int
-        have = lib.pre_dist_abi_version()
-        if have != PRE_DIST_ABI_VERSION:
-            raise ImportError(f"{DIST_SO_PATH} has ABI version {have}, this binding was written for {PRE_DIST_ABI_VERSION}: "
-                              "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for name, argtypes in DIST_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-        _dist = lib
-    return _dist
-
-
-def load_fft():
-    """ctypes handle of libcp_pre_fft.so (loaded once, after torch so that it binds to the hipFFT / HIP runtime
-    torch already loaded); raises loudly if absent."""
-    global _fft
-    if _fft is None:
-        if not os.path.exists(FFT_SO_PATH):
-            raise ImportError(f"{FFT_SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = ctypes.CDLL(FFT_SO_PATH)
-        for name, argtypes in FFT_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_int
-        _fft = lib
-    return _fft
+            fn.restype = c_int64 if name in int64_returns else c_int
+        g[cache] = lib
+    return g[cache]
 
 
 def load():
-    """Load (once) and return the ctypes handle; raise loudly if the extension is absent."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO_PATH):
-            raise ImportError(
-                f"{SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(hipcc --offload-arch=gfx950).  cp_pre_amd has no CPU fallback.")
-        lib = ctypes.CDLL(SO_PATH)
-        # first: a stale .so with the same symbol names but other signatures would pass misaligned arguments into a
-        # kernel launch
-        lib.pre_abi_version.argtypes, lib.pre_abi_version.restype = [], c_int
-        have = lib.pre_abi_version()
-        if have != PRE_ABI_VERSION:
-            raise ImportError(f"{SO_PATH} has ABI version {have}, this binding was written for {PRE_ABI_VERSION}: rebuild it "
-                              "(`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(lib, name)        # AttributeError here = header / library out of sync
-            fn.argtypes = argtypes
-            fn.restype = c_int64 if name.endswith(("_bytes", "_max_segments")) else c_int
-        _lib = lib
-    return _lib
+    """Load (once) and return the handle of libcp_pre_hip.so; raise loudly if the extension is absent."""
+    return _lib or _load("hip")
+
+
+def load_fft():
+    return _fft or _load("fft")
+
+
+def load_dist():
+    return _dist or _load("dist")
+
+
+def load_cov():
+    return _cov or _load("cov")
+
+
+def load_ode():
+    return _ode or _load("ode")
+
+
+def load_setprop():
+    return _setprop or _load("setprop")
+
+
+def load_pair():
+    return _pair or _load("pair")
+
+
+def load_bounds():
+    return _bounds or _load("bounds")
 
 
 def require_gpu():

@@ -65,13 +65,57 @@ def _on_device(fields, fn):
     return _dispatch.from_device(fn(*devs), origin)
 
 
-def _fused_call(name, call):
-    """Run a fused entry point; None means 'compose instead'."""
-    rc = call()
+def _arr(views):
+    """``pre_field_t[n]`` of n device views."""
+    return (_lib.PreField * len(views))(*map(_lib.field, views))
+
+
+def _fused(name, call, sets, absolute, out=None, skip_t_rim=False, halo_x=False, out_rule=None, decline=None):
+    """The one way into a fused entry: stage, validate, launch, come home.  ``sets``: one field set, or two (r(a) - r(b)),
+    staged TOGETHER so that both are made contiguous when they share no unit-stride axis.  ``call(dsets, out, flags)``
+    launches ``name`` on the staged sets and returns its code.  ``out_rule`` says what a caller's ``out`` may be: None (the
+    entry takes none), 'ns' (the field shape or, with ``skip_t_rim``, its interior planes) or 'mhd' (the field shape).
+    Returns the result where the fields live, or None where the entry declines (the caller then composes, or runs two
+    passes).  ``decline``: what a decline means when ``halo_x`` / an interior ('ns') or given ('mhd') ``out`` was asked
+    for, which no other route serves: a text to raise RuntimeError with (the single-set calls), or None to fall through
+    all the same (the paired calls: their two-pass route raises on its own, from its single-set passes)."""
+    fields = sets[0] if len(sets) == 1 else [*sets[0], *sets[1]]
+    # (asked here, where the caller's grad mode still holds, and only for the requests whose rules name autograd)
+    grad = (halo_x or out is not None) and _dispatch.needs_grad(*fields)
+    with torch.no_grad():
+        devs, origin = _stage(fields)
+        d0, given = devs[0], out is not None
+        if out is None:
+            out = _lib.empty_like_layout(d0, score_rows=absolute and origin is None)
+        interior = False
+        if out_rule == 'ns':
+            interior = (skip_t_rim and out.dim() == 4 and d0.shape[1] >= 3 and
+                        tuple(out.shape) == (d0.shape[0], d0.shape[1] - 2, d0.shape[2], d0.shape[3]))
+            if not (out.is_cuda and out.dtype == torch.float32 and (out.shape == d0.shape or interior)):
+                raise ValueError("out must be an fp32 device tensor of the field shape "
+                                 "(or, with skip_t_rim, of its interior planes [BS,Nt-2,Nx,Ny])")
+            # (the planes of an interior out must be dense, its batch and time strides are free: a t-slab driver that
+            # shards the marginal calibration hands in a TIME-MAJOR buffer [Nt-2][BS][Nx][Ny] seen as [BS,Nt-2,Nx,Ny],
+            # whose planes then are the contiguous send blocks of its all-to-all - pipeline.marginal_qhat)
+            dense_planes = out.dim() == 4 and out.stride(3) == 1 and out.stride(2) == out.shape[3]
+            if interior and not (dense_planes and origin is None and not grad):
+                raise ValueError("an interior-plane out needs device-resident fields, dense [Nx,Ny] planes and no autograd")
+        elif given and not (out.is_cuda and out.dtype == torch.float32 and out.shape == d0.shape and origin is None and not grad):
+            raise ValueError("out must be an fp32 device tensor of the field shape, the fields device-resident, no autograd")
+        if halo_x and (origin is not None or grad or
+                       any(d.data_ptr() != f.data_ptr() or d.stride(3) != 1 for d, f in zip(devs, fields))):
+            raise ValueError("halo_x needs device-resident, Ny-contiguous views of a larger grid and no autograd")
+        flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_INTERIOR_T if skip_t_rim else 0) | \
+                (_lib.PRE_FLAG_OUT_INTERIOR_T if interior else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
+        k = len(sets[0])
+        with torch.cuda.device(d0.device):
+            rc = call([devs] if len(sets) == 1 else [devs[:k], devs[k:]], out, flags)
     if rc == _lib.PRE_E_UNSUPPORTED:
-        return False
+        if decline is not None and (halo_x or (given if out_rule == 'mhd' else interior)):
+            raise RuntimeError(decline)
+        return None
     _lib.check(rc, name)
-    return True
+    return _dispatch.from_device(out, origin)
 
 
 class _Residual2D:
@@ -98,19 +142,47 @@ class _Residual2D:
         return self.fused and not _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in
                                                          (self.D_t, self.D_x, self.D_y, self.D_xx_yy)])
 
+    def _linear2(self, i, j, ratio, composed, method, vars, minus, boundary, absolute):
+        """``D_x(vars[:, i]) + ratio * D_y(vars[:, j])`` (``composed``): NS continuity, MHD gauss.  One set through
+        ``vector_convops.linear2`` (which keeps the result differentiable itself, operator kernels included), two in one
+        pass of ``pre_pair_linear2_f32``."""
+        sets = ((vars[:, i], vars[:, j]),)
+        if minus is None:
+            if self._want_fused(vars):
+                from .vector_convops import linear2
+                res = linear2(sets[0][0], self.D_x.kernel, sets[0][1], self.D_y.kernel, ratio, _lib.PRE_FLAG_ABS if absolute else 0)
+                if res is not None:
+                    return _finish(res, boundary, _CROP3, absolute, True)
+            return _tail(None, sets, composed, boundary, _CROP3, absolute)
+        _check_minus(vars, minus)
+        sets += ((minus[:, i], minus[:, j]),)
+        ks = self._k27(self.D_x, self.D_y) if self._want_fused(vars, minus) else None
+        res = None if ks is None else _fused("pre_pair_linear2_f32", lambda d, o, flags: _lib.load_pair().pre_pair_linear2_f32(
+            _arr(d[0]), _arr(d[1]), ctypes.byref(_lib.field(o)), *ks, float(ratio), *o.shape, flags, _lib.stream()), sets, absolute)
+        return _tail(res, sets, composed, boundary, _CROP3, absolute, (method, vars, minus))
 
-def _attach(res, fields, composed, absolute):
-    """``res``: a fused result (with |.| already applied if ``absolute``), or None.  If a field requires grad the
-    result is hooked into autograd: a backward recomputes ``composed`` (operator by operator) and differentiates
-    that; a forward that is never differentiated pays nothing."""
+
+def _attach(res, sets, composed, absolute):
+    """``res``: a fused result of one field set, or r(a) - r(b) of two (with |.| already applied if ``absolute``), or None.
+    If a field requires grad the result is hooked into autograd: a backward recomputes ``composed`` (operator by
+    operator; ``composed(*a) - composed(*b)`` for two sets, so gradients reach both) and differentiates that; a forward
+    that is never differentiated pays nothing."""
+    fields = sets[0] if len(sets) == 1 else [*sets[0], *sets[1]]
     if res is None or not _dispatch.needs_grad(*fields):
         return res
-    fn = (lambda *f: _on_device(f, composed).abs()) if absolute else (lambda *f: _on_device(f, composed))
+    k = len(sets[0])
+
+    def fn(*f):
+        d = _on_device(f[:k], composed)
+        if len(f) > k:
+            d = d - _on_device(f[k:], composed)
+        return d.abs() if absolute else d
     return _dispatch._Recompute.apply(res, fn, *fields)
 
 
 def _check_minus(vars, minus, device_view=False):
-    """Validate ``minus=`` before any device work: a tensor of ``vars``' shape and dtype on ``vars``' device.
+    """Validate ``minus=``: a tensor of ``vars``' shape and dtype on ``vars``' device.  Every ``minus=`` route calls this
+    BEFORE any device work, so that a bad second set is reported as such on a machine without a GPU too.
     ``device_view`` (halo_x, an interior-plane out): both sets must be Ny-contiguous device views, like the x-slab views
     the flag reads past - views that staging never copies, so the halo rows read are those of the caller's grid."""
     if not isinstance(minus, torch.Tensor):
@@ -126,45 +198,17 @@ def _check_minus(vars, minus, device_view=False):
                          "of the same geometry")
 
 
-def _pair_attach(res, fa, fb, composed, absolute):
-    """``_attach`` for a fused r(a) - r(b): a backward recomputes ``composed(*a) - composed(*b)`` and differentiates it,
-    so gradients reach both sets."""
-    if res is None or not _dispatch.needs_grad(*fa, *fb):
-        return res
-    k = len(fa)
-
-    def fn(*f):
-        d = _on_device(f[:k], composed) - _on_device(f[k:], composed)
-        return d.abs() if absolute else d
-    return _dispatch._Recompute.apply(res, fn, *fa, *fb)
-
-
-def _pair_stage(fa, fb):
-    """Device views of both sets, made contiguous together when they share no unit-stride axis."""
-    devs, origin = _stage(list(fa) + list(fb))
-    return devs[:len(fa)], devs[len(fa):], origin
-
-
-def _pair_fused(name, fa, fb, absolute, call):
-    """One paired pass: ``call(da, db, out)`` launches a ``pre_pair_*`` entry; None means 'two-pass instead'."""
-    with torch.no_grad():
-        da, db, origin = _pair_stage(fa, fb)
-        out = _lib.empty_like_layout(da[0], score_rows=absolute and origin is None)
-        with torch.cuda.device(out.device):
-            ok = _fused_call(name, lambda: call(da, db, out))
-    return _dispatch.from_device(out, origin) if ok else None
-
-
 def _two_pass(run, fa, fb, absolute):
-    """The two-pass route: ``run(fields)`` (a single-set fused pass on device tensors, or None) for each set, then an
-    in-place subtract / |.| on the first result.  None if the single-set pass declines too."""
+    """The two-pass route of r(a) - r(b): ``run(fields, first)`` is a single-set fused pass on device tensors (or None),
+    ``first`` telling the pass whose result is kept (it may write a caller's ``out``) from the one into a scratch buffer;
+    then an in-place subtract / |.| on the first result.  None if the single-set pass declines too."""
     with torch.no_grad():
         da, db = [_dispatch.to_device(f) for f in fa], [_dispatch.to_device(f) for f in fb]
         origin = next((o for _, o in da + db if o is not None), None)
-        a = run([d for d, _ in da])
+        a = run([d for d, _ in da], True)
         if a is None:
             return None
-        b = run([d for d, _ in db])
+        b = run([d for d, _ in db], False)
         if b is None:
             return None
         a.sub_(b)
@@ -189,6 +233,17 @@ def _finish(res, boundary, crop, absolute, already_abs):
     return res if boundary else res[crop]
 
 
+def _tail(res, sets, composed, boundary, crop, absolute, pair=None):
+    """How every ``residual_*`` ends.  ``res``: what a fused route gave (|.| applied), or None: then the composed route
+    runs, for two sets as ``_pair_composed(*pair, ...)`` with ``pair = (method, vars, minus)``.  A fused result is hooked
+    into autograd (``_attach``); either is cropped unless ``boundary``."""
+    if res is not None:
+        return _finish(_attach(res, sets, composed, absolute), boundary, crop, absolute, True)
+    if pair is not None:
+        return _pair_composed(*pair, boundary, crop, absolute)
+    return _finish(_on_device(sets[0], composed), boundary, crop, absolute, False)
+
+
 # ======================================================================= Navier-Stokes
 class NavierStokes(_Residual2D):
     """``Marginal/NS_Residuals_CP.py:203-240``: continuity and momentum residuals of (u, v, p)."""
@@ -199,30 +254,9 @@ class NavierStokes(_Residual2D):
 
     def residual_continuity(self, vars, boundary=False, absolute=False, minus=None):
         """``minus``: r(vars) - r(minus) in one pass (``pre_pair_linear2_f32``; see the module docstring)."""
-        u, v = vars[:, 0], vars[:, 1]
         ratio = self.dx / self.dy
-        if minus is not None:
-            _check_minus(vars, minus)
-            fa, fb = (u, v), (minus[:, 0], minus[:, 1])
-            res = None
-            ks = self._k27(self.D_x, self.D_y) if self._want_fused(vars, minus) else None
-            if ks is not None:
-                flags = _lib.PRE_FLAG_ABS if absolute else 0
-                res = _pair_fused("pre_pair_linear2_f32", fa, fb, absolute, lambda da, db, out: _lib.load_pair().pre_pair_linear2_f32(
-                    (_lib.PreField * 2)(*map(_lib.field, da)), (_lib.PreField * 2)(*map(_lib.field, db)),
-                    ctypes.byref(_lib.field(out)), *ks, float(ratio), *out.shape, flags, _lib.stream()))
-            if res is None:
-                return _pair_composed(self.residual_continuity, vars, minus, boundary, _CROP3, absolute)
-            res = _pair_attach(res, fa, fb, lambda u, v: self.D_x(u) + ratio * self.D_y(v), absolute)
-            return _finish(res, boundary, _CROP3, absolute, True)
-        res = None
-        if self._want_fused(vars):
-            from .vector_convops import linear2
-            res = linear2(u, self.D_x.kernel, v, self.D_y.kernel, ratio, _lib.PRE_FLAG_ABS if absolute else 0)
-        done_abs = res is not None and absolute
-        if res is None:
-            res = _on_device((u, v), lambda u, v: self.D_x(u) + ratio * self.D_y(v))
-        return _finish(res, boundary, _CROP3, absolute, done_abs)
+        return self._linear2(0, 1, ratio, lambda u, v: self.D_x(u) + ratio * self.D_y(v), self.residual_continuity,
+                             vars, minus, boundary, absolute)
 
     def residual_momentum(self, vars, boundary=False, absolute=False, out=None, skip_t_rim=False, halo_x=False, minus=None):
         """``out``: optional preallocated device tensor [BS,Nt,Nx,Ny] for the uncropped residual
@@ -240,7 +274,7 @@ class NavierStokes(_Residual2D):
         Nt_slab.  Fused route only (raises otherwise).
         ``minus``: r(vars) - r(minus) (the data-driven score) in one pass of both sets (``pre_pair_ns_momentum_f32``);
         ``out``, ``skip_t_rim`` and ``halo_x`` apply to both sets with the same validation."""
-        u, v, p = vars[:, 0], vars[:, 1], vars[:, 2]
+        sets = ((vars[:, 0], vars[:, 1], vars[:, 2]),)
         dt, dx, dy, nu = self.dt, self.dx, self.dy, self.nu
         D_t, D_x, D_y, D_xx_yy = self.D_t, self.D_x, self.D_y, self.D_xx_yy
 
@@ -248,98 +282,39 @@ class NavierStokes(_Residual2D):
             res_x = D_t(u)*dx*dy + u*D_x(u)*dt*dy + v*D_y(u)*dt*dx - nu*D_xx_yy(u)*dt + D_x(p)*dt*dy
             res_y = D_t(v)*dx*dy + u*D_x(v)*dt*dx + v*D_y(v)*dt*dy - nu*D_xx_yy(v)*dt + D_y(p)*dt*dx
             return res_x + res_y
-        if minus is not None:
-            return self._momentum_minus(vars, minus, boundary, absolute, out, skip_t_rim, halo_x, composed)
-        ks = self._k27(self.D_t, self.D_x, self.D_y, self.D_xx_yy) if self._want_fused(vars) else None
-        if ks is not None:
-            with torch.no_grad():
-                (du, dv, dp), origin = _stage((u, v, p))
-                if out is None:
-                    out = _lib.empty_like_layout(du, score_rows=absolute and origin is None)
-                interior = (skip_t_rim and out.dim() == 4 and du.shape[1] >= 3 and
-                            tuple(out.shape) == (du.shape[0], du.shape[1] - 2, du.shape[2], du.shape[3]))
-                if not (out.is_cuda and out.dtype == torch.float32 and (out.shape == du.shape or interior)):
-                    raise ValueError("out must be an fp32 device tensor of the field shape "
-                                     "(or, with skip_t_rim, of its interior planes [BS,Nt-2,Nx,Ny])")
-                # (the planes of an interior out must be dense, its batch and time strides are free: a t-slab driver that
-                # shards the marginal calibration hands in a TIME-MAJOR buffer [Nt-2][BS][Nx][Ny] seen as [BS,Nt-2,Nx,Ny],
-                # whose planes then are the contiguous send blocks of its all-to-all - pipeline.marginal_qhat)
-                dense_planes = out.dim() == 4 and out.stride(3) == 1 and out.stride(2) == out.shape[3]
-                if interior and not (dense_planes and origin is None and not _dispatch.needs_grad(u, v, p)):
-                    raise ValueError("an interior-plane out needs device-resident fields, dense [Nx,Ny] planes and no autograd")
-                flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_INTERIOR_T if skip_t_rim else 0) | \
-                        (_lib.PRE_FLAG_OUT_INTERIOR_T if interior else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
-                if halo_x and (origin is not None or _dispatch.needs_grad(u, v, p) or
-                               any(d.data_ptr() != f.data_ptr() or d.stride(3) != 1 for d, f in zip((du, dv, dp), (u, v, p)))):
-                    raise ValueError("halo_x needs device-resident, Ny-contiguous views of a larger grid and no autograd")
-                fu, fv, fp, fo = _lib.field(du), _lib.field(dv), _lib.field(dp), _lib.field(out)
-                with torch.cuda.device(du.device):
-                    ok = _fused_call("pre_residual_ns_momentum_f32", lambda: _lib.load().pre_residual_ns_momentum_f32(
-                        ctypes.byref(fu), ctypes.byref(fv), ctypes.byref(fp), ctypes.byref(fo), *ks,
-                        float(dt), float(dx), float(dy), float(nu), *du.shape, flags, _lib.stream()))
-                if (interior or halo_x) and not ok:
-                    raise RuntimeError("pre_residual_ns_momentum_f32: an interior-plane out / halo_x needs Ny-contiguous "
-                                       "views and star-shaped operator kernels")
-                if interior:
-                    return out if boundary else out[..., 1:-1, 1:-1]
-            if ok:
-                res = _attach(_dispatch.from_device(out, origin), (u, v, p), composed, absolute)
-                return _finish(res, boundary, _CROP3, absolute, True)
-        if halo_x:
-            raise RuntimeError("halo_x: only the fused route reads the halo rows")
-        return _finish(_on_device((u, v, p), composed), boundary, _CROP3, absolute, False)
-
-    def _momentum_minus(self, vars, minus, boundary, absolute, out, skip_t_rim, halo_x, composed):
-        out_given = out
         interior_out = skip_t_rim and out is not None and out.dim() == 4 and vars.dim() == 5 and out.shape[1] == vars.shape[2] - 2
-        _check_minus(vars, minus, device_view=halo_x or interior_out)
-        fa, fb = (vars[:, 0], vars[:, 1], vars[:, 2]), (minus[:, 0], minus[:, 1], minus[:, 2])
-        ks = self._k27(self.D_t, self.D_x, self.D_y, self.D_xx_yy) if self._want_fused(vars, minus) else None
-        ok = False
+        pair = None
+        if minus is not None:
+            _check_minus(vars, minus, device_view=halo_x or interior_out)
+            sets += ((minus[:, 0], minus[:, 1], minus[:, 2]),)
+            pair = (self.residual_momentum, vars, minus)
+        ks = self._k27(D_t, D_x, D_y, D_xx_yy) if self._want_fused(vars, minus) else None
+        res = None
         if ks is not None:
-            with torch.no_grad():
-                da, db, origin = _pair_stage(fa, fb)
-                du = da[0]
-                if out is None:
-                    out = _lib.empty_like_layout(du, score_rows=absolute and origin is None)
-                interior = (skip_t_rim and out.dim() == 4 and du.shape[1] >= 3 and
-                            tuple(out.shape) == (du.shape[0], du.shape[1] - 2, du.shape[2], du.shape[3]))
-                if not (out.is_cuda and out.dtype == torch.float32 and (out.shape == du.shape or interior)):
-                    raise ValueError("out must be an fp32 device tensor of the field shape "
-                                     "(or, with skip_t_rim, of its interior planes [BS,Nt-2,Nx,Ny])")
-                dense_planes = out.dim() == 4 and out.stride(3) == 1 and out.stride(2) == out.shape[3]
-                if interior and not (dense_planes and origin is None and not _dispatch.needs_grad(*fa, *fb)):
-                    raise ValueError("an interior-plane out needs device-resident fields, dense [Nx,Ny] planes and no autograd")
-                if halo_x and (origin is not None or _dispatch.needs_grad(*fa, *fb) or
-                               any(d.data_ptr() != f.data_ptr() or d.stride(3) != 1 for d, f in zip(da + db, fa + fb))):
-                    raise ValueError("halo_x needs device-resident, Ny-contiguous views of a larger grid and no autograd")
-                flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_INTERIOR_T if skip_t_rim else 0) | \
-                        (_lib.PRE_FLAG_OUT_INTERIOR_T if interior else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
-                a3, b3, fo = (_lib.PreField * 3)(*map(_lib.field, da)), (_lib.PreField * 3)(*map(_lib.field, db)), _lib.field(out)
-                with torch.cuda.device(du.device):
-                    ok = _fused_call("pre_pair_ns_momentum_f32", lambda: _lib.load_pair().pre_pair_ns_momentum_f32(
-                        a3, b3, ctypes.byref(fo), *ks, float(self.dt), float(self.dx), float(self.dy), float(self.nu),
-                        *du.shape, flags, _lib.stream()))
-                if interior and ok:
-                    return out if boundary else out[..., 1:-1, 1:-1]
-            if ok:
-                res = _pair_attach(_dispatch.from_device(out, origin), fa, fb, composed, absolute)
-                return _finish(res, boundary, _CROP3, absolute, True)
-            if not _dispatch.needs_grad(*fa, *fb):
+            tail = (*ks, float(dt), float(dx), float(dy), float(nu))
+            if minus is None:
+                res = _fused("pre_residual_ns_momentum_f32", lambda d, o, flags: _lib.load().pre_residual_ns_momentum_f32(
+                    *[ctypes.byref(_lib.field(t)) for t in d[0] + [o]], *tail, *d[0][0].shape, flags, _lib.stream()),
+                    sets, absolute, out, skip_t_rim, halo_x, 'ns',
+                    "pre_residual_ns_momentum_f32: an interior-plane out / halo_x needs Ny-contiguous views and star-shaped "
+                    "operator kernels")
+            else:
+                res = _fused("pre_pair_ns_momentum_f32", lambda d, o, flags: _lib.load_pair().pre_pair_ns_momentum_f32(
+                    _arr(d[0]), _arr(d[1]), ctypes.byref(_lib.field(o)), *tail, *d[0][0].shape, flags, _lib.stream()),
+                    sets, absolute, out, skip_t_rim, halo_x, 'ns')
+            if res is None and minus is not None and not _dispatch.needs_grad(*sets[0], *sets[1]):
                 # TWO-PASS (the general-star tap structure, whose paired kernel does not fit the registers): the single-set
-                # fused pass of each set, then an in-place subtract / |.|
-                with torch.no_grad():
-                    (dv, origin), (dm, _) = _dispatch.to_device(vars), _dispatch.to_device(minus)
-                    a = self.residual_momentum(dv, True, out=out_given, skip_t_rim=skip_t_rim, halo_x=halo_x)
-                    scratch = torch.empty_like(out_given) if interior_out and out_given is not None else None
-                    a.sub_(self.residual_momentum(dm, True, out=scratch, skip_t_rim=skip_t_rim, halo_x=halo_x))
-                    if absolute:
-                        a.abs_()
-                a = _dispatch.from_device(a, origin)
-                return a if boundary else (a[..., 1:-1, 1:-1] if a.shape[1] == vars.shape[2] - 2 else a[_CROP3])
-        if halo_x:
+                # fused pass of each set.  Only without autograd - its in-place subtract has no backward; fields that
+                # require grad take the composed difference below.  With an interior-plane out r(minus) goes into a
+                # scratch buffer of that shape and the caller's out is the result.
+                res = _two_pass(lambda f, first: self.residual_momentum(
+                    f[0], True, out=out if first else (torch.empty_like(out) if interior_out else None),
+                    skip_t_rim=skip_t_rim, halo_x=halo_x), (vars,), (minus,), absolute)
+        if res is None and halo_x:
             raise RuntimeError("halo_x: only the fused route reads the halo rows")
-        return _pair_composed(self.residual_momentum, vars, minus, boundary, _CROP3, absolute)
+        # (an interior-plane out has lost its first and last time plane already: x and y are left to crop)
+        crop = _CROP2 if res is not None and res.shape[1] == vars.shape[2] - 2 else _CROP3
+        return _tail(res, sets, composed, boundary, crop, absolute, pair)
 
     _WALLS = {'top': 0, 'bottom': 1, 'left': 2, 'right': 3}
 
@@ -386,170 +361,89 @@ class MHD(_Residual2D):
         super().__init__(**kw)
         self.gamma = gamma
 
-    def _fused(self, eq, vars, absolute, halo_x=False, out=None):
-        """``halo_x`` (every ``residual_*`` below takes it): ``vars`` is an x-slab ``full[:, :, :, x0:x1]`` whose rows
+    def _fused(self, eq, vars, absolute, halo_x=False, out=None, minus=None):
+        """One pass of ``pre_residual_mhd_f32`` over the six fields or, with ``minus`` (the continuity equation only), of
+        ``pre_pair_mhd_continuity_f32`` over the first three of both sets; None -> compose / two-pass.
+        ``halo_x`` (every ``residual_*`` below takes it): ``vars`` is an x-slab ``full[:, :, :, x0:x1]`` whose rows
         x0 - 1 and x1 lie in the same memory and are read as x-neighbours instead of the zero padding
         (``PRE_FLAG_HALO_X``, see ``NavierStokes.residual_momentum``); fused route only.
         ``out`` (likewise): a preallocated fp32 device tensor [BS,Nt,Nx,Ny] for the uncropped residual - any batch / plane
         strides over rows that share the fields' contiguous axis (``pipeline.row_padded`` / ``time_major`` buffers: the
         sharded marginal calibration's send blocks); fused route only (raises otherwise)."""
-        ks = self._k27(self.D_t, self.D_x, self.D_y) if self._want_fused(vars) else None
-        if ks is None or vars.shape[1] < 6:
-            if halo_x or out is not None:
+        n = 6 if minus is None else 3
+        ks = self._k27(self.D_t, self.D_x, self.D_y) if self._want_fused(vars, minus) else None
+        if ks is None or vars.shape[1] < n:
+            if minus is None and (halo_x or out is not None):
                 raise RuntimeError("halo_x / out: only the fused route reads the halo rows / writes a caller's buffer")
             return None
-        with torch.no_grad():
-            fields, origin = _stage([vars[:, i] for i in range(6)])
-        if halo_x and (origin is not None or _dispatch.needs_grad(vars) or
-                       any(d.data_ptr() != vars[:, i].data_ptr() or d.stride(3) != 1 for i, d in enumerate(fields))):
-            raise ValueError("halo_x needs device-resident, Ny-contiguous views of a larger grid and no autograd")
-        given = out is not None
-        if given and not (out.is_cuda and out.dtype == torch.float32 and out.shape == fields[0].shape and origin is None
-                          and not _dispatch.needs_grad(vars)):
-            raise ValueError("out must be an fp32 device tensor of the field shape, the fields device-resident, no autograd")
-        if not given:
-            out = _lib.empty_like_layout(fields[0], score_rows=absolute and origin is None)
-        arr = (_lib.PreField * 6)(*[_lib.field(f) for f in fields])
-        fo = _lib.field(out)
-        flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
-        with torch.cuda.device(out.device):
-            ok = _fused_call("pre_residual_mhd_f32", lambda: _lib.load().pre_residual_mhd_f32(
-                _MHD_EQ[eq], arr, ctypes.byref(fo), *ks, float(self.gamma), *out.shape, flags, _lib.stream()))
-        if (halo_x or given) and not ok:
-            raise RuntimeError("pre_residual_mhd_f32: halo_x / out need views that share a contiguous axis with the fields "
-                               "and star-shaped operator kernels")
-        return _dispatch.from_device(out, origin) if ok else None
+        tail = (*ks, float(self.gamma))
+        if minus is None:
+            return _fused("pre_residual_mhd_f32", lambda d, o, flags: _lib.load().pre_residual_mhd_f32(
+                _MHD_EQ[eq], _arr(d[0]), ctypes.byref(_lib.field(o)), *tail, *o.shape, flags, _lib.stream()),
+                ([vars[:, i] for i in range(n)],), absolute, out, False, halo_x, 'mhd',
+                "pre_residual_mhd_f32: halo_x / out need views that share a contiguous axis with the fields "
+                "and star-shaped operator kernels")
+        return _fused("pre_pair_mhd_continuity_f32", lambda d, o, flags: _lib.load_pair().pre_pair_mhd_continuity_f32(
+            _arr(d[0]), _arr(d[1]), ctypes.byref(_lib.field(o)), *tail, *o.shape, flags, _lib.stream()),
+            ([vars[:, i] for i in range(n)], [minus[:, i] for i in range(n)]), absolute, out, False, halo_x, 'mhd')
 
-    def _pair_continuity(self, vars, minus, absolute, halo_x, out):
-        """r(vars) - r(minus) of the continuity equation in one pass (``pre_pair_mhd_continuity_f32``); None -> two-pass."""
-        ks = self._k27(self.D_t, self.D_x, self.D_y) if self._want_fused(vars, minus) else None
-        if ks is None or vars.shape[1] < 3:
-            return None
-        fa, fb = [vars[:, i] for i in range(3)], [minus[:, i] for i in range(3)]
-        with torch.no_grad():
-            da, db, origin = _pair_stage(fa, fb)
-        if halo_x and (origin is not None or _dispatch.needs_grad(vars, minus) or
-                       any(d.data_ptr() != f.data_ptr() or d.stride(3) != 1 for d, f in zip(da + db, fa + fb))):
-            raise ValueError("halo_x needs device-resident, Ny-contiguous views of a larger grid and no autograd")
-        given = out is not None
-        if given and not (out.is_cuda and out.dtype == torch.float32 and out.shape == da[0].shape and origin is None
-                          and not _dispatch.needs_grad(vars, minus)):
-            raise ValueError("out must be an fp32 device tensor of the field shape, the fields device-resident, no autograd")
-        if not given:
-            out = _lib.empty_like_layout(da[0], score_rows=absolute and origin is None)
-        a3, b3, fo = (_lib.PreField * 3)(*map(_lib.field, da)), (_lib.PreField * 3)(*map(_lib.field, db)), _lib.field(out)
-        flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
-        with torch.cuda.device(out.device):
-            ok = _fused_call("pre_pair_mhd_continuity_f32", lambda: _lib.load_pair().pre_pair_mhd_continuity_f32(
-                a3, b3, ctypes.byref(fo), *ks, float(self.gamma), *out.shape, flags, _lib.stream()))
-        return _dispatch.from_device(out, origin) if ok else None
-
-    def _minus(self, eq, vars, minus, boundary, absolute, halo_x, out, fields_of, composed):
-        """``residual_<eq>(..., minus=)``: one pass (continuity), else TWO-PASS - the single-set fused pass of ``vars``
-        into the result (``out`` if given), that of ``minus`` into one scratch buffer, an in-place subtract (or |.|) -
-        else the composed difference."""
+    def _residual(self, eq, idx, composed, vars, boundary, absolute, halo_x, out, minus):
+        """``residual_<eq>`` of the fields ``vars[:, idx]``.  With ``minus=``: one pass (continuity), else TWO-PASS - the
+        single-set fused pass of ``vars`` into the result (``out`` if given), that of ``minus`` into one scratch buffer, an
+        in-place subtract (or |.|) - else the composed difference."""
+        sets = (tuple(vars[:, i] for i in idx),)
+        if minus is None:
+            return _tail(self._fused(eq, vars, absolute, halo_x, out), sets, composed, boundary, _CROP3, absolute)
         _check_minus(vars, minus, device_view=halo_x)
-        res = self._pair_continuity(vars, minus, absolute, halo_x, out) if eq == 'continuity' else None
+        res = self._fused(eq, vars, absolute, halo_x, out, minus) if eq == 'continuity' else None
         if res is None:
-            first = [out]
-
-            def run(f):
-                o, first[0] = first[0], None
-                return self._fused(eq, f[0], False, halo_x, o)
-            res = _two_pass(run, (vars,), (minus,), absolute)
-        if res is None:
-            return _pair_composed(getattr(self, 'residual_' + eq), vars, minus, boundary, _CROP3, absolute)
-        res = _pair_attach(res, fields_of(vars), fields_of(minus), composed, absolute)
-        return _finish(res, boundary, _CROP3, absolute, True)
+            res = _two_pass(lambda f, first: self._fused(eq, f[0], False, halo_x, out if first else None), (vars,), (minus,),
+                            absolute)
+        sets += (tuple(minus[:, i] for i in idx),)
+        return _tail(res, sets, composed, boundary, _CROP3, absolute, (getattr(self, 'residual_' + eq), vars, minus))
 
     def residual_continuity(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
         """``minus``: r(vars) - r(minus) in one pass (``pre_pair_mhd_continuity_f32``)."""
         D_t, D_x, D_y = self.D_t, self.D_x, self.D_y
-        fields = (vars[:, 0], vars[:, 1], vars[:, 2])
 
         def composed(rho, u, v):
             return D_t(rho) + u*D_x(rho) + rho*D_x(u) + v*D_y(rho) + rho*D_y(v)
-        if minus is not None:
-            return self._minus('continuity', vars, minus, boundary, absolute, halo_x, out,
-                               lambda x: (x[:, 0], x[:, 1], x[:, 2]), composed)
-        res = _attach(self._fused('continuity', vars, absolute, halo_x, out), fields, composed, absolute)
-        if res is None:
-            return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
-        return _finish(res, boundary, _CROP3, absolute, True)
+        return self._residual('continuity', (0, 1, 2), composed, vars, boundary, absolute, halo_x, out, minus)
 
     def residual_momentum(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
-        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_minus``)."""
+        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_residual``)."""
         D_t, D_x, D_y = self.D_t, self.D_x, self.D_y
-        fields = tuple(vars[:, i] for i in range(6))
 
         def composed(rho, u, v, p, Bx, By):
             res_x = D_t(u) + u*D_x(u) + (1/rho)*D_x(p) - 2*(Bx/rho)*D_x(Bx) + v*D_y(u) - (By/rho)*D_y(Bx) - (Bx/rho)*D_y(By)
             res_y = D_t(v) + u*D_x(v) + (1/rho)*D_y(p) - 2*(By/rho)*D_y(By) + v*D_y(v) - (By/rho)*D_x(Bx) - (Bx/rho)*D_x(By)
             return res_x + res_y
-        if minus is not None:
-            return self._minus('momentum', vars, minus, boundary, absolute, halo_x, out, lambda x: tuple(x[:, i] for i in range(6)), composed)
-        res = _attach(self._fused('momentum', vars, absolute, halo_x, out), fields, composed, absolute)
-        if res is None:
-            return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
-        return _finish(res, boundary, _CROP3, absolute, True)
+        return self._residual('momentum', range(6), composed, vars, boundary, absolute, halo_x, out, minus)
 
     def residual_energy(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
-        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_minus``)."""
+        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_residual``)."""
         D_t, D_x, D_y, gamma = self.D_t, self.D_x, self.D_y, self.gamma
-        fields = tuple(vars[:, i] for i in range(6))
 
         def composed(rho, u, v, p, Bx, By):
             p_gas = p - 0.5*(Bx**2 + By**2)
             return (D_t(rho) + u*D_x(p) + v*D_y(p) + (gamma-2)*(u*Bx+v*By)*(D_x(Bx) + D_y(By))
                     + (gamma*p_gas+By**2)*D_x(u) + (gamma*p_gas+Bx**2)*D_y(v) - Bx*By*(D_y(u) + D_x(v)))
-        if minus is not None:
-            return self._minus('energy', vars, minus, boundary, absolute, halo_x, out, lambda x: tuple(x[:, i] for i in range(6)), composed)
-        res = _attach(self._fused('energy', vars, absolute, halo_x, out), fields, composed, absolute)
-        if res is None:
-            return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
-        return _finish(res, boundary, _CROP3, absolute, True)
+        return self._residual('energy', range(6), composed, vars, boundary, absolute, halo_x, out, minus)
 
     def residual_induction(self, vars, boundary=False, absolute=False, halo_x=False, out=None, minus=None):
-        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_minus``)."""
+        """``minus``: r(vars) - r(minus), TWO-PASS (see ``_residual``)."""
         D_t, D_x, D_y = self.D_t, self.D_x, self.D_y
-        fields = (vars[:, 1], vars[:, 2], vars[:, 4], vars[:, 5])
 
         def composed(u, v, Bx, By):
             res_x = D_t(Bx) - By*D_y(u) + Bx*D_y(v) - v*D_y(Bx) + u*D_y(By)
             res_y = D_t(By) + By*D_x(u) - Bx*D_x(v) - v*D_x(Bx) + u*D_x(By)
             return res_x + res_y
-        if minus is not None:
-            return self._minus('induction', vars, minus, boundary, absolute, halo_x, out, lambda x: (x[:, 1], x[:, 2], x[:, 4], x[:, 5]), composed)
-        res = _attach(self._fused('induction', vars, absolute, halo_x, out), fields, composed, absolute)
-        if res is None:
-            return _finish(_on_device(fields, composed), boundary, _CROP3, absolute, False)
-        return _finish(res, boundary, _CROP3, absolute, True)
+        return self._residual('induction', (1, 2, 4, 5), composed, vars, boundary, absolute, halo_x, out, minus)
 
     def residual_gauss(self, vars, boundary=False, absolute=False, minus=None):
         """``minus``: r(vars) - r(minus) in one pass (``pre_pair_linear2_f32``)."""
-        Bx, By = vars[:, 4], vars[:, 5]
-        if minus is not None:
-            _check_minus(vars, minus)
-            fa, fb = (Bx, By), (minus[:, 4], minus[:, 5])
-            res = None
-            ks = self._k27(self.D_x, self.D_y) if self._want_fused(vars, minus) else None
-            if ks is not None:
-                flags = _lib.PRE_FLAG_ABS if absolute else 0
-                res = _pair_fused("pre_pair_linear2_f32", fa, fb, absolute, lambda da, db, out: _lib.load_pair().pre_pair_linear2_f32(
-                    (_lib.PreField * 2)(*map(_lib.field, da)), (_lib.PreField * 2)(*map(_lib.field, db)),
-                    ctypes.byref(_lib.field(out)), *ks, 1.0, *out.shape, flags, _lib.stream()))
-            if res is None:
-                return _pair_composed(self.residual_gauss, vars, minus, boundary, _CROP3, absolute)
-            res = _pair_attach(res, fa, fb, lambda Bx, By: self.D_x(Bx) + self.D_y(By), absolute)
-            return _finish(res, boundary, _CROP3, absolute, True)
-        res = None
-        if self._want_fused(vars):
-            from .vector_convops import linear2
-            res = linear2(Bx, self.D_x.kernel, By, self.D_y.kernel, 1.0, _lib.PRE_FLAG_ABS if absolute else 0)
-        done_abs = res is not None and absolute
-        if res is None:
-            res = _on_device((Bx, By), lambda Bx, By: self.D_x(Bx) + self.D_y(By))
-        return _finish(res, boundary, _CROP3, absolute, done_abs)
+        return self._linear2(4, 5, 1.0, lambda Bx, By: self.D_x(Bx) + self.D_y(By), self.residual_gauss,
+                             vars, minus, boundary, absolute)
 
 
 # ======================================================================= reduced MHD (JOREK)
@@ -591,49 +485,44 @@ class JOREK:
         return torch.as_tensor(x, dtype=torch.float32).to(like.device)
 
     def _fused(self, eq, fields, coef, absolute):
-        """One streaming pass (``pre_residual_jorek_f32``); None -> compose."""
+        """One streaming pass (``pre_residual_jorek_f32``); None -> compose.  No ``out`` / ``halo_x`` here."""
         if not self.fused or any(f.numel() == 0 for f in fields) or \
                 _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self._ops()]):
             return None
         ks = [_dispatch.dense27(o.kernel) for o in self._ops()]
         if any(k is None for k in ks):
             return None
-        with torch.no_grad():
-            devs, origin = _stage(fields)
-        f0 = devs[0]
-        if self.R.numel() != f0.shape[3]:
-            raise RuntimeError(f"R has {self.R.numel()} points, the fields' last axis {f0.shape[3]} (the reference "
-                               "broadcasts its 1-D R along the last axis)")
-        # R as one more field view that repeats the row: unit stride on the axis the fields are contiguous on
-        Rd = self.R.to(f0.device)
-        if f0.stride(3) == 1:
-            Rb = Rd.view(1, 1, 1, -1).expand(f0.shape)
-        elif f0.stride(1) == 1:                                           # Nt fastest (the surrogate's memory order)
-            Rb = Rd.view(-1, 1).expand(-1, f0.shape[1]).contiguous().as_strided(tuple(f0.shape), (0, 1, 0, f0.shape[1]))
-        else:
-            return None
-        out = _lib.empty_like_layout(f0, score_rows=absolute and origin is None)
-        arr = (_lib.PreField * 3)(*[_lib.field(devs[i] if i < len(devs) else devs[0]) for i in range(3)])
-        fo, fr = _lib.field(out), _lib.field(Rb)
-        with torch.cuda.device(out.device):
-            ok = _fused_call("pre_residual_jorek_f32", lambda: _lib.load().pre_residual_jorek_f32(
-                eq, arr, ctypes.byref(fr), ctypes.byref(fo), *ks, _lib.farr(coef), *out.shape,
-                _lib.PRE_FLAG_ABS if absolute else 0, _lib.stream()))
-        return _dispatch.from_device(out, origin) if ok else None
 
-    def _minus(self, eq, vars, minus, boundary, absolute, composed, coef, method):
-        """r(vars) - r(minus), TWO-PASS: the single-set fused pass of each set, then an in-place subtract (or |.|)."""
+        def call(d, out, flags):
+            devs, f0 = d[0], d[0][0]
+            if self.R.numel() != f0.shape[3]:
+                raise RuntimeError(f"R has {self.R.numel()} points, the fields' last axis {f0.shape[3]} (the reference "
+                                   "broadcasts its 1-D R along the last axis)")
+            # R as one more field view that repeats the row: unit stride on the axis the fields are contiguous on
+            Rd = self.R.to(f0.device)
+            if f0.stride(3) == 1:
+                Rb = Rd.view(1, 1, 1, -1).expand(f0.shape)
+            elif f0.stride(1) == 1:                                       # Nt fastest (the surrogate's memory order)
+                Rb = Rd.view(-1, 1).expand(-1, f0.shape[1]).contiguous().as_strided(tuple(f0.shape), (0, 1, 0, f0.shape[1]))
+            else:
+                return _lib.PRE_E_UNSUPPORTED                             # (no layout of R to go with the fields': compose)
+            return _lib.load().pre_residual_jorek_f32(
+                eq, _arr([devs[i] if i < len(devs) else devs[0] for i in range(3)]), ctypes.byref(_lib.field(Rb)),
+                ctypes.byref(_lib.field(out)), *ks, _lib.farr(coef), *out.shape, flags, _lib.stream())
+        return _fused("pre_residual_jorek_f32", call, (fields,), absolute)
+
+    def _residual(self, eq, fa, composed, coef, method, vars, minus, boundary, absolute):
+        """How both equations end.  ``minus``: r(vars) - r(minus), TWO-PASS: the single-set fused pass of each set, then an
+        in-place subtract (or |.|)."""
+        if minus is None:
+            return _tail(self._fused(eq, fa, coef, absolute), (fa,), composed, boundary, _CROP3, absolute)
         _check_minus(vars, minus)
-        k = 2 if eq == 0 else 3
-        fa, fb = self.unstack_fields(vars)[:k], self.unstack_fields(minus)[:k]
-        res = _two_pass(lambda f: self._fused(eq, tuple(f), coef, False), fa, fb, absolute)
-        if res is None:
-            return _pair_composed(method, vars, minus, boundary, _CROP3, absolute)
-        res = _pair_attach(res, fa, fb, composed, absolute)
-        return _finish(res, boundary, _CROP3, absolute, True)
+        fb = tuple(self.unstack_fields(minus)[:len(fa)])
+        res = _two_pass(lambda f, first: self._fused(eq, tuple(f), coef, False), fa, fb, absolute)
+        return _tail(res, (fa, fb), composed, boundary, _CROP3, absolute, (method, vars, minus))
 
     def residual_continuity(self, vars, boundary=False, norms=False, absolute=False, minus=None):
-        """:207-221.  ``minus``: r(vars) - r(minus), two-pass (``_minus``)."""
+        """:207-221.  ``minus``: r(vars) - r(minus), two-pass (``_residual``)."""
         D_t, D_R, D_Z, D_RR, D_ZZ = self._ops()
         rho, phi, _ = self.unstack_fields(vars)
         if norms and (self.dx is None or self.dy is None or self.dt is None):
@@ -653,16 +542,11 @@ class JOREK:
             coef = [float(2*dx*dy), float(dt), float((2*dt*dy)*2), float((4*dt)*D)]
         else:
             coef = [1.0, 1.0, 2.0, float(torch.tensor(self.D, dtype=torch.float32))]
-        if minus is not None:
-            return self._minus(0, vars, minus, boundary, absolute, composed, coef,
-                               lambda x, b: self.residual_continuity(x, b, norms))
-        res = _attach(self._fused(0, (rho, phi), coef, absolute), (rho, phi), composed, absolute)
-        if res is None:
-            return _finish(_on_device((rho, phi), composed), boundary, _CROP3, absolute, False)
-        return _finish(res, boundary, _CROP3, absolute, True)
+        return self._residual(0, (rho, phi), composed, coef, lambda x, b: self.residual_continuity(x, b, norms),
+                              vars, minus, boundary, absolute)
 
     def residual_temperature(self, vars, boundary=False, norms=False, absolute=False, minus=None):
-        """:224-243.  ``minus``: r(vars) - r(minus), two-pass (``_minus``)."""
+        """:224-243.  ``minus``: r(vars) - r(minus), two-pass (``_residual``)."""
         if norms:
             raise Exception("Norm not implemented yet")              # (as the reference, :230)
         D_t, D_R, D_Z, D_RR, D_ZZ = self._ops()
@@ -676,12 +560,7 @@ class JOREK:
                 K * (D_RR(T) + (1/R)*D_R(T) + D_ZZ(T))
         t = lambda v: torch.tensor(v, dtype=torch.float32)
         coef = [float(2 * t(self.gamma)), 0.0, 0.0, float(t(self.K))]
-        if minus is not None:
-            return self._minus(1, vars, minus, boundary, absolute, composed, coef, self.residual_temperature)
-        res = _attach(self._fused(1, (rho, phi, T), coef, absolute), (rho, phi, T), composed, absolute)
-        if res is None:
-            return _finish(_on_device((rho, phi, T), composed), boundary, _CROP3, absolute, False)
-        return _finish(res, boundary, _CROP3, absolute, True)
+        return self._residual(1, (rho, phi, T), composed, coef, self.residual_temperature, vars, minus, boundary, absolute)
 
 
 class PRE_MHD(MHD):
@@ -731,7 +610,6 @@ class PRE_Wave:
             res = _dispatch.xcorr(uu, self.D.kernel, nd=3, flags=flags)  # (raises if no kernel reads the halo rows)
         return res if boundary else res[_CROP3]
 
-
     def _minus(self, uu, mm, boundary, absolute, halo_x, out, flags):
         if _dispatch.needs_grad(uu, mm, self.D.kernel):
             if halo_x or out is not None:
@@ -741,11 +619,11 @@ class PRE_Wave:
             raise ValueError("halo_x / out need device-resident fields and no autograd")
         (uu, origin), (mm, _) = _dispatch.to_device(uu), _dispatch.to_device(mm)
         res = _dispatch.xcorr_pair(uu, mm, self.D.kernel, 3, flags, out=out)
-        if res is None:                       # two-pass: r(uu) into the result, r(mm) into a scratch buffer, subtract
-            res = _dispatch._xcorr_impl(uu, self.D.kernel, 3, flags & _lib.PRE_FLAG_HALO_X, out=out)
-            res.sub_(_dispatch._xcorr_impl(mm, self.D.kernel, 3, flags & _lib.PRE_FLAG_HALO_X))
-            if absolute:
-                res.abs_()
+        if res is None:
+            # two-pass: r(uu) into the result, r(mm) into a scratch buffer.  PRE_FLAG_ABS is stripped from the two passes:
+            # |.| applies to the difference, after the subtraction
+            res = _two_pass(lambda f, first: _dispatch._xcorr_impl(f[0], self.D.kernel, 3, flags & _lib.PRE_FLAG_HALO_X,
+                                                                  out=out if first else None), (uu,), (mm,), absolute)
         res = _dispatch.from_device(res, origin)
         return res if boundary else res[_CROP3]
 
@@ -792,31 +670,19 @@ class Burgers:
         def composed(uu):
             dxd, dtd, nud = (c.to(uu.device) for c in (dx, dt, nu))
             return dxd * self.D_t(uu) + dtd * uu * self.D_x(uu) - nud * self.D_xx(uu) * (2 * dtd / dxd)
-        fused = self.fused and uu.numel() > 0 and not _dispatch.needs_grad(self.D_t.kernel, self.D_x.kernel, self.D_xx.kernel)
+        # (the fused entries take [BS,Nt,Nx] only: a [BS,1,Nt,Nx] field composes)
+        fused = self.fused and uu.numel() > 0 and uu.dim() == 3 and \
+            not _dispatch.needs_grad(self.D_t.kernel, self.D_x.kernel, self.D_xx.kernel)
         ks = [_dispatch.dense9(o.kernel) for o in (self.D_t, self.D_x, self.D_xx)] if fused else [None]
+        sets, pair, name, load = ((uu,),), None, "pre_residual_burgers_f32", _lib.load
         if minus is not None:
             _check_minus(uu, minus)
-            res = None
-            if all(k is not None for k in ks) and uu.dim() == 3:
-                c3, flags = float(2 * dt / dx), _lib.PRE_FLAG_ABS if absolute else 0
-                res = _pair_fused("pre_pair_burgers_f32", (uu,), (minus,), absolute, lambda da, db, out: _lib.load_pair().pre_pair_burgers_f32(
-                    _lib.ptr(da[0]), _lib.iarr64(da[0].stride()), _lib.ptr(db[0]), _lib.iarr64(db[0].stride()), _lib.ptr(out),
-                    _lib.iarr64(out.stride()), *ks, float(dx), float(dt), float(nu), c3, *out.shape, flags, _lib.stream()))
-            if res is None:
-                return _pair_composed(lambda x, b: self.residual(x, b), uu, minus, boundary, _CROP2, absolute)
-            res = _pair_attach(res, (uu,), (minus,), composed, absolute)
-            return res if boundary else res[_CROP2]
-        if all(k is not None for k in ks) and uu.dim() == 3:
-            with torch.no_grad():
-                (du,), origin = _stage((uu,))
-            out = _lib.empty_like_layout(du, score_rows=absolute and origin is None)
-            c3 = float(2 * dt / dx)                       # evaluated in fp32 like the reference
-            with torch.cuda.device(du.device):
-                ok = _fused_call("pre_residual_burgers_f32", lambda: _lib.load().pre_residual_burgers_f32(
-                    _lib.ptr(du), _lib.iarr64(du.stride()), _lib.ptr(out), _lib.iarr64(out.stride()), *ks,
-                    float(dx), float(dt), float(nu), c3,
-                    *du.shape, _lib.PRE_FLAG_ABS if absolute else 0, _lib.stream()))
-            if ok:
-                res = _attach(_dispatch.from_device(out, origin), (uu,), composed, absolute)
-                return res if boundary else res[_CROP2]
-        return _finish(_on_device((uu,), composed), boundary, _CROP2, absolute, False)
+            sets, pair = ((uu,), (minus,)), (lambda x, b: self.residual(x, b), uu, minus)
+            name, load = "pre_pair_burgers_f32", _lib.load_pair
+        res = None
+        if all(k is not None for k in ks):
+            tail = (*ks, float(dx), float(dt), float(nu), float(2 * dt / dx))      # (2 dt / dx in fp32 like the reference)
+            res = _fused(name, lambda d, o, flags: getattr(load(), name)(
+                *[x for t in [s[0] for s in d] + [o] for x in (_lib.ptr(t), _lib.iarr64(t.stride()))], *tail, *o.shape, flags,
+                _lib.stream()), sets, absolute)
+        return _tail(res, sets, composed, boundary, _CROP2, absolute, pair)

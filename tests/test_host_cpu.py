@@ -157,6 +157,19 @@ def test_missing_extension_fails_loudly(monkeypatch, tmp_path):
         _lib.load_fft()
 
 
+def test_library_of_another_abi_version_fails_loudly(monkeypatch):
+    """A stale shared object (same symbol names, other signatures) must not load: every library of the table is checked
+    against the version its signatures were written for, libcp_pre_fft.so included."""
+    assert "fft" in _lib._LIBS and len(_lib._LIBS) == 8
+    for key, (cache, _, _, version, _) in _lib._LIBS.items():
+        monkeypatch.setattr(_lib, cache, None)
+        monkeypatch.setattr(_lib, version, getattr(_lib, version) + 1)
+        with pytest.raises(ImportError, match="ABI version"):
+            _lib._load(key)
+    with pytest.raises(ImportError, match="libcp_pre_fft.so has ABI version 1"):
+        _lib.load_fft()
+
+
 def test_compat_import_paths_resolve_to_the_product_classes():
     """cp_pre_amd/compat on sys.path gives the reference's own import lines (INTEGRATION.md level 1)."""
     import importlib
