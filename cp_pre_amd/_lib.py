@@ -169,6 +169,25 @@ BOUNDS_SIGNATURES = {
     "pre_bounds_rowcount_f32": _opnd + _opnd + [c_int64] * 4 + [_fp, c_int64, _fp, c_int, _fp, c_int64, c_void_p],
 }
 
+# libcp_pre_vjp.so (include/cp_pre_vjp.h): vector-Jacobian products of the residuals and the deterministic sum of squares
+VJP_SO_PATH = os.path.join(_HERE, "libcp_pre_vjp.so")
+PRE_VJP_ABI_VERSION = 1
+PRE_VJP_CROP, PRE_VJP_VIEW3D, PRE_VJP_SUMSQ_WORKSPACE = 1, 2, 2048
+_scale = [c_float, _fp]                                   # host_scale, dev_scale
+VJP_SIGNATURES = {
+    "pre_vjp_abi_version": [],
+    "pre_vjp_stencil3d_f32": [_fld, _fld, POINTER(c_float), POINTER(c_int32), c_int] + _scale + [c_int64] * 4 + [c_int, c_void_p],
+    "pre_vjp_stencil2d_f32": [_fp, _i64p, _fp, _i64p, POINTER(c_float), POINTER(c_int32), c_int] + _scale + [c_int64] * 3 +
+                             [c_int, c_void_p],
+    "pre_vjp_linear2_f32": [_fld, POINTER(PreField), POINTER(c_float), POINTER(c_float), c_float] + _scale + [c_int64] * 4 +
+                           [c_int, c_void_p],
+    "pre_vjp_burgers_f32": [_fp, _i64p, _fp, _i64p, _fp, _i64p] + [POINTER(c_float)] * 3 + [c_float] * 4 + _scale +
+                           [c_int64] * 3 + [c_int, c_void_p],
+    "pre_vjp_ns_momentum_f32": [_fld, POINTER(PreField), POINTER(PreField)] + [POINTER(c_float)] * 4 + [c_float] * 4 + _scale +
+                               [c_int64] * 4 + [c_int, c_void_p],
+    "pre_vjp_sumsq_f32": [_fld] + [c_int64] * 4 + [c_int, _fp, _fp, c_void_p],
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -185,7 +204,11 @@ _LIBS = {
     "pair": ("_pair", "PAIR_", "pre_pair_abi_version", "PRE_PAIR_ABI_VERSION", ()),
     "bounds": ("_bounds", "BOUNDS_", "pre_bounds_abi_version", "PRE_BOUNDS_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = None
+# The libraries added since: same five-tuple, a table of their own (``_load`` consults both)
+_LIBS_MORE = {
+    "vjp": ("_vjp", "VJP_", "pre_vjp_abi_version", "PRE_VJP_ABI_VERSION", ()),
+}
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -193,7 +216,7 @@ def _load(key):
     """ctypes handle of one library (loaded once, after torch, so that it binds to the HIP / hipFFT runtime torch already
     loaded); raises ImportError loudly if the file is absent or of another ABI version."""
     g = globals()
-    cache, prefix, version_fn, version, int64_returns = _LIBS[key]
+    cache, prefix, version_fn, version, int64_returns = _LIBS[key] if key in _LIBS else _LIBS_MORE[key]
     if g[cache] is None:
         path, want = g[prefix + "SO_PATH"], g[version]
         if not os.path.exists(path):
@@ -246,6 +269,10 @@ def load_pair():
 
 def load_bounds():
     return _bounds or _load("bounds")
+
+
+def load_vjp():
+    return _vjp or _load("vjp")
 
 
 def require_gpu():

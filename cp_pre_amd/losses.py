@@ -1,0 +1,338 @@
+"""Physics-informed residual losses with fused HIP backward passes.
+
+The reference trains its surrogates with the PDE residual in the loss (``Physics_Informed/Wave_FNO_PISL.py:209-217``,
+``Wave_FNO_PI.py:202-228``, ``Advection_FNO_PI.py:207-217``)::
+
+    PI_loss(pred)      = residual(pred).pow(2).mean()
+    PISL(pred, yy)     = (residual(pred) - residual(yy)).pow(2).mean()
+    combined(pred, yy) = lp + 1000 * PISL(pred, yy)
+
+and calls ``loss.backward()`` on the device.  Here::
+
+    ns = NavierStokes(dt, dx, dy)
+    loss = pi_loss(ns.residual_momentum, pred)                 # mean(r^2), 0-d fp32 device tensor
+    loss = pisl_loss(ns.residual_momentum, pred, yy)           # mean((r(pred) - r(yy))^2)
+    (lp + 1000 * loss).backward()                              # pred.grad by the fused VJP
+    gu = residual_vjp(ns.residual_momentum, vars, g)           # a general upstream g, same kernels
+
+Forward: the existing fused residual pass (the paired pass for PISL) writes the uncropped residual r, then
+``pre_vjp_sumsq_f32`` sums ``m * r^2`` deterministically in fp64 (``m``: the cells the loss averages over).  Without a
+gradient r is dropped at once; with one it is the only new tensor kept.  Backward: ONE launch of ``libcp_pre_vjp.so``
+(``include/cp_pre_vjp.h``) reads r - masked and scaled by ``2 / N * upstream`` on load, the upstream gradient staying
+on the device - and the fields the residual is non-linear in, and writes the gradient of every field into its slot of
+one tensor of ``pred``'s shape.
+
+Fused routes: a single linear operator (a ``ConvOperator`` of ``convops_2d`` / ``convops_1d``, ``PRE_Wave``,
+``Advection``), NS continuity, NS momentum (``PRE_NS``), Burgers.  Everything else - MHD, JOREK, operator kernels that
+require grad or have weight off the 7-point star, inputs on the CPU or without unit stride on their last axis,
+``fused=False``, a ``yy`` that requires grad - falls back to what ran before: ``method(...).pow(2).mean()`` through
+autograd.  ``last_route()`` says which route the last call took.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _dispatch, _lib
+from . import residuals as R
+from .convops_1d import ConvOperator as ConvOperator1D
+from .convops_2d import ConvOperator as ConvOperator2D
+
+_last_route = None
+
+
+def last_route():
+    """'fused:<kind>' (kind: stencil3d, stencil2d, linear2, burgers, ns_momentum) or 'fallback:<why>' of the last
+    ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
+    return _last_route
+
+
+# ------------------------------------------------------------------------------------------- what a method is
+class _Spec:
+    """One residual method, resolved: ``kind`` (None: no fused VJP), ``nd`` residual axes, ``chan`` - the channels of a
+    stacked ``[BS,F,...]`` input the residual reads (None: the input is the field itself), ``why`` a fallback is taken."""
+
+    def __init__(self, method):
+        self.method, self.kind, self.why, self.chan, self.nd = method, None, None, None, 3
+        self.is_op = isinstance(method, (ConvOperator1D, ConvOperator2D))
+        obj = method if self.is_op else getattr(method, "__self__", None)
+        name = getattr(method, "__name__", "")
+        self.obj = obj
+        if self.is_op:
+            self.nd = 2 if isinstance(method, ConvOperator1D) else 3
+            if getattr(method, "conv", None) != method.convolution:
+                self.why = "spectral operator"
+            else:
+                self.kind, self.ops = "stencil%dd" % self.nd, (method,)
+        elif obj is None or not callable(method):
+            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
+        elif isinstance(obj, R.NavierStokes) and name in ("residual_momentum", "residual"):
+            self.kind, self.chan, self.ops = "ns_momentum", (0, 1, 2), (obj.D_t, obj.D_x, obj.D_y, obj.D_xx_yy)
+        elif isinstance(obj, R.NavierStokes) and name == "residual_continuity":
+            self.kind, self.chan, self.ops = "linear2", (0, 1), (obj.D_x, obj.D_y)
+        elif isinstance(obj, R.Burgers) and name == "residual":
+            self.kind, self.nd, self.ops = "burgers", 2, (obj.D_t, obj.D_x, obj.D_xx)
+        elif isinstance(obj, R.PRE_Wave) and name == "residual":
+            self.kind, self.ops = "stencil3d", (obj.D,)
+        elif isinstance(obj, R.Advection) and name == "residual":
+            self.kind, self.nd, self.ops = "stencil2d", 2, (obj.D,)
+        elif isinstance(obj, (R.MHD, R.JOREK)):
+            self.why = "no fused VJP for " + type(obj).__name__
+            self.chan = ()                                        # (stacked input; JOREK's own layout: shapes not checked here)
+        else:
+            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
+
+    # -------- shapes (host only)
+    def field_shape(self, x):
+        """Shape of the uncropped residual of input ``x``; raises on a rank the method does not take."""
+        if isinstance(self.obj, R.JOREK):
+            if x.dim() != 5:
+                raise ValueError(f"expected vars [BS,F,Nx,Ny,Nt], got {tuple(x.shape)}")
+            return (x.shape[0], x.shape[4], x.shape[2], x.shape[3])
+        if self.chan is not None:
+            if x.dim() != 5 or x.shape[1] < len(self.chan):
+                raise ValueError(f"expected vars [BS,F>={len(self.chan)},Nt,Nx,Ny], got {tuple(x.shape)}")
+            return (x.shape[0],) + tuple(x.shape[2:])
+        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5:
+            return (x.shape[0],) + tuple(x.shape[2:])
+        if x.dim() != self.nd + 1:
+            raise ValueError(f"expected a {self.nd + 1}-D field, got {tuple(x.shape)}")
+        return tuple(x.shape)
+
+    def out_shape(self, x, boundary):
+        s = self.field_shape(x)
+        return s if boundary else s[:1] + tuple(max(n - 2, 0) for n in s[1:])
+
+    # -------- the method itself
+    def call(self, x, boundary, minus=None):
+        """``method(x)`` (``- method(minus)``), cropped unless ``boundary``: the differentiable route that ran before."""
+        if self.is_op:
+            r = self.method(x) if minus is None else self.method(x) - self.method(minus)
+            return r if boundary else r[(Ellipsis,) + (slice(1, -1),) * self.nd]
+        if minus is None:
+            return self.method(x, boundary=boundary)
+        return self.method(x, boundary=boundary, minus=minus)
+
+    def full(self, x, minus):
+        """The uncropped residual by the existing fused passes (no autograd)."""
+        with torch.no_grad():
+            if not self.is_op:
+                return self.call(x, True, minus)
+            if minus is None:
+                return _dispatch._xcorr_impl(x, self.method.kernel, self.nd)
+            r = _dispatch.xcorr_pair(x, minus, self.method.kernel, self.nd)
+            return r if r is not None else self.method(x) - self.method(minus)
+
+    # -------- can the fused VJP run?  (host checks + one download of the operator kernels)
+    def prepare(self, x, minus=None):
+        """(why, kernels): ``why`` is None if the fused VJP can run on ``x`` - ``kernels`` are then the host copies of the
+        operator kernels the launch takes - else the reason for the fallback.  Changes nothing on ``self``."""
+        why, kernels = self.why, ()
+        if self.kind is None:
+            return why, kernels
+        if not x.is_cuda or (minus is not None and not minus.is_cuda):
+            why = "input on the CPU"
+        elif x.numel() == 0:
+            why = "empty input"
+        elif x.stride(-1) != 1 or (minus is not None and minus.stride(-1) != 1):
+            why = "no unit stride on the last axis"
+        elif getattr(self.obj, "fused", True) is False:
+            why = "fused=False"
+        elif minus is not None and minus.requires_grad and torch.is_grad_enabled():
+            why = "yy requires grad"
+        elif _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
+            why = "operator kernel requires grad"
+        elif isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
+            why = "multi-channel wave input"
+        else:
+            ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
+            if self.kind.startswith("stencil"):
+                if ks[0].ndim != self.nd or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
+                    why = "operator kernel off the 7-point star"
+                else:
+                    w, off = _dispatch.taps_of(ks[0])
+                    if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
+                        why = "operator kernel off the 7-point star"
+                    kernels = (w, off)
+            else:
+                if any(k.shape != (3,) * self.nd or not _is_star(k) for k in ks):
+                    why = "operator kernel off the 7-point star"
+                kernels = tuple(_lib.farr(k.reshape(-1)) for k in ks)
+        return why, kernels
+
+    # -------- the VJP launch: gfull [BS,*field] (unit stride last) -> gradient of x's shape
+    def vjp(self, kernels, gfull, x, crop, host_scale, dev_scale):
+        """``kernels``: what ``prepare`` returned.  None if the library declines."""
+        lib = _lib.load_vjp()
+        grad = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        flags = _lib.PRE_VJP_CROP if crop else 0
+        scale = (float(host_scale), _lib.ptr(dev_scale))
+        if gfull.stride(-1) != 1:
+            gfull = gfull.contiguous()
+        name = "pre_vjp_" + self.kind + "_f32"
+        with torch.cuda.device(x.device):
+            st = _lib.stream()
+            if self.kind == "ns_momentum":
+                obj = self.obj
+                if x.shape[1] > 3:
+                    grad[:, 3:].zero_()
+                rc = lib.pre_vjp_ns_momentum_f32(
+                    ctypes.byref(_lib.field(gfull)), R._arr([x[:, 0], x[:, 1]]), R._arr([grad[:, 0], grad[:, 1], grad[:, 2]]),
+                    *kernels, float(obj.dt), float(obj.dx), float(obj.dy), float(obj.nu), *scale, *gfull.shape, flags, st)
+            elif self.kind == "linear2":
+                if x.shape[1] > 2:
+                    grad[:, 2:].zero_()
+                rc = lib.pre_vjp_linear2_f32(ctypes.byref(_lib.field(gfull)), R._arr([grad[:, 0], grad[:, 1]]), *kernels,
+                                             float(self.obj.dx / self.obj.dy), *scale, *gfull.shape, flags, st)
+            elif self.kind == "burgers":
+                obj = self.obj
+                rc = lib.pre_vjp_burgers_f32(
+                    *[a for t in (gfull, x, grad) for a in (_lib.ptr(t), _lib.iarr64(t.stride()))], *kernels,
+                    float(obj.dx), float(obj.dt), float(obj.nu), float(2 * obj.dt / obj.dx), *scale, *gfull.shape, flags, st)
+            else:
+                w, off = kernels
+                wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
+                ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
+                out = grad[:, 0] if grad.dim() == self.nd + 2 else grad
+                if self.nd == 3:
+                    rc = lib.pre_vjp_stencil3d_f32(ctypes.byref(_lib.field(gfull)), ctypes.byref(_lib.field(out)), wv, ov, len(w),
+                                                   *scale, *gfull.shape, flags, st)
+                else:
+                    rc = lib.pre_vjp_stencil2d_f32(_lib.ptr(gfull), _lib.iarr64(gfull.stride()), _lib.ptr(out),
+                                                   _lib.iarr64(out.stride()), wv, ov, len(w), *scale, *gfull.shape, flags, st)
+        if rc == _lib.PRE_E_UNSUPPORTED:
+            return None
+        _lib.check(rc, name)
+        return grad
+
+
+def _is_star(k):
+    idx = np.argwhere(k != 0) - 1
+    return not len(idx) or not (np.count_nonzero(idx, axis=1) > 1).any()
+
+
+# ------------------------------------------------------------------------------------------- validation (host only)
+def _check_tensor(t, what):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} has dtype {t.dtype}: the residual losses take float32")
+
+
+def _check_like(t, like, what, shape=None):
+    """``t``: a float32 tensor of ``shape`` (default ``like``'s) on ``like``'s device; raises before any device work."""
+    _check_tensor(t, what)
+    shape = tuple(like.shape) if shape is None else tuple(shape)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what} has shape {tuple(t.shape)}, expected {shape}")
+    if t.device != like.device:
+        raise ValueError(f"{what} is on {t.device}, pred on {like.device}")
+
+
+# ------------------------------------------------------------------------------------------- the loss
+def _mean_sq(r, boundary):
+    """(mean of ``m * r^2`` as a 0-d fp32 device tensor, N) by ``pre_vjp_sumsq_f32``; r: the uncropped residual."""
+    dims = r.shape[1:]
+    n = r.shape[0]
+    for d in dims:
+        n *= d if boundary else max(d - 2, 0)
+    if r.stride(-1) != 1:
+        r = r.contiguous()
+    r4 = r if r.dim() == 4 else r.unsqueeze(0)
+    flags = (0 if boundary else _lib.PRE_VJP_CROP) | (_lib.PRE_VJP_VIEW3D if r.dim() == 3 else 0)
+    ws = torch.empty(_lib.PRE_VJP_SUMSQ_WORKSPACE + 1, dtype=torch.float64, device=r.device)
+    with torch.cuda.device(r.device):
+        _lib.check(_lib.load_vjp().pre_vjp_sumsq_f32(ctypes.byref(_lib.field(r4)), *r4.shape, flags, _lib.ptr(ws),
+                                                     ctypes.c_void_p(ws.data_ptr() + 8 * _lib.PRE_VJP_SUMSQ_WORKSPACE),
+                                                     _lib.stream()), "pre_vjp_sumsq_f32")
+    return (ws[-1] / float(n) if n else ws[-1] * float("nan")).to(torch.float32), n
+
+
+def _recompute_grad(spec, x, minus, boundary, g):
+    """The gradient by the route that ran before (what the fused backward does where the library declines)."""
+    with torch.enable_grad():
+        v = x.detach().requires_grad_(True)
+        y = spec.call(v, boundary, minus)
+        return torch.autograd.grad(y, v, g.to(y.device))[0]
+
+
+class _LossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, spec, kernels, yy, boundary):
+        r = spec.full(pred, yy)
+        loss, n = _mean_sq(r, boundary)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(r, pred)              # r: the one new tensor kept; pred is the caller's
+            ctx.spec, ctx.kernels, ctx.yy, ctx.boundary, ctx.n = spec, kernels, yy, boundary, n
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        # (once_differentiable: the VJP launch builds no graph, so create_graph=True raises instead of returning a gradient
+        # that silently has none)
+        r, pred = ctx.saved_tensors
+        spec, n = ctx.spec, ctx.n
+        up = gout.detach().to(device=pred.device, dtype=torch.float32).reshape(1)
+        grad = spec.vjp(ctx.kernels, r, pred, not ctx.boundary, 2.0 / n if n else 0.0, up)
+        if grad is None:                                 # (not expected after prepare(): the library declined)
+            m = r if ctx.boundary else r[(Ellipsis,) + (slice(1, -1),) * spec.nd]
+            grad = _recompute_grad(spec, pred, ctx.yy, ctx.boundary, (2.0 / max(n, 1)) * up * m)
+        return grad, None, None, None, None
+
+
+def _loss(residual_method, pred, yy, boundary):
+    global _last_route
+    spec = _Spec(residual_method)
+    _check_tensor(pred, "pred")
+    spec.field_shape(pred)                               # (called for its raise: a rank the method does not take)
+    if yy is not None:
+        _check_like(yy, pred, "yy")
+    why, kernels = spec.prepare(pred, yy)
+    if why is not None:
+        _last_route = "fallback:" + why
+        return spec.call(pred, boundary, yy).pow(2).mean()
+    _last_route = "fused:" + spec.kind
+    return _LossFn.apply(pred, spec, kernels, None if yy is None else yy.detach(), bool(boundary))
+
+
+def pi_loss(residual_method, pred, boundary=False):
+    """``residual_method(pred, boundary).pow(2).mean()`` (``PI_loss``, Physics_Informed/Wave_FNO_PISL.py:213-214) as a
+    0-d fp32 tensor on ``pred``'s device, differentiable with respect to ``pred``.  ``residual_method``: a bound
+    ``residual*`` method of a class of ``cp_pre_amd.residuals``, or a ``ConvOperator`` (2-D: [BS,Nt,Nx,Ny], 1-D:
+    [BS,Nt,Nx]).  ``boundary`` as on the residual methods (False: the mean runs over the interior ``[1:-1]`` of every
+    residual axis; over an empty interior it is NaN, as ``torch.mean`` of an empty tensor)."""
+    return _loss(residual_method, pred, None, boundary)
+
+
+def pisl_loss(residual_method, pred, yy, boundary=False):
+    """``(residual(pred) - residual(yy)).pow(2).mean()`` (``PISL``, Physics_Informed/Wave_FNO_PISL.py:216-217).  ``yy``
+    (``pred``'s shape, dtype and device) is data: the fused route does not differentiate it (one that requires grad takes
+    the fallback, which does)."""
+    return _loss(residual_method, pred, yy, boundary)
+
+
+def residual_vjp(residual_method, vars, g, boundary=False):
+    """The vector-Jacobian product ``d <g, residual_method(vars, boundary)> / d vars`` for a general upstream gradient
+    ``g`` (the shape of the method's result), by the kernels the losses use.  Returns a tensor of ``vars``' shape."""
+    global _last_route
+    spec = _Spec(residual_method)
+    _check_tensor(vars, "vars")
+    _check_like(g, vars, "g", spec.out_shape(vars, boundary))
+    why, kernels = spec.prepare(vars)
+    if why is not None:
+        _last_route = "fallback:" + why
+        return _recompute_grad(spec, vars, None, boundary, g)
+    if g.numel() == 0:                                   # (an empty interior: nothing reaches vars)
+        _last_route = "fused:" + spec.kind
+        return torch.zeros(vars.shape, dtype=torch.float32, device=vars.device)
+    with torch.no_grad():
+        gfull = g if boundary else torch.nn.functional.pad(g, (1, 1) * spec.nd)
+        grad = spec.vjp(kernels, gfull, vars, False, 1.0, None)
+    if grad is None:
+        _last_route = "fallback:declined by the library"
+        return _recompute_grad(spec, vars, None, boundary, g)
+    _last_route = "fused:" + spec.kind
+    return grad

@@ -1,0 +1,152 @@
+"""Physics-informed residual losses on one GPU: a training step's loss + backward by the fused route (A,
+``losses.pi_loss(method, v)`` + ``backward()``: the fused residual pass, ``pre_vjp_sumsq_f32``, one VJP launch of
+``libcp_pre_vjp.so``) against what ran before for the same gradient (B, ``method(v).pow(2).mean().backward()``: the fused
+forward, then the composed expression re-evaluated and differentiated by torch).  Both run alternately in one process on
+the same tensors; each timing is the median of --reps device-event measurements after --warmup calls.  B's peak memory
+is measured at batch 1 first and the batch of the timed case is chosen from it (never by running out of memory).
+Counting full-tensor streams for NS momentum, A moves 4 (forward) + 1 (sum of squares) + 6 (VJP) = 11.
+Also: the VJP launch alone (``residual_vjp`` with a full-grid g), time and 4 B x streams x cells / time against 8 TB/s.
+The NS momentum case is held against its floor (A at least 3x faster than B: met / MISSED).
+Plain text lines on stdout and in --out.
+
+    python tools/loss_bench.py [--reps 7] [--warmup 2] [--out profiles/loss/loss_bench.txt] [--max-batch 16]
+    rocprofv3 --kernel-trace --stats -- python tools/loss_bench.py --vjp-only      # the VJP kernel under the profiler
+"""
+import argparse
+import datetime
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from cp_pre_amd import losses  # noqa: E402
+from cp_pre_amd import residuals as R  # noqa: E402
+
+HBM = 8.0e12
+
+
+def _ev():
+    return torch.cuda.Event(enable_timing=True)
+
+
+def alternate(fns, reps, warmup):
+    """median ms of each fn, the fns interleaved call by call"""
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for i, f in enumerate(fns):
+            a, b = _ev(), _ev()
+            a.record()
+            f()
+            b.record()
+            b.synchronize()
+            times[i].append(a.elapsed_time(b))
+    return [sorted(t)[len(t) // 2] for t in times]
+
+
+def peak_of(fn):
+    """bytes allocated at the peak of fn() beyond what was allocated before it"""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - before
+
+
+def steps(method, v):
+    def a():
+        v.grad = None
+        losses.pi_loss(method, v).backward()
+
+    def b():
+        v.grad = None
+        method(v).pow(2).mean().backward()
+    return a, b
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--max-batch", type=int, default=16, help="cap of the timed NS batch (B's memory may allow more)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss", "loss_bench.txt"))
+    ap.add_argument("--vjp-only", action="store_true", help="only a few NS momentum VJP launches (for a profiler)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "loss_bench needs the MI355X"
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    rand = lambda *s: torch.rand(*s, device=dev, generator=g).add_(0.5)              # noqa: E731
+    lines = []
+
+    def emit(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    ns = R.NavierStokes(0.01, 1 / 512, 1 / 512)
+    if args.vjp_only:
+        v, gg = rand(8, 3, 64, 512, 512), rand(8, 64, 512, 512)
+        for _ in range(5):
+            losses.residual_vjp(ns.residual_momentum, v, gg, boundary=True)
+        torch.cuda.synchronize()
+        return
+    free, total = torch.cuda.mem_get_info()
+    emit(f"# loss_bench {datetime.date.today().isoformat()} on {torch.cuda.get_device_name(0)}, torch {torch.__version__}, "
+         f"HBM free {free / 2**30:.0f} of {total / 2**30:.0f} GiB; reps {args.reps}, warmup {args.warmup}")
+    emit("# timings: device events around host + device work of one call, median; A and B interleaved on the same tensors. "
+         "Every case's tensors are far larger than the 256 MiB of last-level cache, so each pass streams from HBM (cold) "
+         "whether or not the call before it touched the same bytes")
+
+    cases = [
+        ("ns_momentum", lambda bs: rand(bs, 3, 64, 512, 512), ns.residual_momentum, args.max_batch, 11),
+        ("burgers", lambda bs: rand(bs, 200, 512), R.Burgers(1 / 512, 0.0025, 0.002).residual, 4096, 7),
+        ("wave", lambda bs: rand(bs, 64, 512, 512), R.PRE_Wave(0.01, 1 / 512).residual, args.max_batch, 5),
+    ]
+    for name, mk, method, cap, streams_a in cases:
+        # B's peak per sample at a small batch; the timed batch: what fits half the free memory, capped
+        small = 2 if name != "burgers" else 64
+        v = mk(small).requires_grad_(True)
+        a, b = steps(method, v)
+        b()
+        per = peak_of(b) / small
+        del v, a, b
+        bs = int(max(1, min(cap, 0.5 * free / (per + 2 * mk(1).numel() * 4))))
+        v = mk(bs).requires_grad_(True)
+        a, b = steps(method, v)
+        a()
+        route = losses.last_route()
+        ga = v.grad.clone()
+        b()
+        err = float((ga - v.grad).abs().max() / v.grad.abs().max())
+        del ga
+        pa, pb = peak_of(a), peak_of(b)
+        ms_a, ms_b = alternate([a, b], args.reps, args.warmup)
+        cells = v.numel() // (3 if name == "ns_momentum" else 1)
+        field = cells * 4
+        emit(f"{name}: shape {list(v.shape)} route {route}; A (pi_loss + backward) {ms_a:.3f} ms, B (method(v).pow(2).mean().backward()) "
+             f"{ms_b:.3f} ms, B/A = {ms_b / ms_a:.2f}x; peak memory A {pa / field:.2f} fields ({pa / 2**30:.2f} GiB), "
+             f"B {pb / field:.2f} fields ({pb / 2**30:.2f} GiB); A at {streams_a} streams = "
+             f"{streams_a * field / (ms_a * 1e-3) / HBM:.3f} of 8 TB/s; max |grad A - grad B| / max |grad B| = {err:.2e}")
+        if name == "ns_momentum":
+            emit(f"ns_momentum floor, A at least 3x faster than B: {'met' if ms_b >= 3 * ms_a else 'MISSED'} ({ms_b / ms_a:.2f}x)")
+            gg = rand(*([v.shape[0]] + list(v.shape[2:])))
+            vd = v.detach()
+            (ms_v,) = alternate([lambda: losses.residual_vjp(method, vd, gg, boundary=True)], args.reps, args.warmup)
+            emit(f"ns_momentum VJP launch alone (pre_vjp_ns_momentum_f32, 3 streams in, 3 out, device events around the call): "
+                 f"{ms_v:.3f} ms, 6 x 4 B x {cells} cells / time = {6 * field / (ms_v * 1e-3) / 1e12:.2f} TB/s = "
+                 f"{6 * field / (ms_v * 1e-3) / HBM:.3f} of 8 TB/s")
+            del gg
+        del v, a, b
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
