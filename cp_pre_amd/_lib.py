@@ -188,6 +188,27 @@ VJP_SIGNATURES = {
     "pre_vjp_sumsq_f32": [_fld] + [c_int64] * 4 + [c_int, _fp, _fp, c_void_p],
 }
 
+# libcp_pre_screen.so (include/cp_pre_screen.h): per-sample score and per-level inside counts in the residual's own launch
+SCREEN_SO_PATH = os.path.join(_HERE, "libcp_pre_screen.so")
+PRE_SCREEN_ABI_VERSION = 1
+PRE_SCREEN_MAX_LEVELS = 16
+
+
+class PreScreen(ctypes.Structure):
+    """``pre_screen_t``: the levels, the modulation view, the crop and the accumulators of one screening launch."""
+    _fields_ = [("q", c_void_p), ("nk", c_int), ("modulation", c_void_p), ("mT", c_int64), ("mX", c_int64),
+                ("ct", c_int), ("cx", c_int), ("cy", c_int), ("score", c_void_p), ("count", c_void_p), ("count_ld", c_int64)]
+
+
+_scr = [POINTER(PreScreen)] + [c_int64] * 4 + [c_int, c_void_p]          # s, B, T, X, Y, flags, stream
+SCREEN_SIGNATURES = {
+    "pre_screen_abi_version": [],
+    "pre_screen_stencil3d_f32": [_fld, POINTER(c_float), POINTER(c_int32), c_int] + _scr,
+    "pre_screen_linear2_f32": [_fld, _fld, POINTER(c_float), POINTER(c_float), c_float] + _scr,
+    "pre_screen_ns_momentum_f32": [_fld, _fld, _fld] + [POINTER(c_float)] * 4 + [c_float] * 4 + _scr,
+    "pre_screen_mhd_f32": [c_int, POINTER(PreField)] + [POINTER(c_float)] * 3 + [c_double] + _scr,
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -207,8 +228,9 @@ _LIBS = {
 # The libraries added since: same five-tuple, a table of their own (``_load`` consults both)
 _LIBS_MORE = {
     "vjp": ("_vjp", "VJP_", "pre_vjp_abi_version", "PRE_VJP_ABI_VERSION", ()),
+    "screen": ("_screen", "SCREEN_", "pre_screen_abi_version", "PRE_SCREEN_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -273,6 +295,10 @@ def load_bounds():
 
 def load_vjp():
     return _vjp or _load("vjp")
+
+
+def load_screen():
+    return _screen or _load("screen")
 
 
 def require_gpu():

@@ -1,0 +1,400 @@
+"""Screen predictions against calibrated sets without storing the residual.
+
+What a calibrated joint set is used for afterwards (``Joint/NS_Residuals_CP.py:328-329,350-352,502-503``,
+``Joint/MHD_Residuals_CP.py:409-410``, ``Active_Learning/Burgers_AL_Joint.py:305-379``,
+``Other_UQ/Evaluation/Eval.py:287-288``) is to ask of each new prediction whether its residual lies inside the set::
+
+    ns = NavierStokes(dt, dx, dy)
+    s = screen(ns.residual_momentum, vars, qhats, modulation)     # one launch, no residual tensor
+    s.score                 # fp32 [n]      max over the counted cells of |r| / m   (ncf_metric_joint(..., crop=1))
+    s.inside                # int64 [nk, n] counted cells with |r| <= q_k * m
+    s.accept()              # bool [nk, n]  filter_sims_joint at every level
+    s.coverage_joint()      # float64 [nk]  emp_cov_joint at every level
+    s.coverage_marginal()   # float64 [nk]  emp_cov at every level, bounds +-q_k * m
+    s.within(0.95)          # bool [nk, n]  filter_sims_within_bounds
+
+Fused route (``libcp_pre_screen.so``, ``include/cp_pre_screen.h``): the march of the residual passes evaluates the residual
+in registers and reduces it per sample - a maximum and nk integer counts - so the three launches and the residual buffer of
+the route a user writes today (residual, ``ncf_metric_joint``, ``CoverageLevels``) become one launch that stores nothing.
+Fused kinds: ``stencil3d`` (a ``ConvOperator`` of ``convops_2d``, ``PRE_Wave``), ``linear2`` (NS continuity, MHD gauss),
+``ns_momentum``, ``mhd_continuity`` / ``mhd_momentum`` / ``mhd_energy`` / ``mhd_induction``.  Everything else takes that
+three-pass route (residual, ``ncf_metric_joint``, then ``CoverageLevels`` once per sample) and returns the same ``Screened``: the 1-D family (Advection, Burgers: their marched axis is the batch),
+JOREK, views without unit stride on their last axis, row widths that are no multiple of 4, inputs on the CPU (staged as
+elsewhere), ``minus=``, operator kernels off the 7-point star or requiring grad, ``fused=False``, float64 levels or
+modulation.  ``last_route()`` says which route the last call took.
+
+Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _dispatch, _lib
+from . import inductive_cp as icp
+from . import residuals as R
+from .convops_1d import ConvOperator as ConvOperator1D
+from .convops_2d import ConvOperator as ConvOperator2D
+from .losses import _is_star
+
+_last_route = None
+
+
+def last_route():
+    """'fused:<kind>' or 'fallback:<why>' of the last ``screen`` / ``Screen.add_slab`` call."""
+    return _last_route
+
+
+# ------------------------------------------------------------------------------------------- the result
+class Screened:
+    """``score`` fp32 [n], ``inside`` int64 [nk, n], ``cells`` counted cells per sample (host int)."""
+
+    def __init__(self, score, inside, cells):
+        self.score, self.inside, self.cells = score, inside, int(cells)
+
+    def accept(self):
+        """bool [nk, n]: every counted cell of the sample inside the level's band (``filter_sims_joint`` per level)."""
+        return self.inside == self.cells
+
+    def _group_sum(self, t, group):
+        if group is not None:
+            torch.distributed.all_reduce(t, group=group)
+        return t.cpu().numpy()
+
+    def coverage_joint(self, group=None):
+        """float64 [nk]: fraction of samples accepted (``emp_cov_joint`` per level: count / n in float64).  ``group``: the
+        ranks that split the samples; one all-reduce of int64 [nk + 1]."""
+        nk, n = self.inside.shape
+        buf = torch.empty(nk + 1, dtype=torch.int64, device=self.inside.device)
+        torch.sum(self.accept(), dim=1, out=buf[:nk])
+        buf[nk] = n
+        host = self._group_sum(buf, group)
+        return np.array([float(c) / float(host[nk]) for c in host[:nk]], np.float64)
+
+    def coverage_marginal(self, group=None):
+        """float64 [nk]: fraction of all counted cells of all samples inside (``emp_cov`` per level, bounds +-q_k * m)."""
+        nk, n = self.inside.shape
+        buf = torch.empty(nk + 1, dtype=torch.int64, device=self.inside.device)
+        torch.sum(self.inside, dim=1, out=buf[:nk])
+        buf[nk] = n * self.cells
+        host = self._group_sum(buf, group)
+        return np.array([float(c) / float(host[nk]) for c in host[:nk]], np.float64)
+
+    def within(self, threshold):
+        """bool [nk, n]: at least ``threshold`` of the sample's counted cells inside, compared in float64
+        (``filter_sims_within_bounds(..., within=True)``)."""
+        return (self.inside.double() / float(self.cells)) >= threshold
+
+
+# ------------------------------------------------------------------------------------------- what a method is
+_MHD_EQ = {"residual_continuity": 0, "residual_momentum": 1, "residual_energy": 2, "residual_induction": 3}
+_MHD_CHAN = {0: (0, 1, 2), 1: tuple(range(6)), 2: tuple(range(6)), 3: (1, 2, 4, 5)}
+
+
+class _Spec:
+    """One residual method, resolved as ``losses._Spec`` resolves it: ``kind`` (None: no fused screen), ``chan`` - the
+    channels of a stacked ``[BS,F,...]`` input the residual reads (None: the input is the field itself)."""
+
+    def __init__(self, method):
+        self.method, self.kind, self.why, self.chan, self.nd, self.ops = method, None, None, None, 3, ()
+        self.is_op = isinstance(method, (ConvOperator1D, ConvOperator2D))
+        obj = method if self.is_op else getattr(method, "__self__", None)
+        name = getattr(method, "__name__", "")
+        self.obj = obj
+        if self.is_op:
+            self.nd = 2 if isinstance(method, ConvOperator1D) else 3
+            if getattr(method, "conv", None) != method.convolution:
+                self.why = "spectral operator"
+            elif self.nd == 2:
+                self.why = "1-D family: the marched axis is the batch"
+            else:
+                self.kind, self.ops = "stencil3d", (method,)
+        elif obj is None or not callable(method):
+            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
+        elif isinstance(obj, R.NavierStokes) and name in ("residual_momentum", "residual"):
+            self.kind, self.chan, self.ops = "ns_momentum", (0, 1, 2), (obj.D_t, obj.D_x, obj.D_y, obj.D_xx_yy)
+        elif isinstance(obj, R.NavierStokes) and name == "residual_continuity":
+            self.kind, self.chan, self.ops, self.ratio = "linear2", (0, 1), (obj.D_x, obj.D_y), obj.dx / obj.dy
+        elif isinstance(obj, R.MHD) and name == "residual_gauss":
+            self.kind, self.chan, self.ops, self.ratio = "linear2", (4, 5), (obj.D_x, obj.D_y), 1.0
+        elif isinstance(obj, R.MHD) and (name in _MHD_EQ or name == "residual"):
+            self.eq = _MHD_EQ.get(name, 3)                        # (PRE_MHD.residual is the induction equation)
+            self.kind = "mhd_" + ("continuity", "momentum", "energy", "induction")[self.eq]
+            self.chan, self.ops = _MHD_CHAN[self.eq], (obj.D_t, obj.D_x, obj.D_y)
+        elif isinstance(obj, R.PRE_Wave) and name == "residual":
+            self.kind, self.ops = "stencil3d", (obj.D,)
+        elif isinstance(obj, (R.Burgers, R.Advection)) and name == "residual":
+            self.nd, self.why = 2, "1-D family: the marched axis is the batch"
+        elif isinstance(obj, R.JOREK) and name in ("residual_continuity", "residual_temperature"):
+            self.why, self.chan = "no fused screen for JOREK", ()
+        else:
+            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
+
+    def field_shape(self, x):
+        """Shape of the uncropped residual of input ``x``; raises on a rank the method does not take."""
+        if isinstance(self.obj, R.JOREK):
+            if x.dim() != 5:
+                raise ValueError(f"expected vars [BS,F,Nx,Ny,Nt], got {tuple(x.shape)}")
+            return (x.shape[0], x.shape[4], x.shape[2], x.shape[3])
+        if self.chan is not None:
+            need = max(self.chan) + 1
+            if x.dim() != 5 or x.shape[1] < need:
+                raise ValueError(f"expected vars [BS,F>={need},Nt,Nx,Ny], got {tuple(x.shape)}")
+            return (x.shape[0],) + tuple(x.shape[2:])
+        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5:
+            return (x.shape[0],) + tuple(x.shape[2:])
+        if x.dim() != self.nd + 1:
+            raise ValueError(f"expected a {self.nd + 1}-D field, got {tuple(x.shape)}")
+        return tuple(x.shape)
+
+    def reads_halo(self):
+        """Does the method's own residual pass take ``halo_x``?  (A ``ConvOperator`` call, NS continuity and MHD gauss do
+        not: their slabs would be evaluated against zero padding.)"""
+        return not self.is_op and self.kind != "linear2" and isinstance(self.obj, (R.NavierStokes, R.MHD, R.PRE_Wave))
+
+    def full(self, x, minus, halo_x):
+        """The uncropped residual by the existing passes (what the fallback's first launch is)."""
+        if halo_x and not self.reads_halo():
+            raise RuntimeError("halo_x: only the fused screen reads the halo rows for this method, and it declined")
+        with torch.no_grad():
+            kw = {} if minus is None else {"minus": minus}
+            if halo_x:
+                kw["halo_x"] = True
+            if self.is_op:
+                r = self.method(x)
+                return r if minus is None else r - self.method(minus)
+            return self.method(x, boundary=True, **kw)
+
+    def fields(self, x):
+        if self.chan is None:
+            return [x[:, 0] if x.dim() == 5 else x]
+        return [x[:, i] for i in self.chan]
+
+    def prepare(self, x, minus, qhats, modulation):
+        """(why, kernels): ``why`` is None if the fused screen can run; host checks and one download of the operator
+        kernels (``_dispatch.host_kernel`` on every call: a screen applies the kernels its operators hold now)."""
+        if self.kind is None:
+            return self.why, ()
+        if minus is not None:
+            return "minus=", ()
+        if not x.is_cuda:
+            return "input on the CPU", ()
+        if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
+            return "float64 levels or modulation", ()
+        if x.stride(-1) != 1:
+            return "no unit stride on the last axis", ()
+        if x.shape[-1] % 4 != 0:
+            return "row width not a multiple of 4", ()
+        if getattr(self.obj, "fused", True) is False:
+            return "fused=False", ()
+        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
+            return "operator kernel requires grad", ()
+        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
+            return "multi-channel wave input", ()
+        if self.kind.startswith("mhd_") and x.shape[1] < 6:
+            return "fewer than six MHD channels", ()              # (pre_screen_mhd_f32 takes the six views)
+        ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
+        if self.kind == "stencil3d":
+            if ks[0].ndim != 3 or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
+                return "operator kernel off the 7-point star", ()
+            w, off = _dispatch.taps_of(ks[0])
+            if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
+                return "operator kernel off the 7-point star", ()
+            return None, (w, off)
+        if any(k.shape != (3, 3, 3) or not _is_star(k) for k in ks):
+            return "operator kernel off the 7-point star", ()
+        return None, tuple(_lib.farr(k.reshape(-1)) for k in ks)
+
+    def launch(self, kernels, x, st, flags):
+        """The fused launch on device views; returns the library's code."""
+        lib = _lib.load_screen()
+        fs = self.fields(x)
+        shape = tuple(fs[0].shape)
+        tail = (ctypes.byref(st), *shape, flags, _lib.stream())
+        if self.kind == "stencil3d":
+            w, off = kernels
+            wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
+            ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
+            return lib.pre_screen_stencil3d_f32(ctypes.byref(_lib.field(fs[0])), wv, ov, len(w), *tail)
+        if self.kind == "linear2":
+            return lib.pre_screen_linear2_f32(ctypes.byref(_lib.field(fs[0])), ctypes.byref(_lib.field(fs[1])), *kernels,
+                                              float(self.ratio), *tail)
+        if self.kind == "ns_momentum":
+            o = self.obj
+            return lib.pre_screen_ns_momentum_f32(*[ctypes.byref(_lib.field(f)) for f in fs], *kernels, float(o.dt), float(o.dx),
+                                                  float(o.dy), float(o.nu), *tail)
+        six = R._arr([x[:, i] for i in range(6)])
+        return lib.pre_screen_mhd_f32(self.eq, six, *kernels, float(self.obj.gamma), *tail)
+
+
+# ------------------------------------------------------------------------------------------- validation (host only)
+def _check_inputs(spec, vars, qhats, modulation, minus, crop, nk=None):
+    """Every shape, dtype and device error, raised before any device work.  Returns the residual's uncropped shape."""
+    if not isinstance(vars, torch.Tensor):
+        raise TypeError("vars must be a torch.Tensor")
+    if vars.dtype != torch.float32:
+        raise TypeError(f"vars has dtype {vars.dtype}: the screen takes float32 fields")
+    shape = spec.field_shape(vars)
+    if vars.numel() == 0:
+        raise ValueError("screen of an empty batch")
+    if not isinstance(qhats, torch.Tensor):
+        raise TypeError("qhats must be a torch.Tensor [nk]")
+    if qhats.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"qhats has dtype {qhats.dtype}: float32 levels (float64 ones take the fallback)")
+    if qhats.dim() != 1 or not 1 <= qhats.shape[0] <= _lib.PRE_SCREEN_MAX_LEVELS:
+        raise ValueError(f"qhats has shape {tuple(qhats.shape)}, expected [nk] with 1 <= nk <= {_lib.PRE_SCREEN_MAX_LEVELS}")
+    if nk is not None and qhats.shape[0] != nk:
+        raise ValueError(f"qhats has shape {tuple(qhats.shape)}, expected ({nk},)")
+    if qhats.device != vars.device:
+        raise ValueError(f"qhats is on {qhats.device}, vars on {vars.device}")
+    if modulation is not None:
+        if not isinstance(modulation, torch.Tensor):
+            raise TypeError("modulation must be a torch.Tensor or None")
+        if modulation.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"modulation has dtype {modulation.dtype}")
+        if tuple(modulation.shape) != tuple(shape[1:]):
+            raise ValueError(f"modulation has shape {tuple(modulation.shape)}, expected {tuple(shape[1:])}: the uncropped "
+                             "extents of the residual")
+        if modulation.device != vars.device:
+            raise ValueError(f"modulation is on {modulation.device}, vars on {vars.device}")
+    if minus is not None:
+        R._check_minus(vars, minus)
+    crop = tuple(int(c) for c in crop)
+    if len(crop) != len(shape) - 1 or any(c < 0 for c in crop):
+        raise ValueError(f"crop {crop}: one non-negative count per residual axis")
+    if any(n - 2 * c <= 0 for n, c in zip(shape[1:], crop)):
+        raise ValueError(f"crop {crop} leaves no cell of a {tuple(shape[1:])} residual")
+    cells = 1
+    for n, c in zip(shape[1:], crop):
+        cells *= n - 2 * c
+    if cells >= 1 << 32:
+        raise ValueError("cells per sample >= 2^32: screen the grid in slabs")
+    return shape, crop, cells
+
+
+def _dev_key(d):
+    d = torch.device(d)
+    return d.type, (d.index or 0)
+
+
+class Screen:
+    """Accumulating screen of ``n_local`` samples at ``nk`` levels: ``add_slab`` once per slab of the grid (x-slabs with
+    ``halo_x``, t-slabs with their halo planes, as ``JointCalibration.add_slab`` takes them), ``finish`` -> ``Screened``.
+    Maximum and integer adds compose exactly: the slabs of a grid give the bits of the whole grid."""
+
+    def __init__(self, n_local, nk, device):
+        if n_local < 1 or not 1 <= nk <= _lib.PRE_SCREEN_MAX_LEVELS:
+            raise ValueError(f"Screen needs n_local >= 1 and 1 <= nk <= {_lib.PRE_SCREEN_MAX_LEVELS} (got {n_local}, {nk})")
+        self.n_local, self.nk, self.device = int(n_local), int(nk), torch.device(device)
+        self.acc = None                # int32 [nk + 1, n_local]: row 0 the score's bits, rows 1.. the counts; made at the first slab
+        self.cells = 0
+
+    def _buffers(self, device):
+        if self.acc is None:
+            self.acc = torch.zeros(self.nk + 1, self.n_local, dtype=torch.int32, device=device)
+        return self.acc
+
+    def add_slab(self, method, vars_slab, qhats, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None):
+        """``vars_slab``: the method's input on a slab of the grid (all local samples); ``modulation_slab`` [T,X,Y] of the
+        slab's uncropped residual extents, or None (m == 1); ``crop`` cells per side of each residual axis are left out
+        (``JointCalibration.add_slab``'s meaning); ``halo_x``: the slab's rows -1 and X lie in the same memory."""
+        global _last_route
+        spec = method if isinstance(method, _Spec) else _Spec(method)
+        shape, crop, cells = _check_inputs(spec, vars_slab, qhats, modulation_slab, minus, crop, self.nk)
+        if shape[0] != self.n_local:
+            raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
+        if _dev_key(vars_slab.device) != _dev_key(self.device):
+            raise ValueError(f"slab on {vars_slab.device}, this Screen was made for {self.device}")
+        why, kernels = spec.prepare(vars_slab, minus, qhats, modulation_slab)
+        if halo_x and not vars_slab.is_cuda:
+            raise ValueError("halo_x needs a device-resident view of a larger grid (a staged copy has no halo rows)")
+        if halo_x and why is not None and not spec.reads_halo():
+            # (before any device work: this slab would be evaluated against zero padding and counted as if it were right)
+            raise RuntimeError(f"halo_x: the fused screen cannot run ({why}) and no other pass of this method reads the halo rows")
+        if why is None:
+            acc = self._buffers(vars_slab.device)
+            mod = modulation_slab
+            if mod is not None and mod.stride(-1) != 1:
+                mod = mod.contiguous()
+            q = qhats.contiguous()
+            st = _lib.PreScreen(_lib.ptr(q), self.nk, _lib.ptr(mod), mod.stride(0) if mod is not None else 0,
+                                mod.stride(1) if mod is not None else 0, crop[0], crop[1], crop[2],
+                                ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
+            with torch.no_grad(), torch.cuda.device(vars_slab.device):
+                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0)
+            if rc == _lib.PRE_E_UNSUPPORTED:
+                why = "declined by the library"
+                if halo_x and not spec.reads_halo():
+                    raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
+            else:
+                _lib.check(rc, "pre_screen_" + spec.kind.split("_")[0] + "_f32")
+                _last_route = "fused:" + spec.kind
+                self.cells += cells
+                return
+        _last_route = "fallback:" + why
+        self._fallback(spec, vars_slab, qhats, modulation_slab, crop, halo_x, minus)
+        self.cells += cells
+
+    def _fallback(self, spec, vars, qhats, modulation, crop, halo_x, minus):
+        """What a user writes today: the residual by the existing pass with ``boundary=True``, ``ncf_metric_joint`` over
+        the cropped interior, ``CoverageLevels`` for the counts.  ``CoverageLevels`` counts over all the samples it is
+        given, so the per-sample counts take one pass PER SAMPLE (n launches over a sample each; together they read the
+        residual once): this route is for correctness where the fused launch cannot run, not for speed."""
+        from . import pipeline
+        res = spec.full(vars, minus, halo_x)
+        res, _ = _dispatch.to_device(res)
+        acc = self._buffers(res.device)
+        wide = qhats.dtype == torch.float64 or (modulation is not None and modulation.dtype == torch.float64)
+        q = qhats.to(res.device)
+        mod = modulation.to(res.device) if modulation is not None else None
+        sl = (slice(None),) + tuple(slice(c, n - c) for c, n in zip(crop, res.shape[1:]))
+        if wide:
+            # numpy would compute the score and the bounds in float64: so does this route (torch, on the device)
+            r64 = res[sl].double().abs()
+            m64 = mod[sl[1:]].double() if mod is not None else None
+            s = (r64 / m64 if m64 is not None else r64).reshape(res.shape[0], -1)
+            score = s.max(dim=1).values
+            score = torch.where(torch.isnan(s).any(dim=1), torch.full_like(score, float("nan")), score).float()
+            hw = q.double().reshape(-1, *([1] * (res.dim() - 1)))
+            hw = hw * m64 if m64 is not None else hw
+            counts = torch.stack([(r64 <= hw[k]).reshape(res.shape[0], -1).sum(dim=1) for k in range(self.nk)])
+        else:
+            ones = mod if mod is not None else torch.ones(res.shape[1:], dtype=torch.float32, device=res.device)
+            if len(set(crop)) == 1 and res.dim() == 4:
+                score = icp.ncf_metric_joint(res, None, ones, crop=crop[0])
+            else:
+                score = icp.ncf_metric_joint(res[sl].contiguous(), None, ones[sl[1:]].contiguous())
+            # the counts per sample: a CoverageLevels pass per sample (its marginal count is a total over its samples)
+            rows, mrows = res[sl], (mod[sl[1:]] if mod is not None else None)
+            counts = torch.empty(self.nk, res.shape[0], dtype=torch.int64, device=res.device)
+            cov = pipeline.CoverageLevels(1, self.nk, res.device)
+            for i in range(res.shape[0]):
+                cov.acc.zero_()
+                cov.add_slab(rows[i:i + 1], q, modulation=mrows)
+                counts[:, i] = cov.acc
+        bits = score.contiguous().view(torch.int32)
+        # unsigned maximum of the bit patterns (non-negative scores: the patterns are non-negative int32 too)
+        torch.maximum(acc[0], bits, out=acc[0])
+        acc[1:] += counts.to(torch.int32)
+
+    def finish(self):
+        if self.acc is None or self.cells == 0:
+            raise ValueError("Screen.finish() before any slab")
+        return Screened(self.acc[0].view(torch.float32).clone(), self.acc[1:].to(torch.int64) & 0xffffffff, self.cells)
+
+
+def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=None):
+    """Screen the predictions ``vars`` against the sets ``|r| <= qhats[k] * modulation``.  ``boundary=False``: the counted
+    cells are the interior ``[1:-1]`` of every residual axis, as the reference crops its residuals (``modulation`` keeps
+    the uncropped extents: its rim is never used); ``boundary=True``: every cell.  Returns a :class:`Screened`."""
+    spec = _Spec(residual_method)
+    crop = (0,) * spec.nd if boundary else (1,) * spec.nd
+    shape, _, _ = _check_inputs(spec, vars, qhats, modulation, minus, crop)
+    s = Screen(shape[0], qhats.shape[0], vars.device)
+    s.add_slab(spec, vars, qhats, modulation, crop=crop, minus=minus)
+    out = s.finish()
+    if not vars.is_cuda:                                     # (staged inputs: the verdicts come home, as elsewhere)
+        out.score, out.inside = out.score.to(vars.device), out.inside.to(vars.device)
+    return out

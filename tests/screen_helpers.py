@@ -1,0 +1,169 @@
+"""Helpers shared by tests/test_screen_cpu.py and tests/test_gpu_screen.py: the inputs of every screening case and their
+float64 reference, from the oracle alone.
+
+Reference: ``oracle.residuals.*`` evaluated in float64 on CPU copies of the fields (the oracle's operators hold float32
+taps; ``oracle_fp64`` casts them to the field's dtype at the one place the oracle convolves), uncropped; from it
+``s_ref = max |r_ref| / m`` and ``count_ref[k] = #{|r_ref| <= q_k * m}`` over the counted region, m and q_k taken as the
+float32 values the device gets, the arithmetic in float64.
+
+Tolerances (tests/test_gpu_screen.py): tau = 1e-5 * max |r_ref|, m_min the smallest modulation in the
+counted region; score within tau / m_min + one fp32 ulp of s_ref; a cell is undecided at level k if
+``||r_ref| - q_k m| <= tau``, the counts may differ from count_ref by the undecided cells of that (k, sample), which are at
+most 1 % of the counted cells; ``accept`` is exact for every sample, because every q_k lies further than tau / m_min from
+every s_ref.  tests/test_screen_cpu.py asserts those caps for every case below."""
+import contextlib
+
+import numpy as np
+import torch
+
+from oracle import convops as ocv
+from oracle import residuals as orr
+
+NS_DT, NS_DX, NS_DY, NS_NU = 0.01, 1 / 64, 1 / 32, 0.001
+WAVE_DT, WAVE_DX = 0.01, 0.02
+KINDS = ("wave", "lap", "ns_continuity", "ns_momentum", "mhd_continuity", "mhd_momentum", "mhd_energy", "mhd_induction",
+         "mhd_gauss")
+FUSED_KIND = {"wave": "stencil3d", "lap": "stencil3d", "ns_continuity": "linear2", "ns_momentum": "ns_momentum",
+              "mhd_continuity": "mhd_continuity", "mhd_momentum": "mhd_momentum", "mhd_energy": "mhd_energy",
+              "mhd_induction": "mhd_induction", "mhd_gauss": "linear2"}
+NCHAN = {"wave": None, "lap": None, "ns_continuity": 2, "ns_momentum": 3, "mhd_continuity": 6, "mhd_momentum": 6,
+         "mhd_energy": 6, "mhd_induction": 6, "mhd_gauss": 6}
+N_CAL = 8
+
+
+@contextlib.contextmanager
+def oracle_fp64():
+    """The oracle's convolution with its float32 taps cast to the field's dtype: ``oracle.residuals`` in float64."""
+    orig = ocv.xcorr_torch
+    ocv.xcorr_torch = lambda field, kernel: orig(field, kernel.to(field.dtype))
+    try:
+        yield
+    finally:
+        ocv.xcorr_torch = orig
+
+
+def oracle_residual(kind, x):
+    """The uncropped residual of ``x`` (float64 CPU) by the oracle."""
+    with oracle_fp64():
+        if kind == "wave":
+            return orr.wave_residual(x, 1.0, WAVE_DT, WAVE_DX, boundary=True)
+        if kind == "lap":
+            return ocv.ConvOperator2D(("x", "y"), 2)(x)
+        if kind == "ns_continuity":
+            return orr.ns_continuity(x, NS_DX, NS_DY, boundary=True)
+        if kind == "ns_momentum":
+            return orr.ns_momentum(x, NS_DT, NS_DX, NS_DY, NS_NU, boundary=True)
+        return getattr(orr, kind)(x, boundary=True)
+
+
+def method_of(kind, device="cpu"):
+    """The ``cp_pre_amd`` method the screen takes for ``kind``."""
+    from cp_pre_amd import residuals as R
+    from cp_pre_amd.convops_2d import ConvOperator
+    if kind == "wave":
+        return R.PRE_Wave(WAVE_DT, WAVE_DX, device=device).residual
+    if kind == "lap":
+        return ConvOperator(("x", "y"), 2, device=device)
+    if kind.startswith("ns_"):
+        return getattr(R.NavierStokes(NS_DT, NS_DX, NS_DY, nu=NS_NU, device=device), "residual_" + kind[3:])
+    return getattr(R.MHD(device=device), "residual_" + kind[4:])
+
+
+def fields(kind, shape, seed=0, n=None):
+    """float32 CPU input of ``kind`` on (B, T, X, Y): per channel a positive base, one smooth mode and noise whose
+    amplitude grows by half from sample to sample (so the per-sample scores lie well apart)."""
+    B, T, X, Y = shape
+    B = B if n is None else n
+    gen = torch.Generator().manual_seed(7919 * seed + sum(shape) + len(kind))
+    nch = NCHAN[kind] or 1
+    t = torch.arange(T, dtype=torch.float64)[:, None, None] / T
+    x = torch.arange(X, dtype=torch.float64)[None, :, None] / X
+    y = torch.arange(Y, dtype=torch.float64)[None, None, :] / Y
+    out = torch.empty(B, nch, T, X, Y, dtype=torch.float64)
+    for b in range(B):
+        amp = 0.02 * 1.5 ** (b % 8)
+        for c in range(nch):
+            ph = 2 * np.pi * torch.rand(1, generator=gen, dtype=torch.float64)
+            mode = torch.sin(2 * np.pi * ((1 + c % 2) * x + (1 + (c + 1) % 3) * y + t) + ph)
+            out[b, c] = 1.0 + 0.1 * c + 0.2 * mode + amp * torch.randn(T, X, Y, generator=gen, dtype=torch.float64)
+    out = out.float()
+    return out[:, 0] if NCHAN[kind] is None else out
+
+
+def modulation(kind, shape, seed=0):
+    """float32 [T,X,Y]: [0.5, 2] times the per-cell std of the residuals of a synthetic calibration set of N_CAL
+    samples."""
+    cal = oracle_residual(kind, fields(kind, shape, seed + 100, n=N_CAL).double())
+    gen = torch.Generator().manual_seed(31 * seed + sum(shape))
+    u = 0.5 + 1.5 * torch.rand(cal.shape[1:], generator=gen, dtype=torch.float64)
+    return (u * cal.std(dim=0, unbiased=False)).float()
+
+
+def region(shape, crop):
+    return (slice(None),) + tuple(slice(c, n - c) for c, n in zip(crop, shape[1:]))
+
+
+class Case:
+    """One screening case: inputs, levels and the float64 reference with its tolerances."""
+
+    def __init__(self, kind, shape, boundary, with_mod, nk, seed=0, crop=None):
+        self.kind, self.shape, self.boundary, self.nk = kind, tuple(shape), boundary, nk
+        self.crop = tuple(crop) if crop is not None else ((0, 0, 0) if boundary else (1, 1, 1))
+        self.x = fields(kind, shape, seed)
+        self.mod = modulation(kind, shape, seed) if with_mod else None
+        r = oracle_residual(kind, self.x.double())
+        self.r_ref = r
+        reg = region(self.shape, self.crop)
+        self.a = r[reg].abs().reshape(r.shape[0], -1)                                # |r_ref| [B, cells]
+        m = self.mod.double() if with_mod else torch.ones(r.shape[1:], dtype=torch.float64)
+        self.m = m[reg[1:]].reshape(-1)                                               # [cells]
+        self.cells = self.m.numel()
+        self.tau = 1e-5 * float(r.abs().max())
+        self.m_min = float(self.m.min())
+        self.s_ref = (self.a / self.m).max(dim=1).values
+        self.tol_s = self.tau / self.m_min
+        self.q = self._levels()
+        hw = self.q.double()[:, None] * self.m[None, :]                               # [nk, cells]
+        d = self.a[None] - hw[:, None]                                                # [nk, B, cells]
+        self.count_ref = (d <= 0).sum(dim=2)
+        self.undecided = (d.abs() <= self.tau).sum(dim=2)
+        self.accept_ref = self.s_ref[None, :] <= self.q.double()[:, None]
+
+    def _levels(self):
+        """nk float32 levels: the midpoints of the widest gaps of the sorted per-sample scores (the levels at which
+        some samples are accepted and others rejected), one above every score, the rest at quantiles of |r_ref| / m over
+        all counted cells."""
+        s = torch.sort(self.s_ref).values
+        gaps = [(float(s[i + 1] - s[i]), float(0.5 * (s[i] + s[i + 1]))) for i in range(len(s) - 1)]
+        mids = [g[1] for g in sorted(gaps, reverse=True)]
+        lv = mids[:max(1, min(len(mids), self.nk // 2))] if mids else [2.0 * float(s[-1])]
+        if len(lv) < self.nk:
+            lv.append(1.5 * float(s[-1]))
+        ratio = (self.a / self.m).reshape(-1)
+        nq = self.nk - len(lv)
+        if nq > 0:
+            ps = torch.linspace(0.3, 0.99, nq, dtype=torch.float64)
+            lv += [float(v) for v in torch.quantile(ratio, ps)]
+        return torch.tensor(sorted(lv[:self.nk]), dtype=torch.float32)
+
+    def caps(self):
+        """(largest share of undecided cells over (k, sample), smallest |s_ref - q_k| in units of tau / m_min, does a
+        level split the samples)"""
+        share = float(self.undecided.max()) / self.cells
+        dist = float((self.s_ref[None, :] - self.q.double()[:, None]).abs().min()) / self.tol_s
+        split = bool(((self.accept_ref.sum(dim=1) > 0) & (self.accept_ref.sum(dim=1) < self.accept_ref.shape[1])).any())
+        return share, dist, split
+
+
+# (B, T, X, Y) of the GPU cases, by the seam they cross (screen_march_kernel: 32 rows x 64 columns for Ny < 96, 16 x 128
+# below 192, 8 x 256 from there; pick_tseg halves T until <= 16; tap-free marches of 8 planes)
+SEAM_SHAPES = {
+    "two_tseg": (3, 17, 5, 12),              # 9 + 8 planes
+    "three_tseg_last_one": (3, 65, 5, 12),   # 7 x 9 + 2: with the t crop the last march is one plane
+    "rows2_narrow": (3, 4, 33, 16),          # 2 row tiles of 32
+    "rows3_narrow": (3, 4, 65, 64),          # 3 row tiles of 32
+    "rows3_mid": (3, 4, 33, 100),            # 3 row tiles of 16, 128-column tile
+    "rows3_wide": (3, 4, 17, 200),           # 3 row tiles of 8
+    "cols2_wide": (3, 4, 9, 260),            # 2 column tiles of 256
+}
+ODD_SHAPES = [(3, 5, 9, 13), (3, 5, 9, 66), (3, 4, 9, 257)]      # partial last quad: the three-pass route

@@ -1,0 +1,152 @@
+"""Screening predictions against calibrated sets on one GPU: the fused screen (A, ``screen.Screen.add_slab``: ONE launch of
+``libcp_pre_screen.so``, nothing stored) against the three-pass route built from the functions that existed before it (B:
+the fused residual pass into a preallocated buffer, ``HipOps.max_scores`` - the joint score pass ``ncf_metric_joint``
+runs - and one joint ``CoverageLevels`` pass: the accept flags, NOT the per-sample counts that A also delivers, so B does
+somewhat less than A and than the package's own fallback), and (R) the residual launch of B ALONE on the same fields.  All three run in
+one process on the same tensors, interleaved call by call; each figure is the median over --blocks alternating blocks of
+--reps calls, and the spread of the block medians is reported with it (the margin any comparison has to be read with).
+nk = 10 levels.  One JSON line per case on stdout and appended to --out.
+
+Shapes (``--div N`` divides every batch by N; the default runs them whole):
+    ns_rank    NS momentum on the per-rank shape [512,3,64,512,512]
+    c3_xslab   NS momentum on one C3 x-slab [4096,3,64,32(+2 halo rows),512], halo_x
+    c4_mhd     MHD induction on the C4 shard [1024,6,64,256,256]
+    c2_wave    the wave residual on [512,32,256,256]
+
+    python tools/screen_bench.py [--cases ns_rank,c2_wave] [--div 8] [--reps 3] [--blocks 5]
+    rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
+        (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from cp_pre_amd import pipeline, screen  # noqa: E402
+from cp_pre_amd import residuals as R  # noqa: E402
+
+NK = 10
+
+
+def _ev():
+    return torch.cuda.Event(enable_timing=True)
+
+
+def blocks_of(fns, reps, blocks, warmup):
+    """per fn: (median of the block medians, smallest, largest) in ms; the fns interleaved call by call"""
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    meds = [[] for _ in fns]
+    for _ in range(blocks):
+        times = [[] for _ in fns]
+        for _ in range(reps):
+            for i, f in enumerate(fns):
+                a, b = _ev(), _ev()
+                a.record()
+                f()
+                b.record()
+                b.synchronize()
+                times[i].append(a.elapsed_time(b))
+        for i, t in enumerate(times):
+            meds[i].append(sorted(t)[len(t) // 2])
+    return [(sorted(m)[len(m) // 2], min(m), max(m)) for m in meds]
+
+
+def case(name, div, dev):
+    """(method, vars view, crop, halo_x, residual call into out=, bytes of fields per cell)"""
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def rnd(*s):
+        return torch.rand(*s, device=dev, generator=g) + 0.5
+    if name == "ns_rank":
+        ns = R.NavierStokes(0.01, 1 / 512, 1 / 512, device=dev)
+        v = rnd(max(512 // div, 1), 3, 64, 512, 512)
+        return ns.residual_momentum, v, (1, 1, 1), False, lambda out: ns.residual_momentum(v, boundary=True, out=out), 12
+    if name == "c3_xslab":
+        ns = R.NavierStokes(0.01, 1 / 512, 1 / 512, device=dev)
+        full = rnd(max(4096 // div, 1), 3, 64, 34, 512)
+        v = full[:, :, :, 1:-1]
+        return (ns.residual_momentum, v, (1, 0, 1), True,
+                lambda out: ns.residual_momentum(v, boundary=True, out=out, halo_x=True), 12)
+    if name == "c4_mhd":
+        mhd = R.MHD(device=dev)
+        v = rnd(max(1024 // div, 1), 6, 64, 256, 256)
+        return mhd.residual_induction, v, (1, 1, 1), False, lambda out: mhd.residual_induction(v, boundary=True, out=out), 16
+    if name == "c2_wave":
+        w = R.PRE_Wave(0.01, 0.02, device=dev)
+        v = rnd(max(512 // div, 1), 32, 256, 256)
+        return w.residual, v, (1, 1, 1), False, lambda out: w.residual(v, boundary=True, out=out), 4
+    raise KeyError(name)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave")
+    ap.add_argument("--div", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--only", choices=["fused", "three", "residual"], default=None, help="run one route alone (for a profiler)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "screen", "screen_bench.jsonl"))
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for name in args.cases.split(","):
+        method, v, crop, halo_x, residual_into, fbytes = case(name, args.div, dev)
+        n = v.shape[0]
+        shape = (n,) + tuple(v.shape[-3:])
+        mod = torch.rand(shape[1:], device=dev) + 0.5
+        q = torch.linspace(0.5, 50.0, NK, device=dev)
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
+
+        def fused():
+            s = screen.Screen(n, NK, dev)
+            s.add_slab(method, v, q, mod, crop=crop, halo_x=halo_x)
+            return s
+
+        def three():
+            residual_into(out)
+            scores = torch.zeros(n, dtype=torch.float32, device=dev)
+            pipeline.HipOps.max_scores(out, mod, crop, scores)
+            cov = pipeline.CoverageLevels(n, NK, dev, joint=True)
+            cov.add_slab(out[reg], q, modulation=mod[reg[1:]])
+            return scores, cov
+
+        def residual():
+            residual_into(out)
+
+        s = fused()
+        route = screen.last_route()
+        sc3, cov = three()
+        torch.cuda.synchronize()
+        got = s.finish()
+        agree = bool(torch.equal(got.accept(), cov.inside)) and bool(torch.equal(got.score.view(torch.int32), sc3.view(torch.int32)))
+        fns = {"fused": fused, "three": three, "residual": residual}
+        pick = [args.only] if args.only else ["fused", "three", "residual"]
+        res = blocks_of([fns[k] for k in pick], args.reps, args.blocks, args.warmup)
+        cells = 1
+        for d in shape:
+            cells *= d
+        line = {"case": name, "shape": list(v.shape), "nk": NK, "route": route, "bit_identical_to_three_pass": agree,
+                "cells": cells, "field_bytes_per_cell": fbytes}
+        for k, (med, lo, hi) in zip(pick, res):
+            line[k + "_ms"] = round(med, 4)
+            line[k + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
+        if "fused" in pick:
+            line["fused_TBps_of_fields"] = round(cells * fbytes / (line["fused_ms"] * 1e-3) / 1e12, 3)
+        txt = json.dumps(line)
+        print(txt, flush=True)
+        with open(args.out, "a") as f:
+            f.write(txt + "\n")
+        del v, out, mod
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
