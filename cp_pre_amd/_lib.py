@@ -209,6 +209,16 @@ SCREEN_SIGNATURES = {
     "pre_screen_mhd_f32": [c_int, POINTER(PreField)] + [POINTER(c_float)] * 3 + [c_double] + _scr,
 }
 
+# libcp_pre_screen1d.so (include/cp_pre_screen1d.h): the same screen for the 1-D residuals on [B,Nt,Nx] (PreScreen reused)
+SCREEN1D_SO_PATH = os.path.join(_HERE, "libcp_pre_screen1d.so")
+PRE_SCREEN1D_ABI_VERSION = 1
+_scr1 = [POINTER(PreScreen)] + [c_int64] * 3 + [c_int, c_void_p]         # s, B, T, X, flags, stream
+SCREEN1D_SIGNATURES = {
+    "pre_screen1d_abi_version": [],
+    "pre_screen1d_stencil2d_f32": [_fp, _i64p, POINTER(c_float), POINTER(c_int32), c_int] + _scr1,
+    "pre_screen1d_burgers_f32": [_fp, _i64p] + [POINTER(c_float)] * 3 + [c_float] * 4 + _scr1,
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -229,8 +239,9 @@ _LIBS = {
 _LIBS_MORE = {
     "vjp": ("_vjp", "VJP_", "pre_vjp_abi_version", "PRE_VJP_ABI_VERSION", ()),
     "screen": ("_screen", "SCREEN_", "pre_screen_abi_version", "PRE_SCREEN_ABI_VERSION", ()),
+    "screen1d": ("_screen1d", "SCREEN1D_", "pre_screen1d_abi_version", "PRE_SCREEN1D_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -299,6 +310,10 @@ def load_vjp():
 
 def load_screen():
     return _screen or _load("screen")
+
+
+def load_screen1d():
+    return _screen1d or _load("screen1d")
 
 
 def require_gpu():

@@ -18,10 +18,17 @@ in registers and reduces it per sample - a maximum and nk integer counts - so th
 the route a user writes today (residual, ``ncf_metric_joint``, ``CoverageLevels``) become one launch that stores nothing.
 Fused kinds: ``stencil3d`` (a ``ConvOperator`` of ``convops_2d``, ``PRE_Wave``), ``linear2`` (NS continuity, MHD gauss),
 ``ns_momentum``, ``mhd_continuity`` / ``mhd_momentum`` / ``mhd_energy`` / ``mhd_induction``.  Everything else takes that
-three-pass route (residual, ``ncf_metric_joint``, then ``CoverageLevels`` once per sample) and returns the same ``Screened``: the 1-D family (Advection, Burgers: their marched axis is the batch),
+three-pass route (residual, ``ncf_metric_joint``, then ``CoverageLevels`` once per sample) and returns the same ``Screened``:
 JOREK, views without unit stride on their last axis, row widths that are no multiple of 4, inputs on the CPU (staged as
 elsewhere), ``minus=``, operator kernels off the 7-point star or requiring grad, ``fused=False``, float64 levels or
 modulation.  ``last_route()`` says which route the last call took.
+
+The 1-D family on ``[BS,Nt,Nx]`` (a ``ConvOperator`` of ``convops_1d``, ``Advection.residual``, ``Burgers.residual``) has a
+fused route of its own (``libcp_pre_screen1d.so``, ``include/cp_pre_screen1d.h``): the march above would run over the
+batch, so there a workgroup owns one sample's ``[Nt,Nx]`` plane and marches over its rows, in either layout (Nx-fastest, or
+the Nt-fastest ``u.permute(0,1,3,2)[:,0]`` of the active-learning scripts).  Routes ``fused:rows_stencil2d`` and
+``fused:rows_burgers``; the three-pass route is kept for the reasons above, for a contiguous axis that is no multiple of 4
+and for a ``[BS,1,Nt,Nx]`` input (screened as ``vars[:, 0]``).  ``halo_x`` raises for this family.
 
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 """
@@ -95,10 +102,12 @@ _MHD_CHAN = {0: (0, 1, 2), 1: tuple(range(6)), 2: tuple(range(6)), 3: (1, 2, 4, 
 
 class _Spec:
     """One residual method, resolved as ``losses._Spec`` resolves it: ``kind`` (None: no fused screen), ``chan`` - the
-    channels of a stacked ``[BS,F,...]`` input the residual reads (None: the input is the field itself)."""
+    channels of a stacked ``[BS,F,...]`` input the residual reads (None: the input is the field itself), ``rows_kind`` -
+    the fused screen of the 1-D family ('stencil2d', 'burgers'; None: none), which ``kind`` and ``why`` do not speak of."""
 
     def __init__(self, method):
         self.method, self.kind, self.why, self.chan, self.nd, self.ops = method, None, None, None, 3, ()
+        self.rows_kind = None
         self.is_op = isinstance(method, (ConvOperator1D, ConvOperator2D))
         obj = method if self.is_op else getattr(method, "__self__", None)
         name = getattr(method, "__name__", "")
@@ -109,6 +118,7 @@ class _Spec:
                 self.why = "spectral operator"
             elif self.nd == 2:
                 self.why = "1-D family: the marched axis is the batch"
+                self.rows_kind, self.ops = "stencil2d", (method,)
             else:
                 self.kind, self.ops = "stencil3d", (method,)
         elif obj is None or not callable(method):
@@ -127,6 +137,10 @@ class _Spec:
             self.kind, self.ops = "stencil3d", (obj.D,)
         elif isinstance(obj, (R.Burgers, R.Advection)) and name == "residual":
             self.nd, self.why = 2, "1-D family: the marched axis is the batch"
+            if isinstance(obj, R.Burgers):
+                self.rows_kind, self.ops = "burgers", (obj.D_t, obj.D_x, obj.D_xx)
+            else:
+                self.rows_kind, self.ops = "stencil2d", (obj.D,)
         elif isinstance(obj, R.JOREK) and name in ("residual_continuity", "residual_temperature"):
             self.why, self.chan = "no fused screen for JOREK", ()
         else:
@@ -145,6 +159,8 @@ class _Spec:
             return (x.shape[0],) + tuple(x.shape[2:])
         if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5:
             return (x.shape[0],) + tuple(x.shape[2:])
+        if self.rows_kind is not None and x.dim() == 4 and x.shape[1] == 1:
+            return (x.shape[0],) + tuple(x.shape[2:])             # ([BS,1,Nt,Nx]: screened as x[:, 0], three-pass)
         if x.dim() != self.nd + 1:
             raise ValueError(f"expected a {self.nd + 1}-D field, got {tuple(x.shape)}")
         return tuple(x.shape)
@@ -158,6 +174,8 @@ class _Spec:
         """The uncropped residual by the existing passes (what the fallback's first launch is)."""
         if halo_x and not self.reads_halo():
             raise RuntimeError("halo_x: only the fused screen reads the halo rows for this method, and it declined")
+        if self.rows_kind is not None and x.dim() == 4:
+            x, minus = x[:, 0], (minus[:, 0] if minus is not None else None)
         with torch.no_grad():
             kw = {} if minus is None else {"minus": minus}
             if halo_x:
@@ -206,6 +224,50 @@ class _Spec:
         if any(k.shape != (3, 3, 3) or not _is_star(k) for k in ks):
             return "operator kernel off the 7-point star", ()
         return None, tuple(_lib.farr(k.reshape(-1)) for k in ks)
+
+    def prepare_rows(self, x, minus, qhats, modulation):
+        """``prepare`` for the fused screen of the 1-D family (``rows_kind``): (why, kernels)."""
+        if minus is not None:
+            return "minus=", ()
+        if not x.is_cuda:
+            return "input on the CPU", ()
+        if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
+            return "float64 levels or modulation", ()
+        if x.dim() == 4:
+            return "[BS,1,Nt,Nx] input", ()
+        if x.stride(2) != 1 and x.stride(1) != 1:
+            return "no unit-stride axis", ()
+        if x.shape[2 if x.stride(2) == 1 else 1] % 4 != 0:
+            return "contiguous-axis length not a multiple of 4", ()
+        if getattr(self.obj, "fused", True) is False:
+            return "fused=False", ()
+        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
+            return "operator kernel requires grad", ()
+        ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
+        if self.rows_kind == "stencil2d":
+            if ks[0].ndim != 2 or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
+                return "operator kernel off the 5-point star", ()
+            w, off = _dispatch.taps_of(ks[0])
+            if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
+                return "operator kernel off the 5-point star", ()
+            return None, (w, off)
+        if any(k.shape != (3, 3) or k[0, 0] or k[0, 2] or k[2, 0] or k[2, 2] for k in ks):
+            return "operator kernel off the 5-point star", ()
+        return None, tuple(_lib.farr(k.reshape(-1)) for k in ks)
+
+    def launch_rows(self, kernels, x, st, flags):
+        """The fused launch of the 1-D family on a [BS,Nt,Nx] device view; returns the library's code."""
+        lib = _lib.load_screen1d()
+        head = (_lib.ptr(x), _lib.iarr64(x.stride()))
+        tail = (ctypes.byref(st), *x.shape, flags, _lib.stream())
+        if self.rows_kind == "stencil2d":
+            w, off = kernels
+            wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
+            ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
+            return lib.pre_screen1d_stencil2d_f32(*head, wv, ov, len(w), *tail)
+        o = self.obj
+        return lib.pre_screen1d_burgers_f32(*head, *kernels, float(o.dx), float(o.dt), float(o.nu), float(2 * o.dt / o.dx),
+                                            *tail)               # (2 dt / dx in fp32, as Burgers.residual)
 
     def launch(self, kernels, x, st, flags):
         """The fused launch on device views; returns the library's code."""
@@ -313,24 +375,34 @@ class Screen:
         if halo_x and why is not None and not spec.reads_halo():
             # (before any device work: this slab would be evaluated against zero padding and counted as if it were right)
             raise RuntimeError(f"halo_x: the fused screen cannot run ({why}) and no other pass of this method reads the halo rows")
+        rows = spec.rows_kind is not None                     # (the 1-D family: halo_x has raised above)
+        if rows:
+            why, kernels = spec.prepare_rows(vars_slab, minus, qhats, modulation_slab)
         if why is None:
             acc = self._buffers(vars_slab.device)
             mod = modulation_slab
-            if mod is not None and mod.stride(-1) != 1:
+            if rows:
+                nt_fast = vars_slab.stride(2) != 1            # the modulation's unit-stride axis must be the field's
+                if mod is not None and mod.stride(0 if nt_fast else 1) != 1:
+                    mod = mod.t().contiguous().t() if nt_fast else mod.contiguous()
+            elif mod is not None and mod.stride(-1) != 1:
                 mod = mod.contiguous()
             q = qhats.contiguous()
             st = _lib.PreScreen(_lib.ptr(q), self.nk, _lib.ptr(mod), mod.stride(0) if mod is not None else 0,
-                                mod.stride(1) if mod is not None else 0, crop[0], crop[1], crop[2],
+                                mod.stride(1) if mod is not None else 0, crop[0], crop[1], 0 if rows else crop[2],
                                 ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
             with torch.no_grad(), torch.cuda.device(vars_slab.device):
-                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0)
+                if rows:
+                    rc = spec.launch_rows(kernels, vars_slab, st, 0)
+                else:
+                    rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0)
             if rc == _lib.PRE_E_UNSUPPORTED:
                 why = "declined by the library"
                 if halo_x and not spec.reads_halo():
                     raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
             else:
-                _lib.check(rc, "pre_screen_" + spec.kind.split("_")[0] + "_f32")
-                _last_route = "fused:" + spec.kind
+                _lib.check(rc, "pre_screen1d_" + spec.rows_kind + "_f32" if rows else "pre_screen_" + spec.kind.split("_")[0] + "_f32")
+                _last_route = "fused:" + ("rows_" + spec.rows_kind if rows else spec.kind)
                 self.cells += cells
                 return
         _last_route = "fallback:" + why

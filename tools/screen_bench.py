@@ -12,8 +12,13 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
     c3_xslab   NS momentum on one C3 x-slab [4096,3,64,32(+2 halo rows),512], halo_x
     c4_mhd     MHD induction on the C4 shard [1024,6,64,256,256]
     c2_wave    the wave residual on [512,32,256,256]
+    c5_burgers_nx / c5_burgers_nt
+               Burgers on the C5 shard [8192,200,512], Nx-fastest and in the Nt-fastest layout of the active-learning
+               scripts (``libcp_pre_screen1d.so``: a workgroup per sample plane).  The 1-D residual pass takes no ``out=``:
+               (B) and (R) allocate their residual from torch's caching allocator on every call, and (B) scores the
+               cropped copy as the package's fallback does (``ncf_metric_joint`` on ``res[1:-1, 1:-1].contiguous()``)
 
-    python tools/screen_bench.py [--cases ns_rank,c2_wave] [--div 8] [--reps 3] [--blocks 5]
+    python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
 """
@@ -26,6 +31,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from cp_pre_amd import inductive_cp as icp  # noqa: E402
 from cp_pre_amd import pipeline, screen  # noqa: E402
 from cp_pre_amd import residuals as R  # noqa: E402
 
@@ -81,12 +87,18 @@ def case(name, div, dev):
         w = R.PRE_Wave(0.01, 0.02, device=dev)
         v = rnd(max(512 // div, 1), 32, 256, 256)
         return w.residual, v, (1, 1, 1), False, lambda out: w.residual(v, boundary=True, out=out), 4
+    if name in ("c5_burgers_nx", "c5_burgers_nt"):
+        bg = R.Burgers(1 / 512, 0.005, 0.002, device=dev)
+        v = rnd(max(8192 // div, 1), 200, 512)
+        if name.endswith("nt"):
+            v = v.transpose(1, 2).contiguous().transpose(1, 2)
+        return bg.residual, v, (1, 1), False, lambda out: bg.residual(v, boundary=True), 4
     raise KeyError(name)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave")
+    ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt")
     ap.add_argument("--div", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=5)
@@ -99,10 +111,13 @@ def main():
     for name in args.cases.split(","):
         method, v, crop, halo_x, residual_into, fbytes = case(name, args.div, dev)
         n = v.shape[0]
-        shape = (n,) + tuple(v.shape[-3:])
+        one_d = len(crop) == 2
+        shape = (n,) + tuple(v.shape[-len(crop):])
         mod = torch.rand(shape[1:], device=dev) + 0.5
+        if one_d and v.stride(-1) != 1:
+            mod = mod.t().contiguous().t()
         q = torch.linspace(0.5, 50.0, NK, device=dev)
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        out = None if one_d else torch.empty(shape, dtype=torch.float32, device=dev)
         reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
 
         def fused():
@@ -111,6 +126,12 @@ def main():
             return s
 
         def three():
+            if one_d:
+                res = residual_into(None)
+                scores = icp.ncf_metric_joint(res[reg].contiguous(), None, mod[reg[1:]].contiguous())
+                cov = pipeline.CoverageLevels(n, NK, dev, joint=True)
+                cov.add_slab(res[reg], q, modulation=mod[reg[1:]])
+                return scores, cov
             residual_into(out)
             scores = torch.zeros(n, dtype=torch.float32, device=dev)
             pipeline.HipOps.max_scores(out, mod, crop, scores)
