@@ -219,6 +219,26 @@ SCREEN1D_SIGNATURES = {
     "pre_screen1d_burgers_f32": [_fp, _i64p] + [POINTER(c_float)] * 3 + [c_float] * 4 + _scr1,
 }
 
+# libcp_pre_screenflat.so (include/cp_pre_screenflat.h): the same screen for Nt-fastest views of the 2-D residuals
+SCREENFLAT_SO_PATH = os.path.join(_HERE, "libcp_pre_screenflat.so")
+PRE_SCREENFLAT_ABI_VERSION = 1
+
+
+class PreScreenFlat(ctypes.Structure):
+    """``pre_screenflat_t``: ``pre_screen_t`` with three modulation strides (the unit-stride axis is T)."""
+    _fields_ = [("q", c_void_p), ("nk", c_int), ("modulation", c_void_p), ("mT", c_int64), ("mX", c_int64), ("mY", c_int64),
+                ("ct", c_int), ("cx", c_int), ("cy", c_int), ("score", c_void_p), ("count", c_void_p), ("count_ld", c_int64)]
+
+
+_scrf = [POINTER(PreScreenFlat)] + [c_int64] * 4 + [c_int, c_void_p]     # s, B, T, X, Y, flags, stream
+SCREENFLAT_SIGNATURES = {
+    "pre_screenflat_abi_version": [],
+    "pre_screenflat_stencil3d_f32": [_fld, POINTER(c_float), POINTER(c_int32), c_int] + _scrf,
+    "pre_screenflat_linear2_f32": [_fld, _fld, POINTER(c_float), POINTER(c_float), c_float] + _scrf,
+    "pre_screenflat_ns_momentum_f32": [_fld, _fld, _fld] + [POINTER(c_float)] * 4 + [c_float] * 4 + _scrf,
+    "pre_screenflat_mhd_f32": [c_int, POINTER(PreField)] + [POINTER(c_float)] * 3 + [c_double] + _scrf,
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -240,8 +260,9 @@ _LIBS_MORE = {
     "vjp": ("_vjp", "VJP_", "pre_vjp_abi_version", "PRE_VJP_ABI_VERSION", ()),
     "screen": ("_screen", "SCREEN_", "pre_screen_abi_version", "PRE_SCREEN_ABI_VERSION", ()),
     "screen1d": ("_screen1d", "SCREEN1D_", "pre_screen1d_abi_version", "PRE_SCREEN1D_ABI_VERSION", ()),
+    "screenflat": ("_screenflat", "SCREENFLAT_", "pre_screenflat_abi_version", "PRE_SCREENFLAT_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -314,6 +335,10 @@ def load_screen():
 
 def load_screen1d():
     return _screen1d or _load("screen1d")
+
+
+def load_screenflat():
+    return _screenflat or _load("screenflat")
 
 
 def require_gpu():

@@ -30,6 +30,12 @@ the Nt-fastest ``u.permute(0,1,3,2)[:,0]`` of the active-learning scripts).  Rou
 ``fused:rows_burgers``; the three-pass route is kept for the reasons above, for a contiguous axis that is no multiple of 4
 and for a ``[BS,1,Nt,Nx]`` input (screened as ``vars[:, 0]``).  ``halo_x`` raises for this family.
 
+Nt-fastest views of the 2-D residuals - ``pred.permute(0,1,4,2,3)`` of the surrogate's native ``[BS,F,Nx,Ny,Nt]``, what
+``Joint/NS_Residuals_CP.py:282-305`` and ``Joint/MHD_Residuals_CP.py:326-346`` pass - have a fused route as well
+(``libcp_pre_screenflat.so``, ``include/cp_pre_screenflat.h``): the merged-row march of the residual pass's flat form with
+the same end of a plane.  Routes ``fused:flat_<kind>``; taken when the rows are dense (``stride(Ny) == Nt``), ``Ny*Nt`` is a
+multiple of 4 and ``Nt < 96``, else the three-pass route says why.  ``halo_x`` on such a view behaves as before.
+
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 """
 from __future__ import annotations
@@ -213,6 +219,10 @@ class _Spec:
             return "multi-channel wave input", ()
         if self.kind.startswith("mhd_") and x.shape[1] < 6:
             return "fewer than six MHD channels", ()              # (pre_screen_mhd_f32 takes the six views)
+        return self._star_kernels()
+
+    def _star_kernels(self):
+        """(why, kernels) of the 2-D family: one download of the operator kernels, all weight on the 7-point star."""
         ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
         if self.kind == "stencil3d":
             if ks[0].ndim != 3 or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
@@ -224,6 +234,55 @@ class _Spec:
         if any(k.shape != (3, 3, 3) or not _is_star(k) for k in ks):
             return "operator kernel off the 7-point star", ()
         return None, tuple(_lib.farr(k.reshape(-1)) for k in ks)
+
+    def nt_fastest(self, x):
+        """Is ``x`` an Nt-fastest view of a 2-D residual's input (unit stride on Nt, not on Ny)?"""
+        return self.kind is not None and x.dim() >= 4 and x.stride(-3) == 1 and x.stride(-1) != 1
+
+    def prepare_flat(self, x, minus, qhats, modulation):
+        """``prepare`` for the fused screen of Nt-fastest views (``nt_fastest(x)``): (why, kernels)."""
+        if minus is not None:
+            return "minus=", ()
+        if not x.is_cuda:
+            return "input on the CPU", ()
+        if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
+            return "float64 levels or modulation", ()
+        T, Y = x.shape[-3], x.shape[-1]
+        if T >= 96:
+            return "Nt >= 96", ()                                   # (FLAT_MAX_Y: the residual pass leaves its flat form there too)
+        if (Y * T) % 4 != 0:
+            return "merged row Ny*Nt not a multiple of 4", ()
+        if Y <= 1 or x.stride(-1) != T:
+            return "rows not dense", ()                               # (a t-slab of an Nt-fastest tensor)
+        if getattr(self.obj, "fused", True) is False:
+            return "fused=False", ()
+        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
+            return "operator kernel requires grad", ()
+        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
+            return "multi-channel wave input", ()
+        if self.kind.startswith("mhd_") and x.shape[1] < 6:
+            return "fewer than six MHD channels", ()
+        return self._star_kernels()
+
+    def launch_flat(self, kernels, x, st, flags):
+        """The fused launch on Nt-fastest device views; returns the library's code."""
+        lib = _lib.load_screenflat()
+        fs = self.fields(x)
+        tail = (ctypes.byref(st), *fs[0].shape, flags, _lib.stream())
+        if self.kind == "stencil3d":
+            w, off = kernels
+            wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
+            ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
+            return lib.pre_screenflat_stencil3d_f32(ctypes.byref(_lib.field(fs[0])), wv, ov, len(w), *tail)
+        if self.kind == "linear2":
+            return lib.pre_screenflat_linear2_f32(ctypes.byref(_lib.field(fs[0])), ctypes.byref(_lib.field(fs[1])), *kernels,
+                                                  float(self.ratio), *tail)
+        if self.kind == "ns_momentum":
+            o = self.obj
+            return lib.pre_screenflat_ns_momentum_f32(*[ctypes.byref(_lib.field(f)) for f in fs], *kernels, float(o.dt),
+                                                      float(o.dx), float(o.dy), float(o.nu), *tail)
+        six = R._arr([x[:, i] for i in range(6)])
+        return lib.pre_screenflat_mhd_f32(self.eq, six, *kernels, float(self.obj.gamma), *tail)
 
     def prepare_rows(self, x, minus, qhats, modulation):
         """``prepare`` for the fused screen of the 1-D family (``rows_kind``): (why, kernels)."""
@@ -378,6 +437,10 @@ class Screen:
         rows = spec.rows_kind is not None                     # (the 1-D family: halo_x has raised above)
         if rows:
             why, kernels = spec.prepare_rows(vars_slab, minus, qhats, modulation_slab)
+        # Nt-fastest views of the 2-D residuals: the flat route (halo_x keeps the behaviour it had: the flat form pads x)
+        flat = not rows and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
+        if flat:
+            why, kernels = spec.prepare_flat(vars_slab, minus, qhats, modulation_slab)
         if why is None:
             acc = self._buffers(vars_slab.device)
             mod = modulation_slab
@@ -385,15 +448,25 @@ class Screen:
                 nt_fast = vars_slab.stride(2) != 1            # the modulation's unit-stride axis must be the field's
                 if mod is not None and mod.stride(0 if nt_fast else 1) != 1:
                     mod = mod.t().contiguous().t() if nt_fast else mod.contiguous()
+            elif flat:
+                if mod is not None and (mod.stride(0) != 1 or mod.stride(2) != mod.shape[0]):
+                    mod = mod.permute(1, 2, 0).contiguous().permute(2, 0, 1)       # (one sample-sized copy, memory [X,Y,T])
             elif mod is not None and mod.stride(-1) != 1:
                 mod = mod.contiguous()
             q = qhats.contiguous()
-            st = _lib.PreScreen(_lib.ptr(q), self.nk, _lib.ptr(mod), mod.stride(0) if mod is not None else 0,
-                                mod.stride(1) if mod is not None else 0, crop[0], crop[1], 0 if rows else crop[2],
-                                ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
+            if flat:
+                st = _lib.PreScreenFlat(_lib.ptr(q), self.nk, _lib.ptr(mod), *(mod.stride() if mod is not None else (0, 0, 0)),
+                                        crop[0], crop[1], crop[2], ctypes.c_void_p(acc[0].data_ptr()),
+                                        ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
+            else:
+                st = _lib.PreScreen(_lib.ptr(q), self.nk, _lib.ptr(mod), mod.stride(0) if mod is not None else 0,
+                                    mod.stride(1) if mod is not None else 0, crop[0], crop[1], 0 if rows else crop[2],
+                                    ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
             with torch.no_grad(), torch.cuda.device(vars_slab.device):
                 if rows:
                     rc = spec.launch_rows(kernels, vars_slab, st, 0)
+                elif flat:
+                    rc = spec.launch_flat(kernels, vars_slab, st, 0)
                 else:
                     rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0)
             if rc == _lib.PRE_E_UNSUPPORTED:
@@ -401,8 +474,9 @@ class Screen:
                 if halo_x and not spec.reads_halo():
                     raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
             else:
-                _lib.check(rc, "pre_screen1d_" + spec.rows_kind + "_f32" if rows else "pre_screen_" + spec.kind.split("_")[0] + "_f32")
-                _last_route = "fused:" + ("rows_" + spec.rows_kind if rows else spec.kind)
+                _lib.check(rc, "pre_screen1d_" + spec.rows_kind + "_f32" if rows else
+                           ("pre_screenflat_" if flat else "pre_screen_") + spec.kind.split("_")[0] + "_f32")
+                _last_route = "fused:" + ("rows_" + spec.rows_kind if rows else "flat_" + spec.kind if flat else spec.kind)
                 self.cells += cells
                 return
         _last_route = "fallback:" + why

@@ -17,8 +17,13 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                scripts (``libcp_pre_screen1d.so``: a workgroup per sample plane).  The 1-D residual pass takes no ``out=``:
                (B) and (R) allocate their residual from torch's caching allocator on every call, and (B) scores the
                cropped copy as the package's fallback does (``ncf_metric_joint`` on ``res[1:-1, 1:-1].contiguous()``)
+    c3_rank8_ntfast / c4_induction_ntfast
+               NS momentum on memory [512,3,512,512,64] and MHD induction on memory [1024,6,256,256,64], both seen
+               through ``permute(0,1,4,2,3)`` as the reference's 2-D scripts pass them (``libcp_pre_screenflat.so``: the
+               merged-row march).  (B) scores with ``ncf_metric_joint(..., crop=1)`` as the package's fallback does in
+               this layout; (R) is the flat residual launch into a buffer laid out like the fields
 
-    python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt] [--div 8] [--reps 3] [--blocks 5]
+    python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
 """
@@ -93,12 +98,20 @@ def case(name, div, dev):
         if name.endswith("nt"):
             v = v.transpose(1, 2).contiguous().transpose(1, 2)
         return bg.residual, v, (1, 1), False, lambda out: bg.residual(v, boundary=True), 4
+    if name == "c3_rank8_ntfast":
+        ns = R.NavierStokes(0.01, 1 / 512, 1 / 512, device=dev)
+        v = rnd(max(512 // div, 1), 3, 512, 512, 64).permute(0, 1, 4, 2, 3)
+        return ns.residual_momentum, v, (1, 1, 1), False, lambda out: ns.residual_momentum(v, boundary=True, out=out), 12
+    if name == "c4_induction_ntfast":
+        mhd = R.MHD(device=dev)
+        v = rnd(max(1024 // div, 1), 6, 256, 256, 64).permute(0, 1, 4, 2, 3)
+        return mhd.residual_induction, v, (1, 1, 1), False, lambda out: mhd.residual_induction(v, boundary=True, out=out), 16
     raise KeyError(name)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt")
+    ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
     ap.add_argument("--div", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=5)
@@ -112,12 +125,17 @@ def main():
         method, v, crop, halo_x, residual_into, fbytes = case(name, args.div, dev)
         n = v.shape[0]
         one_d = len(crop) == 2
+        nt_fast = not one_d and v.stride(-1) != 1
         shape = (n,) + tuple(v.shape[-len(crop):])
         mod = torch.rand(shape[1:], device=dev) + 0.5
         if one_d and v.stride(-1) != 1:
             mod = mod.t().contiguous().t()
         q = torch.linspace(0.5, 50.0, NK, device=dev)
+        if nt_fast:
+            mod = mod.permute(1, 2, 0).contiguous().permute(2, 0, 1)
         out = None if one_d else torch.empty(shape, dtype=torch.float32, device=dev)
+        if nt_fast:
+            out = torch.empty((n,) + shape[2:] + shape[1:2], dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
         reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
 
         def fused():
@@ -133,8 +151,11 @@ def main():
                 cov.add_slab(res[reg], q, modulation=mod[reg[1:]])
                 return scores, cov
             residual_into(out)
-            scores = torch.zeros(n, dtype=torch.float32, device=dev)
-            pipeline.HipOps.max_scores(out, mod, crop, scores)
+            if nt_fast:
+                scores = icp.ncf_metric_joint(out, None, mod, crop=1)
+            else:
+                scores = torch.zeros(n, dtype=torch.float32, device=dev)
+                pipeline.HipOps.max_scores(out, mod, crop, scores)
             cov = pipeline.CoverageLevels(n, NK, dev, joint=True)
             cov.add_slab(out[reg], q, modulation=mod[reg[1:]])
             return scores, cov
