@@ -239,6 +239,16 @@ SCREENFLAT_SIGNATURES = {
     "pre_screenflat_mhd_f32": [c_int, POINTER(PreField)] + [POINTER(c_float)] * 3 + [c_double] + _scrf,
 }
 
+# libcp_pre_vjpflat.so (include/cp_pre_vjpflat.h): the vector-Jacobian products of libcp_pre_vjp.so for Nt-fastest views
+VJPFLAT_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflat.so")
+PRE_VJPFLAT_ABI_VERSION = 1
+VJPFLAT_SIGNATURES = {
+    "pre_vjpflat_abi_version": [],
+    "pre_vjpflat_stencil3d_f32": VJP_SIGNATURES["pre_vjp_stencil3d_f32"],
+    "pre_vjpflat_linear2_f32": VJP_SIGNATURES["pre_vjp_linear2_f32"],
+    "pre_vjpflat_ns_momentum_f32": VJP_SIGNATURES["pre_vjp_ns_momentum_f32"],
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -261,8 +271,9 @@ _LIBS_MORE = {
     "screen": ("_screen", "SCREEN_", "pre_screen_abi_version", "PRE_SCREEN_ABI_VERSION", ()),
     "screen1d": ("_screen1d", "SCREEN1D_", "pre_screen1d_abi_version", "PRE_SCREEN1D_ABI_VERSION", ()),
     "screenflat": ("_screenflat", "SCREENFLAT_", "pre_screenflat_abi_version", "PRE_SCREENFLAT_ABI_VERSION", ()),
+    "vjpflat": ("_vjpflat", "VJPFLAT_", "pre_vjpflat_abi_version", "PRE_VJPFLAT_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -339,6 +350,10 @@ def load_screen1d():
 
 def load_screenflat():
     return _screenflat or _load("screenflat")
+
+
+def load_vjpflat():
+    return _vjpflat or _load("vjpflat")
 
 
 def require_gpu():

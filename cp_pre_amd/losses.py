@@ -27,6 +27,15 @@ Fused routes: a single linear operator (a ``ConvOperator`` of ``convops_2d`` / `
 require grad or have weight off the 7-point star, inputs on the CPU or without unit stride on their last axis,
 ``fused=False``, a ``yy`` that requires grad - falls back to what ran before: ``method(...).pow(2).mean()`` through
 autograd.  ``last_route()`` says which route the last call took.
+
+``flat=True`` (off by default: nothing above changes) offers an input WITHOUT unit stride on its last axis to
+``libcp_pre_vjpflat.so`` (``include/cp_pre_vjpflat.h``) when its unit-stride axis is the logical Nt axis - the view the
+reference's scripts pass, ``field[:, 0, 1:-1, 1:-1, 1:-1].permute(0, 3, 1, 2)``.  The forward pass is the one above (it
+already evaluates such views in their memory order); the sum of squares reads that residual where it lies, and ONE launch
+of the merged-row VJP writes the gradient, dense in the input's memory order.  Routes ``fused:flat_stencil3d``,
+``fused:flat_linear2``, ``fused:flat_ns_momentum``; whatever the library or the host checks decline (Nt >= 96, a merged
+row Ny*Nt that is no multiple of 4, u / v whose rows are not dense, the 1-D family, everything that falls back above)
+takes the fallback with its reason.
 """
 from __future__ import annotations
 
@@ -44,8 +53,8 @@ _last_route = None
 
 
 def last_route():
-    """'fused:<kind>' (kind: stencil3d, stencil2d, linear2, burgers, ns_momentum) or 'fallback:<why>' of the last
-    ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
+    """'fused:<kind>' (kind: stencil3d, stencil2d, linear2, burgers, ns_momentum; with ``flat=True`` also flat_stencil3d,
+    flat_linear2, flat_ns_momentum) or 'fallback:<why>' of the last ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
     return _last_route
 
 
@@ -138,29 +147,74 @@ class _Spec:
             why = "empty input"
         elif x.stride(-1) != 1 or (minus is not None and minus.stride(-1) != 1):
             why = "no unit stride on the last axis"
-        elif getattr(self.obj, "fused", True) is False:
-            why = "fused=False"
-        elif minus is not None and minus.requires_grad and torch.is_grad_enabled():
-            why = "yy requires grad"
-        elif _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
-            why = "operator kernel requires grad"
-        elif isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
-            why = "multi-channel wave input"
         else:
-            ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
-            if self.kind.startswith("stencil"):
-                if ks[0].ndim != self.nd or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
-                    why = "operator kernel off the 7-point star"
-                else:
-                    w, off = _dispatch.taps_of(ks[0])
-                    if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
-                        why = "operator kernel off the 7-point star"
-                    kernels = (w, off)
-            else:
-                if any(k.shape != (3,) * self.nd or not _is_star(k) for k in ks):
-                    why = "operator kernel off the 7-point star"
-                kernels = tuple(_lib.farr(k.reshape(-1)) for k in ks)
+            why = self._declined(x, minus)
+            if why is None:
+                why, kernels = self._host_kernels()
         return why, kernels
+
+    def _declined(self, x, minus):
+        """What keeps a fused VJP from running whatever the layout (no download), or None."""
+        if getattr(self.obj, "fused", True) is False:
+            return "fused=False"
+        if minus is not None and minus.requires_grad and torch.is_grad_enabled():
+            return "yy requires grad"
+        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
+            return "operator kernel requires grad"
+        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
+            return "multi-channel wave input"
+        return None
+
+    def _host_kernels(self):
+        """(why, kernels): one download of the operator kernels; ``why`` if they have weight off the 7-point star."""
+        why, kernels = None, ()
+        ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
+        if self.kind.startswith("stencil"):
+            if ks[0].ndim != self.nd or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
+                why = "operator kernel off the 7-point star"
+            else:
+                w, off = _dispatch.taps_of(ks[0])
+                if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
+                    why = "operator kernel off the 7-point star"
+                kernels = (w, off)
+        else:
+            if any(k.shape != (3,) * self.nd or not _is_star(k) for k in ks):
+                why = "operator kernel off the 7-point star"
+            kernels = tuple(_lib.farr(k.reshape(-1)) for k in ks)
+        return why, kernels
+
+    # -------- flat=True: an input without unit stride on its last axis (host checks + one download)
+    def wants_flat(self, x):
+        """Is ``x`` an input ``flat=True`` offers to the merged-row VJP at all?  (Everything else: ``prepare``.)"""
+        return x.is_cuda and x.numel() > 0 and x.dim() > 0 and x.stride(-1) != 1
+
+    def fields(self, x):
+        """The [BS,Nt,Nx,Ny] views of ``x`` the residual reads."""
+        if self.chan is not None:
+            return [x[:, i] for i in self.chan]
+        return [x[:, 0] if x.dim() == 5 else x]
+
+    def prepare_flat(self, x, minus=None):
+        """``prepare`` for the merged-row VJP of ``libcp_pre_vjpflat.so``: (why, kernels).  The layout conditions are the
+        library's own (include/cp_pre_vjpflat.h), stated here so that the reason has a name."""
+        if self.kind is None:
+            return self.why, ()
+        if self.nd != 3:
+            return "no flat VJP for the 1-D family", ()
+        why = self._declined(x, minus)
+        if why is not None:
+            return why, ()
+        f = self.fields(x)
+        Nt, Ny = f[0].shape[1], f[0].shape[3]
+        if f[0].stride(1) != 1:
+            return "the unit-stride axis is not Nt", ()
+        if Nt >= FLAT_MAX_NT:
+            return "Nt >= 96", ()
+        if (Ny * Nt) % 4 != 0:
+            return "merged row Ny*Nt not a multiple of 4", ()
+        if self.kind == "ns_momentum" and any(v.stride(1) != 1 or v.stride(3) != Nt or v.stride(2) != Ny * Nt for v in f[:2]):
+            return "rows of u, v not dense", ()
+        return self._host_kernels()
 
     # -------- the VJP launch: gfull [BS,*field] (unit stride last) -> gradient of x's shape
     def vjp(self, kernels, gfull, x, crop, host_scale, dev_scale):
@@ -208,6 +262,48 @@ class _Spec:
         return grad
 
 
+    # -------- the merged-row VJP launch: gfull [BS,Nt,Nx,Ny], dense in memory order [BS,Nx,Ny,Nt] -> gradient of x's shape
+    def vjp_flat(self, kernels, gfull, x, crop, host_scale, dev_scale):
+        """``kernels``: what ``prepare_flat`` returned.  The gradient is dense in ``x``'s memory order.  None if the
+        library declines."""
+        lib = _lib.load_vjpflat()
+        grad = _lib.empty_like_layout(x)
+        flags = _lib.PRE_VJP_CROP if crop else 0
+        scale = (float(host_scale), _lib.ptr(dev_scale))
+        name = "pre_vjpflat_" + self.kind + "_f32"
+        gf = ctypes.byref(_lib.field(gfull))
+        with torch.cuda.device(x.device):
+            st = _lib.stream()
+            if self.kind == "ns_momentum":
+                obj = self.obj
+                rc = lib.pre_vjpflat_ns_momentum_f32(
+                    gf, R._arr([x[:, 0], x[:, 1]]), R._arr([grad[:, 0], grad[:, 1], grad[:, 2]]), *kernels,
+                    float(obj.dt), float(obj.dx), float(obj.dy), float(obj.nu), *scale, *gfull.shape, flags, st)
+            elif self.kind == "linear2":
+                rc = lib.pre_vjpflat_linear2_f32(gf, R._arr([grad[:, 0], grad[:, 1]]), *kernels,
+                                                 float(self.obj.dx / self.obj.dy), *scale, *gfull.shape, flags, st)
+            else:
+                w, off = kernels
+                wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
+                ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
+                out = grad[:, 0] if grad.dim() == 5 else grad
+                rc = lib.pre_vjpflat_stencil3d_f32(gf, ctypes.byref(_lib.field(out)), wv, ov, len(w), *scale, *gfull.shape, flags, st)
+        if rc == _lib.PRE_E_UNSUPPORTED:
+            return None
+        _lib.check(rc, name)
+        if self.chan is not None and x.shape[1] > len(self.chan):
+            grad[:, len(self.chan):].zero_()
+        return grad
+
+
+FLAT_MAX_NT = 96             # star_march.hip's FLAT_MAX_Y: the merged-row form's own bound on the contiguous extent
+
+
+def _nt_fastest_dense(r):
+    """Is the [BS,Nt,Nx,Ny] tensor ``r`` dense in memory order [BS,Nx,Ny,Nt]?"""
+    return r.dim() == 4 and r.permute(0, 2, 3, 1).is_contiguous()
+
+
 def _is_star(k):
     idx = np.argwhere(k != 0) - 1
     return not len(idx) or not (np.count_nonzero(idx, axis=1) > 1).any()
@@ -232,12 +328,16 @@ def _check_like(t, like, what, shape=None):
 
 
 # ------------------------------------------------------------------------------------------- the loss
-def _mean_sq(r, boundary):
-    """(mean of ``m * r^2`` as a 0-d fp32 device tensor, N) by ``pre_vjp_sumsq_f32``; r: the uncropped residual."""
+def _mean_sq(r, boundary, where_it_lies=False):
+    """(mean of ``m * r^2`` as a 0-d fp32 device tensor, N) by ``pre_vjp_sumsq_f32``; r: the uncropped residual.
+    ``where_it_lies``: an Nt-fastest r is summed in its memory order [BS,Nx,Ny,Nt] instead of being copied (the crop is
+    symmetric on every axis: the masked set is the same)."""
     dims = r.shape[1:]
     n = r.shape[0]
     for d in dims:
         n *= d if boundary else max(d - 2, 0)
+    if where_it_lies and _nt_fastest_dense(r):
+        r = r.permute(0, 2, 3, 1)
     if r.stride(-1) != 1:
         r = r.contiguous()
     r4 = r if r.dim() == 4 else r.unsqueeze(0)
@@ -283,13 +383,49 @@ class _LossFn(torch.autograd.Function):
         return grad, None, None, None, None
 
 
-def _loss(residual_method, pred, yy, boundary):
+class _FlatLossFn(torch.autograd.Function):
+    """``_LossFn`` for ``flat=True``: ``r`` arrives evaluated (the caller has checked where it lies), the backward pass is
+    the merged-row launch."""
+
+    @staticmethod
+    def forward(ctx, pred, spec, kernels, yy, boundary, r):
+        loss, n = _mean_sq(r, boundary, where_it_lies=True)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(r, pred)
+            ctx.spec, ctx.kernels, ctx.yy, ctx.boundary, ctx.n = spec, kernels, yy, boundary, n
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        r, pred = ctx.saved_tensors
+        spec, n = ctx.spec, ctx.n
+        up = gout.detach().to(device=pred.device, dtype=torch.float32).reshape(1)
+        grad = spec.vjp_flat(ctx.kernels, r, pred, not ctx.boundary, 2.0 / n if n else 0.0, up)
+        if grad is None:                                 # (not expected after prepare_flat(): the library declined)
+            m = r if ctx.boundary else r[(Ellipsis,) + (slice(1, -1),) * spec.nd]
+            grad = _recompute_grad(spec, pred, ctx.yy, ctx.boundary, (2.0 / max(n, 1)) * up * m)
+        return grad, None, None, None, None, None
+
+
+def _loss(residual_method, pred, yy, boundary, flat=False):
     global _last_route
     spec = _Spec(residual_method)
     _check_tensor(pred, "pred")
     spec.field_shape(pred)                               # (called for its raise: a rank the method does not take)
     if yy is not None:
         _check_like(yy, pred, "yy")
+    if flat and spec.wants_flat(pred):
+        why, kernels = spec.prepare_flat(pred, yy)
+        if why is None:
+            r = spec.full(pred, None if yy is None else yy.detach())
+            if not _nt_fastest_dense(r):
+                why = "the forward pass returned the residual in another memory order"
+        if why is not None:
+            _last_route = "fallback:" + why
+            return spec.call(pred, boundary, yy).pow(2).mean()
+        _last_route = "fused:flat_" + spec.kind
+        return _FlatLossFn.apply(pred, spec, kernels, None if yy is None else yy.detach(), bool(boundary), r)
     why, kernels = spec.prepare(pred, yy)
     if why is not None:
         _last_route = "fallback:" + why
@@ -298,29 +434,51 @@ def _loss(residual_method, pred, yy, boundary):
     return _LossFn.apply(pred, spec, kernels, None if yy is None else yy.detach(), bool(boundary))
 
 
-def pi_loss(residual_method, pred, boundary=False):
+def pi_loss(residual_method, pred, boundary=False, flat=False):
     """``residual_method(pred, boundary).pow(2).mean()`` (``PI_loss``, Physics_Informed/Wave_FNO_PISL.py:213-214) as a
     0-d fp32 tensor on ``pred``'s device, differentiable with respect to ``pred``.  ``residual_method``: a bound
     ``residual*`` method of a class of ``cp_pre_amd.residuals``, or a ``ConvOperator`` (2-D: [BS,Nt,Nx,Ny], 1-D:
     [BS,Nt,Nx]).  ``boundary`` as on the residual methods (False: the mean runs over the interior ``[1:-1]`` of every
-    residual axis; over an empty interior it is NaN, as ``torch.mean`` of an empty tensor)."""
-    return _loss(residual_method, pred, None, boundary)
+    residual axis; over an empty interior it is NaN, as ``torch.mean`` of an empty tensor).  ``flat=True``: an Nt-fastest
+    ``pred`` (no unit stride on its last axis) is offered to the merged-row VJP (module docstring)."""
+    return _loss(residual_method, pred, None, boundary, flat)
 
 
-def pisl_loss(residual_method, pred, yy, boundary=False):
+def pisl_loss(residual_method, pred, yy, boundary=False, flat=False):
     """``(residual(pred) - residual(yy)).pow(2).mean()`` (``PISL``, Physics_Informed/Wave_FNO_PISL.py:216-217).  ``yy``
     (``pred``'s shape, dtype and device) is data: the fused route does not differentiate it (one that requires grad takes
-    the fallback, which does)."""
-    return _loss(residual_method, pred, yy, boundary)
+    the fallback, which does).  ``flat`` as on ``pi_loss``."""
+    return _loss(residual_method, pred, yy, boundary, flat)
 
 
-def residual_vjp(residual_method, vars, g, boundary=False):
+def residual_vjp(residual_method, vars, g, boundary=False, flat=False):
     """The vector-Jacobian product ``d <g, residual_method(vars, boundary)> / d vars`` for a general upstream gradient
-    ``g`` (the shape of the method's result), by the kernels the losses use.  Returns a tensor of ``vars``' shape."""
+    ``g`` (the shape of the method's result), by the kernels the losses use.  Returns a tensor of ``vars``' shape.
+    ``flat`` as on ``pi_loss`` (the gradient is then dense in ``vars``' memory order)."""
     global _last_route
     spec = _Spec(residual_method)
     _check_tensor(vars, "vars")
     _check_like(g, vars, "g", spec.out_shape(vars, boundary))
+    if flat and spec.wants_flat(vars):
+        why, kernels = spec.prepare_flat(vars)
+        if why is not None:
+            _last_route = "fallback:" + why
+            return _recompute_grad(spec, vars, None, boundary, g)
+        _last_route = "fused:flat_" + spec.kind
+        if g.numel() == 0:                               # (an empty interior: nothing reaches vars)
+            return torch.zeros(vars.shape, dtype=torch.float32, device=vars.device)
+        with torch.no_grad():
+            gfull = _lib.empty_like_layout(spec.fields(vars)[0])         # g in vars' memory order, the rim zero
+            if boundary:
+                gfull.copy_(g)
+            else:
+                gfull.zero_()
+                gfull[:, 1:-1, 1:-1, 1:-1].copy_(g)
+            grad = spec.vjp_flat(kernels, gfull, vars, False, 1.0, None) if _nt_fastest_dense(gfull) else None
+        if grad is None:
+            _last_route = "fallback:declined by the library"
+            return _recompute_grad(spec, vars, None, boundary, g)
+        return grad
     why, kernels = spec.prepare(vars)
     if why is not None:
         _last_route = "fallback:" + why

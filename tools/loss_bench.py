@@ -9,7 +9,14 @@ Also: the VJP launch alone (``residual_vjp`` with a full-grid g), time and 4 B x
 The NS momentum case is held against its floor (A at least 3x faster than B: met / MISSED).
 Plain text lines on stdout and in --out.
 
+Cases ``wave_ntfast`` (the cropped Nt-fastest view of the reference's script, Physics_Informed/Wave_FNO_PISL.py:209-217, on
+memory [BS,1,256,256,32]) and ``ns_momentum_ntfast`` (``pred.permute(0,1,4,2,3)`` of memory [BS,3,256,256,32]) time
+``pi_loss(..., flat=True)`` + ``backward()`` (the merged-row VJP of ``libcp_pre_vjpflat.so``) against the same call with
+``flat=False`` (today's fallback for such a view), alternating in one process: medians of --reps alternating measurements
+with their spread, and the peak memory of both.  They run only when named in --cases.
+
     python tools/loss_bench.py [--reps 7] [--warmup 2] [--out profiles/loss/loss_bench.txt] [--max-batch 16]
+    python tools/loss_bench.py --cases wave_ntfast,ns_momentum_ntfast --out profiles/losses/loss_bench_ntfast.txt
     rocprofv3 --kernel-trace --stats -- python tools/loss_bench.py --vjp-only      # the VJP kernel under the profiler
 """
 import argparse
@@ -59,6 +66,56 @@ def peak_of(fn):
     return torch.cuda.max_memory_allocated() - before
 
 
+def alternate_spread(fns, reps, warmup):
+    """(median, min, max) ms of each fn, the fns interleaved call by call"""
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for i, f in enumerate(fns):
+            a, b = _ev(), _ev()
+            a.record()
+            f()
+            b.record()
+            b.synchronize()
+            times[i].append(a.elapsed_time(b))
+    return [(sorted(t)[len(t) // 2], min(t), max(t)) for t in times]
+
+
+def ntfast_case(name, bs, rand, reps, warmup, emit):
+    """``flat=True`` against ``flat=False`` on an Nt-fastest view, interleaved"""
+    if name == "wave_ntfast":
+        method = R.PRE_Wave(0.01, 1 / 256).residual
+        pred = rand(bs, 1, 256, 256, 32).requires_grad_(True)
+        view = lambda: pred[:, 0, 1:-1, 1:-1, 1:-1].permute(0, 3, 1, 2)            # noqa: E731
+    else:
+        method = R.NavierStokes(0.01, 1 / 256, 1 / 256).residual_momentum
+        pred = rand(bs, 3, 256, 256, 32).requires_grad_(True)
+        view = lambda: pred.permute(0, 1, 4, 2, 3)                                  # noqa: E731
+    routes = {}
+
+    def step(flat):
+        def f():
+            pred.grad = None
+            losses.pi_loss(method, view(), flat=flat).backward()
+            routes[flat] = losses.last_route()
+        return f
+    a, b = step(True), step(False)
+    a()
+    ga = pred.grad.clone()
+    b()
+    err = float((ga - pred.grad).abs().max() / pred.grad.abs().max())
+    del ga
+    pa, pb = peak_of(a), peak_of(b)
+    (ma, la, ha), (mb, lb, hb) = alternate_spread([a, b], reps, warmup)
+    field = pred.numel() // pred.shape[1] * 4
+    emit(f"{name}: memory {list(pred.shape)}; flat=True route {routes[True]} {ma:.3f} ms [{la:.3f}, {ha:.3f}], flat=False route "
+         f"{routes[False]} {mb:.3f} ms [{lb:.3f}, {hb:.3f}], False/True = {mb / ma:.2f}x; peak memory flat=True {pa / field:.2f} fields "
+         f"({pa / 2**30:.2f} GiB), flat=False {pb / field:.2f} fields ({pb / 2**30:.2f} GiB); max |grad True - grad False| / max |grad False| "
+         f"= {err:.2e}")
+
+
 def steps(method, v):
     def a():
         v.grad = None
@@ -77,7 +134,10 @@ def main():
     ap.add_argument("--max-batch", type=int, default=16, help="cap of the timed NS batch (B's memory may allow more)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss", "loss_bench.txt"))
     ap.add_argument("--vjp-only", action="store_true", help="only a few NS momentum VJP launches (for a profiler)")
+    ap.add_argument("--cases", default="ns_momentum,burgers,wave",
+                    help="comma-separated: ns_momentum, burgers, wave, wave_ntfast, ns_momentum_ntfast")
     args = ap.parse_args()
+    wanted = [c for c in args.cases.split(",") if c]
     assert torch.cuda.is_available(), "loss_bench needs the MI355X"
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -99,15 +159,22 @@ def main():
     emit(f"# loss_bench {datetime.date.today().isoformat()} on {torch.cuda.get_device_name(0)}, torch {torch.__version__}, "
          f"HBM free {free / 2**30:.0f} of {total / 2**30:.0f} GiB; reps {args.reps}, warmup {args.warmup}")
     emit("# timings: device events around host + device work of one call, median; A and B interleaved on the same tensors. "
-         "Every case's tensors are far larger than the 256 MiB of last-level cache, so each pass streams from HBM (cold) "
-         "whether or not the call before it touched the same bytes")
+         "The tensors of ns_momentum, burgers and wave are far larger than the 256 MiB of last-level cache, so each pass streams "
+         "from HBM (cold) whether or not the call before it touched the same bytes; a field of the *_ntfast cases is 128 MiB at "
+         "batch 16: those steps are short and partly cache-resident")
 
     cases = [
         ("ns_momentum", lambda bs: rand(bs, 3, 64, 512, 512), ns.residual_momentum, args.max_batch, 11),
         ("burgers", lambda bs: rand(bs, 200, 512), R.Burgers(1 / 512, 0.0025, 0.002).residual, 4096, 7),
         ("wave", lambda bs: rand(bs, 64, 512, 512), R.PRE_Wave(0.01, 1 / 512).residual, args.max_batch, 5),
     ]
+    for name in wanted:
+        if name.endswith("_ntfast"):
+            ntfast_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
+            torch.cuda.empty_cache()
     for name, mk, method, cap, streams_a in cases:
+        if name not in wanted:
+            continue
         # B's peak per sample at a small batch; the timed batch: what fits half the free memory, capped
         small = 2 if name != "burgers" else 64
         v = mk(small).requires_grad_(True)
