@@ -249,6 +249,15 @@ VJPFLAT_SIGNATURES = {
     "pre_vjpflat_ns_momentum_f32": VJP_SIGNATURES["pre_vjp_ns_momentum_f32"],
 }
 
+# libcp_pre_wgrad.so (include/cp_pre_wgrad.h): the gradient of the losses with respect to a trainable operator kernel
+WGRAD_SO_PATH = os.path.join(_HERE, "libcp_pre_wgrad.so")
+PRE_WGRAD_ABI_VERSION = 1
+PRE_WGRAD_WORKSPACE = 55296                              # doubles
+WGRAD_SIGNATURES = {
+    "pre_wgrad_abi_version": [],
+    "pre_wgrad_stencil3d_f32": [_fld, _fld, _fld, c_int, c_int, c_int] + _scale + [c_int64] * 4 + [c_int, _fp, _fp, c_void_p],
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -272,8 +281,9 @@ _LIBS_MORE = {
     "screen1d": ("_screen1d", "SCREEN1D_", "pre_screen1d_abi_version", "PRE_SCREEN1D_ABI_VERSION", ()),
     "screenflat": ("_screenflat", "SCREENFLAT_", "pre_screenflat_abi_version", "PRE_SCREENFLAT_ABI_VERSION", ()),
     "vjpflat": ("_vjpflat", "VJPFLAT_", "pre_vjpflat_abi_version", "PRE_VJPFLAT_ABI_VERSION", ()),
+    "wgrad": ("_wgrad", "WGRAD_", "pre_wgrad_abi_version", "PRE_WGRAD_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -354,6 +364,10 @@ def load_screenflat():
 
 def load_vjpflat():
     return _vjpflat or _load("vjpflat")
+
+
+def load_wgrad():
+    return _wgrad or _load("wgrad")
 
 
 def require_gpu():

@@ -36,6 +36,17 @@ of the merged-row VJP writes the gradient, dense in the input's memory order.  R
 ``fused:flat_linear2``, ``fused:flat_ns_momentum``; whatever the library or the host checks decline (Nt >= 96, a merged
 row Ny*Nt that is no multiple of 4, u / v whose rows are not dense, the 1-D family, everything that falls back above)
 takes the fallback with its reason.
+
+``wgrad=True`` (off by default: nothing above changes, ``libcp_pre_wgrad.so`` is never loaded) lets the operator kernel
+itself be trained, as the reference's wave scripts do (``Physics_Informed/Wave_FNO_PI.py:202-210``:
+``D.kernel.requires_grad = True``).  For the kinds that are ONE linear operator - ``stencil3d``, ``stencil2d`` and
+``flat_stencil3d``: a ``ConvOperator``, ``PRE_Wave.residual``, ``Advection.residual`` - a kernel that requires grad no
+longer declines the fused route: forward pass and field VJP are the launches above on a snapshot of the kernel, and in the
+same ``backward`` ONE launch of ``pre_wgrad_stencil3d_f32`` (``include/cp_pre_wgrad.h``) reads the saved r, ``pred`` (and
+``yy``) where they lie and returns ``kernel.grad``: mask and scale on load, no atomics, the same bytes every run.  Routes
+``fused:stencil3d+wgrad``, ``fused:stencil2d+wgrad``, ``fused:flat_stencil3d+wgrad``.  NS momentum, NS continuity and
+Burgers (several operators, or a non-linear residual), any residual where several operator kernels require grad, and
+``residual_vjp`` keep ``fallback:operator kernel requires grad``.  ``kernel_vjp`` is the same launch for a general g.
 """
 from __future__ import annotations
 
@@ -135,9 +146,10 @@ class _Spec:
             return r if r is not None else self.method(x) - self.method(minus)
 
     # -------- can the fused VJP run?  (host checks + one download of the operator kernels)
-    def prepare(self, x, minus=None):
+    def prepare(self, x, minus=None, wgrad=False):
         """(why, kernels): ``why`` is None if the fused VJP can run on ``x`` - ``kernels`` are then the host copies of the
-        operator kernels the launch takes - else the reason for the fallback.  Changes nothing on ``self``."""
+        operator kernels the launch takes - else the reason for the fallback.  Changes nothing on ``self``.  ``wgrad``: a
+        kernel that requires grad does not decline a kind that is one linear operator."""
         why, kernels = self.why, ()
         if self.kind is None:
             return why, kernels
@@ -148,18 +160,22 @@ class _Spec:
         elif x.stride(-1) != 1 or (minus is not None and minus.stride(-1) != 1):
             why = "no unit stride on the last axis"
         else:
-            why = self._declined(x, minus)
+            why = self._declined(x, minus, wgrad)
             if why is None:
                 why, kernels = self._host_kernels()
         return why, kernels
 
-    def _declined(self, x, minus):
+    def trains_kernel(self):
+        """Is this ONE linear operator whose kernel requires grad - what ``wgrad=True`` hands to ``pre_wgrad_stencil3d_f32``?"""
+        return self.kind in ("stencil3d", "stencil2d") and len(self.ops) == 1 and _dispatch.needs_grad(self.ops[0].kernel)
+
+    def _declined(self, x, minus, wgrad=False):
         """What keeps a fused VJP from running whatever the layout (no download), or None."""
         if getattr(self.obj, "fused", True) is False:
             return "fused=False"
         if minus is not None and minus.requires_grad and torch.is_grad_enabled():
             return "yy requires grad"
-        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
+        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]) and not (wgrad and self.trains_kernel()):
             return "operator kernel requires grad"
         if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
             return "multi-channel wave input"
@@ -194,14 +210,14 @@ class _Spec:
             return [x[:, i] for i in self.chan]
         return [x[:, 0] if x.dim() == 5 else x]
 
-    def prepare_flat(self, x, minus=None):
+    def prepare_flat(self, x, minus=None, wgrad=False):
         """``prepare`` for the merged-row VJP of ``libcp_pre_vjpflat.so``: (why, kernels).  The layout conditions are the
         library's own (include/cp_pre_vjpflat.h), stated here so that the reason has a name."""
         if self.kind is None:
             return self.why, ()
         if self.nd != 3:
             return "no flat VJP for the 1-D family", ()
-        why = self._declined(x, minus)
+        why = self._declined(x, minus, wgrad)
         if why is not None:
             return why, ()
         f = self.fields(x)
@@ -294,6 +310,32 @@ class _Spec:
         if self.chan is not None and x.shape[1] > len(self.chan):
             grad[:, len(self.chan):].zero_()
         return grad
+
+
+    # -------- the kernel-gradient launch: g [BS,*field], x (and minus) where they lie -> d / d kernel, on x's device
+    def wgrad(self, g, x, minus, crop, host_scale, dev_scale):
+        """``scale * sum_c m_c g_c (x - minus)_{c + k}`` for every tap k of the operator's kernel, by ONE launch of
+        ``pre_wgrad_stencil3d_f32``.  None if the library declines (another layout, extents other than 1 / 3)."""
+        ext = tuple(self.ops[0].kernel.shape)
+        if len(ext) != self.nd:
+            return None
+        views = [g] + [v[:, 0] if v.dim() == self.nd + 2 else v for v in (x, minus) if v is not None]
+        flags = _lib.PRE_VJP_CROP if crop else 0
+        if self.nd == 2:                                 # [B,T,X] with a (kt,kx) kernel == [1,B,T,X] with (1,kt,kx)
+            views, ext3, flags = [v.unsqueeze(0) for v in views], (1,) + ext, flags | _lib.PRE_VJP_VIEW3D
+        else:
+            ext3 = ext
+        lib = _lib.load_wgrad()
+        ws = torch.empty(_lib.PRE_WGRAD_WORKSPACE, dtype=torch.float64, device=x.device)
+        dk = torch.empty(ext, dtype=torch.float32, device=x.device)
+        fs = [ctypes.byref(_lib.field(v)) for v in views] + [None] * (3 - len(views))
+        with torch.cuda.device(x.device):
+            rc = lib.pre_wgrad_stencil3d_f32(*fs, *ext3, float(host_scale), _lib.ptr(dev_scale), *views[0].shape, flags,
+                                             _lib.ptr(ws), _lib.ptr(dk), _lib.stream())
+        if rc == _lib.PRE_E_UNSUPPORTED:
+            return None
+        _lib.check(rc, "pre_wgrad_stencil3d_f32")
+        return dk
 
 
 FLAT_MAX_NT = 96             # star_march.hip's FLAT_MAX_Y: the merged-row form's own bound on the contiguous extent
@@ -408,7 +450,59 @@ class _FlatLossFn(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
-def _loss(residual_method, pred, yy, boundary, flat=False):
+def _recompute_kernel_grad(spec, x, minus, boundary, g):
+    """d <g, method(x) - method(minus)> / d kernel by the route that ran before: the composed expression on a fresh leaf
+    in the operator's ``kernel`` slot, differentiated by torch."""
+    op = spec.ops[0]
+    held = op.kernel
+    with torch.enable_grad():
+        k = held.detach().clone().requires_grad_(True)
+        op.kernel = k
+        try:
+            y = spec.call(x.detach(), boundary, None if minus is None else minus.detach())
+        finally:
+            op.kernel = held
+        if y.numel() == 0:
+            return torch.zeros_like(k)
+        return torch.autograd.grad(y, k, g.to(y.device))[0]
+
+
+class _KernelLossFn(torch.autograd.Function):
+    """``_LossFn`` / ``_FlatLossFn`` (``flat``: r arrives evaluated) with the operator kernel as a second input: the same
+    forward launches, the same field VJP launch, and ``pre_wgrad_stencil3d_f32`` for the kernel in the same backward."""
+
+    @staticmethod
+    def forward(ctx, pred, kernel, spec, kernels, yy, boundary, flat, r):
+        if r is None:
+            r = spec.full(pred, yy)
+        loss, n = _mean_sq(r, boundary, where_it_lies=flat)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(r, pred, kernel)
+            ctx.spec, ctx.kernels, ctx.yy, ctx.boundary, ctx.n, ctx.flat = spec, kernels, yy, boundary, n, flat
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        r, pred, kernel = ctx.saved_tensors
+        spec, n = ctx.spec, ctx.n
+        up = gout.detach().to(device=pred.device, dtype=torch.float32).reshape(1)
+        scale = 2.0 / n if n else 0.0
+        composed_g = lambda: (2.0 / max(n, 1)) * up * (r if ctx.boundary else r[(Ellipsis,) + (slice(1, -1),) * spec.nd])  # noqa: E731
+        grad = gk = None
+        if ctx.needs_input_grad[0]:
+            grad = (spec.vjp_flat if ctx.flat else spec.vjp)(ctx.kernels, r, pred, not ctx.boundary, scale, up)
+            if grad is None:                             # (not expected after prepare(): the library declined)
+                grad = _recompute_grad(spec, pred, ctx.yy, ctx.boundary, composed_g())
+        if ctx.needs_input_grad[1]:
+            gk = spec.wgrad(r, pred, ctx.yy, not ctx.boundary, scale, up)
+            if gk is None:                               # the library declined (a layout it does not take): composed
+                gk = _recompute_kernel_grad(spec, pred, ctx.yy, ctx.boundary, composed_g())
+            gk = gk.to(kernel.device)
+        return grad, gk, None, None, None, None, None, None
+
+
+def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False):
     global _last_route
     spec = _Spec(residual_method)
     _check_tensor(pred, "pred")
@@ -416,7 +510,7 @@ def _loss(residual_method, pred, yy, boundary, flat=False):
     if yy is not None:
         _check_like(yy, pred, "yy")
     if flat and spec.wants_flat(pred):
-        why, kernels = spec.prepare_flat(pred, yy)
+        why, kernels = spec.prepare_flat(pred, yy, wgrad)
         if why is None:
             r = spec.full(pred, None if yy is None else yy.detach())
             if not _nt_fastest_dense(r):
@@ -424,37 +518,50 @@ def _loss(residual_method, pred, yy, boundary, flat=False):
         if why is not None:
             _last_route = "fallback:" + why
             return spec.call(pred, boundary, yy).pow(2).mean()
+        if wgrad and spec.trains_kernel():
+            _last_route = "fused:flat_" + spec.kind + "+wgrad"
+            return _KernelLossFn.apply(pred, spec.ops[0].kernel, spec, kernels, None if yy is None else yy.detach(),
+                                       bool(boundary), True, r)
         _last_route = "fused:flat_" + spec.kind
         return _FlatLossFn.apply(pred, spec, kernels, None if yy is None else yy.detach(), bool(boundary), r)
-    why, kernels = spec.prepare(pred, yy)
+    why, kernels = spec.prepare(pred, yy, wgrad)
     if why is not None:
         _last_route = "fallback:" + why
         return spec.call(pred, boundary, yy).pow(2).mean()
+    if wgrad and spec.trains_kernel():
+        _last_route = "fused:" + spec.kind + "+wgrad"
+        return _KernelLossFn.apply(pred, spec.ops[0].kernel, spec, kernels, None if yy is None else yy.detach(),
+                                   bool(boundary), False, None)
     _last_route = "fused:" + spec.kind
     return _LossFn.apply(pred, spec, kernels, None if yy is None else yy.detach(), bool(boundary))
 
 
-def pi_loss(residual_method, pred, boundary=False, flat=False):
+def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False):
     """``residual_method(pred, boundary).pow(2).mean()`` (``PI_loss``, Physics_Informed/Wave_FNO_PISL.py:213-214) as a
     0-d fp32 tensor on ``pred``'s device, differentiable with respect to ``pred``.  ``residual_method``: a bound
     ``residual*`` method of a class of ``cp_pre_amd.residuals``, or a ``ConvOperator`` (2-D: [BS,Nt,Nx,Ny], 1-D:
     [BS,Nt,Nx]).  ``boundary`` as on the residual methods (False: the mean runs over the interior ``[1:-1]`` of every
     residual axis; over an empty interior it is NaN, as ``torch.mean`` of an empty tensor).  ``flat=True``: an Nt-fastest
-    ``pred`` (no unit stride on its last axis) is offered to the merged-row VJP (module docstring)."""
-    return _loss(residual_method, pred, None, boundary, flat)
+    ``pred`` (no unit stride on its last axis) is offered to the merged-row VJP (module docstring).  ``wgrad=True``: a
+    single linear operator (a ``ConvOperator``, ``PRE_Wave.residual``, ``Advection.residual``) whose kernel requires grad
+    keeps the fused route and gets ``kernel.grad`` from one launch of ``pre_wgrad_stencil3d_f32`` (route ``...+wgrad``);
+    NS momentum, NS continuity, Burgers and any residual where several operator kernels require grad keep
+    ``fallback:operator kernel requires grad``."""
+    return _loss(residual_method, pred, None, boundary, flat, wgrad)
 
 
-def pisl_loss(residual_method, pred, yy, boundary=False, flat=False):
+def pisl_loss(residual_method, pred, yy, boundary=False, flat=False, wgrad=False):
     """``(residual(pred) - residual(yy)).pow(2).mean()`` (``PISL``, Physics_Informed/Wave_FNO_PISL.py:216-217).  ``yy``
     (``pred``'s shape, dtype and device) is data: the fused route does not differentiate it (one that requires grad takes
-    the fallback, which does).  ``flat`` as on ``pi_loss``."""
-    return _loss(residual_method, pred, yy, boundary, flat)
+    the fallback, which does).  ``flat`` and ``wgrad`` as on ``pi_loss`` (the kernel gradient reads ``pred - yy``)."""
+    return _loss(residual_method, pred, yy, boundary, flat, wgrad)
 
 
 def residual_vjp(residual_method, vars, g, boundary=False, flat=False):
     """The vector-Jacobian product ``d <g, residual_method(vars, boundary)> / d vars`` for a general upstream gradient
     ``g`` (the shape of the method's result), by the kernels the losses use.  Returns a tensor of ``vars``' shape.
-    ``flat`` as on ``pi_loss`` (the gradient is then dense in ``vars``' memory order)."""
+    ``flat`` as on ``pi_loss`` (the gradient is then dense in ``vars``' memory order).  Operator kernels that require grad
+    take ``fallback:operator kernel requires grad`` here (their own gradient: ``kernel_vjp``)."""
     global _last_route
     spec = _Spec(residual_method)
     _check_tensor(vars, "vars")
@@ -494,3 +601,59 @@ def residual_vjp(residual_method, vars, g, boundary=False, flat=False):
         return _recompute_grad(spec, vars, None, boundary, g)
     _last_route = "fused:" + spec.kind
     return grad
+
+
+def kernel_vjp(residual_method, vars, g, boundary=False, minus=None):
+    """The counterpart of ``residual_vjp`` for the operator kernel: ``d <g, method(vars) - method(minus)> / d kernel`` for a
+    general upstream gradient ``g`` (the shape of the method's result), by the launch ``wgrad=True`` uses, with scale 1.
+    ``residual_method``: one linear operator (a ``ConvOperator``, ``PRE_Wave.residual``, ``Advection.residual``); the kernel
+    need not require grad.  Returns a tensor of the kernel's shape on the kernel's device.  Where the fused route declines
+    (``last_route()`` says why) the same gradient comes from ``torch.autograd.grad`` through the composed expression."""
+    global _last_route
+    spec = _Spec(residual_method)
+    if not (spec.is_op or isinstance(spec.obj, (R.PRE_Wave, R.Advection))):
+        raise TypeError("kernel_vjp takes a residual that is one linear operator: a ConvOperator, PRE_Wave.residual, "
+                        "Advection.residual")
+    _check_tensor(vars, "vars")
+    _check_like(g, vars, "g", spec.out_shape(vars, boundary))
+    if minus is not None:
+        _check_like(minus, vars, "minus")
+    kernel = (spec.method if spec.is_op else spec.obj.D).kernel
+    why = spec.why
+    if why is None:
+        if not vars.is_cuda:
+            why = "input on the CPU"
+        elif vars.numel() == 0:
+            why = "empty input"
+        elif getattr(spec.obj, "fused", True) is False:
+            why = "fused=False"
+        elif isinstance(spec.obj, R.PRE_Wave) and vars.dim() == 5 and vars.shape[1] != 1:
+            why = "multi-channel wave input"
+        elif any(s not in (1, 3) for s in kernel.shape) or kernel.dim() != spec.nd:
+            why = "operator kernel extents other than 1 and 3"
+        else:
+            f = spec.fields(vars)[0]
+            m = None if minus is None else spec.fields(minus)[0]
+            if not (all(v.stride(-1) == 1 for v in (f, m) if v is not None) or
+                    (spec.nd == 3 and all(v.stride(1) == 1 for v in (f, m) if v is not None))):
+                why = "no unit stride on the last axis or on Nt"
+    if why is not None:
+        _last_route = "fallback:" + why
+        spec.ops = (spec.method if spec.is_op else spec.obj.D,)          # (a spectral operator resolves to no kind)
+        return _recompute_kernel_grad(spec, vars, minus, boundary, g).to(kernel.device)
+    flat = f.stride(-1) != 1
+    _last_route = "fused:" + ("flat_" if flat else "") + spec.kind + "+wgrad"
+    if g.numel() == 0:                                   # (an empty interior: nothing reaches the kernel)
+        return torch.zeros(kernel.shape, dtype=torch.float32, device=kernel.device)
+    with torch.no_grad():
+        gfull = _lib.empty_like_layout(f)                # g in the field's memory order, the rim zero
+        if boundary:
+            gfull.copy_(g)
+        else:
+            gfull.zero_()
+            gfull[(slice(None),) + (slice(1, -1),) * spec.nd].copy_(g)
+        gk = spec.wgrad(gfull, vars, minus, False, 1.0, None)
+    if gk is None:
+        _last_route = "fallback:declined by the library"
+        return _recompute_kernel_grad(spec, vars, minus, boundary, g).to(kernel.device)
+    return gk.to(kernel.device)

@@ -15,8 +15,14 @@ memory [BS,1,256,256,32]) and ``ns_momentum_ntfast`` (``pred.permute(0,1,4,2,3)`
 ``flat=False`` (today's fallback for such a view), alternating in one process: medians of --reps alternating measurements
 with their spread, and the peak memory of both.  They run only when named in --cases.
 
+Cases ``wave_kgrad`` and ``wave_ntfast_kgrad`` are the shapes of ``wave`` and ``wave_ntfast`` with
+``D.kernel.requires_grad = True`` (Physics_Informed/Wave_FNO_PI.py:202-210): ``pi_loss(..., wgrad=True)`` + ``backward()`` (the
+field VJP and ONE ``pre_wgrad_stencil3d_f32`` launch of ``libcp_pre_wgrad.so``) against the same call without ``wgrad`` (the
+route ``fallback:operator kernel requires grad``), alternating in one process.  They run only when named in --cases.
+
     python tools/loss_bench.py [--reps 7] [--warmup 2] [--out profiles/loss/loss_bench.txt] [--max-batch 16]
     python tools/loss_bench.py --cases wave_ntfast,ns_momentum_ntfast --out profiles/losses/loss_bench_ntfast.txt
+    python tools/loss_bench.py --cases wave_kgrad,wave_ntfast_kgrad --out profiles/losses/loss_bench_kgrad.txt
     rocprofv3 --kernel-trace --stats -- python tools/loss_bench.py --vjp-only      # the VJP kernel under the profiler
 """
 import argparse
@@ -116,6 +122,41 @@ def ntfast_case(name, bs, rand, reps, warmup, emit):
          f"= {err:.2e}")
 
 
+def kgrad_case(name, bs, rand, reps, warmup, emit):
+    """``wgrad=True`` against the same call without it, the operator kernel requiring grad, interleaved"""
+    ntfast = name == "wave_ntfast_kgrad"
+    wave = R.PRE_Wave(0.01, 1 / 256 if ntfast else 1 / 512, device="cuda")
+    wave.D.kernel.requires_grad = True
+    if ntfast:
+        pred = rand(bs, 1, 256, 256, 32).requires_grad_(True)
+        view = lambda: pred[:, 0, 1:-1, 1:-1, 1:-1].permute(0, 3, 1, 2)            # noqa: E731
+    else:
+        pred = rand(bs, 64, 512, 512).requires_grad_(True)
+        view = lambda: pred                                                         # noqa: E731
+    routes = {}
+
+    def step(wgrad):
+        def f():
+            pred.grad = wave.D.kernel.grad = None
+            losses.pi_loss(wave.residual, view(), flat=ntfast, wgrad=wgrad).backward()
+            routes[wgrad] = losses.last_route()
+        return f
+    a, b = step(True), step(False)
+    a()
+    ga, ka = pred.grad.clone(), wave.D.kernel.grad.clone()
+    b()
+    err = float((ga - pred.grad).abs().max() / pred.grad.abs().max())
+    kerr = float((ka - wave.D.kernel.grad).abs().max() / wave.D.kernel.grad.abs().max())
+    del ga
+    pa, pb = peak_of(a), peak_of(b)
+    (ma, la, ha), (mb, lb, hb) = alternate_spread([a, b], reps, warmup)
+    field = pred.numel() * 4
+    emit(f"{name}: memory {list(pred.shape)}; wgrad=True route {routes[True]} {ma:.3f} ms [{la:.3f}, {ha:.3f}], wgrad=False route "
+         f"{routes[False]} {mb:.3f} ms [{lb:.3f}, {hb:.3f}], False/True = {mb / ma:.2f}x; peak memory wgrad=True {pa / field:.2f} fields "
+         f"({pa / 2**30:.2f} GiB), wgrad=False {pb / field:.2f} fields ({pb / 2**30:.2f} GiB); max |dpred True - False| / max = "
+         f"{err:.2e}, max |dK True - False| / max = {kerr:.2e}")
+
+
 def steps(method, v):
     def a():
         v.grad = None
@@ -135,7 +176,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss", "loss_bench.txt"))
     ap.add_argument("--vjp-only", action="store_true", help="only a few NS momentum VJP launches (for a profiler)")
     ap.add_argument("--cases", default="ns_momentum,burgers,wave",
-                    help="comma-separated: ns_momentum, burgers, wave, wave_ntfast, ns_momentum_ntfast")
+                    help="comma-separated: ns_momentum, burgers, wave, wave_ntfast, ns_momentum_ntfast, wave_kgrad, "
+                         "wave_ntfast_kgrad")
     args = ap.parse_args()
     wanted = [c for c in args.cases.split(",") if c]
     assert torch.cuda.is_available(), "loss_bench needs the MI355X"
@@ -169,6 +211,9 @@ def main():
         ("wave", lambda bs: rand(bs, 64, 512, 512), R.PRE_Wave(0.01, 1 / 512).residual, args.max_batch, 5),
     ]
     for name in wanted:
+        if name.endswith("_kgrad"):
+            kgrad_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
+            torch.cuda.empty_cache()
         if name.endswith("_ntfast"):
             ntfast_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
             torch.cuda.empty_cache()
