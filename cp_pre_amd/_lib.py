@@ -258,6 +258,23 @@ WGRAD_SIGNATURES = {
     "pre_wgrad_stencil3d_f32": [_fld, _fld, _fld, c_int, c_int, c_int] + _scale + [c_int64] * 4 + [c_int, _fp, _fp, c_void_p],
 }
 
+# libcp_pre_cns.so (include/cp_pre_cns.h): the compressible-NS right-hand side on the 2-D spatial operators, one pass
+CNS_SO_PATH = os.path.join(_HERE, "libcp_pre_cns.so")
+PRE_CNS_ABI_VERSION = 1
+PRE_CNS_TILE_ROWS, PRE_CNS_TILE_COLS = 16, 64
+
+
+class PreCnsPlane(ctypes.Structure):
+    """``pre_cns_plane_t`` / ``pre_cns_out_t`` (same layout): a [B,X,Y] plane view, unit stride along Y."""
+    _fields_ = [("ptr", c_void_p), ("sB", c_int64), ("sX", c_int64)]
+
+
+CNS_SIGNATURES = {
+    "pre_cns_abi_version": [],
+    "pre_cns_rhs_f32": [POINTER(PreCnsPlane), POINTER(PreCnsPlane)] + [POINTER(c_float)] * 5 + [POINTER(PreBC), c_float,
+                        POINTER(PreCnsPlane), c_float] + [c_int64] * 3 + [c_int, c_void_p],
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -282,8 +299,9 @@ _LIBS_MORE = {
     "screenflat": ("_screenflat", "SCREENFLAT_", "pre_screenflat_abi_version", "PRE_SCREENFLAT_ABI_VERSION", ()),
     "vjpflat": ("_vjpflat", "VJPFLAT_", "pre_vjpflat_abi_version", "PRE_VJPFLAT_ABI_VERSION", ()),
     "wgrad": ("_wgrad", "WGRAD_", "pre_wgrad_abi_version", "PRE_WGRAD_ABI_VERSION", ()),
+    "cns": ("_cns", "CNS_", "pre_cns_abi_version", "PRE_CNS_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -368,6 +386,10 @@ def load_vjpflat():
 
 def load_wgrad():
     return _wgrad or _load("wgrad")
+
+
+def load_cns():
+    return _cns or _load("cns")
 
 
 def require_gpu():
