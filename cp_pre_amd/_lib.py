@@ -275,6 +275,16 @@ CNS_SIGNATURES = {
                         POINTER(PreCnsPlane), c_float] + [c_int64] * 3 + [c_int, c_void_p],
 }
 
+# libcp_pre_cnsvjp.so (include/cp_pre_cnsvjp.h): the vector-Jacobian product of that right-hand side, one pass (PreCnsPlane reused)
+CNSVJP_SO_PATH = os.path.join(_HERE, "libcp_pre_cnsvjp.so")
+PRE_CNSVJP_ABI_VERSION = 1
+PRE_CNSVJP_TILE_ROWS, PRE_CNSVJP_TILE_COLS = 16, 64
+CNSVJP_SIGNATURES = {
+    "pre_cnsvjp_abi_version": [],
+    "pre_cns_vjp_f32": [POINTER(PreCnsPlane)] * 3 + [POINTER(c_float)] * 5 + [POINTER(PreBC), c_float, POINTER(PreCnsPlane),
+                        c_float] + [c_int64] * 3 + [c_int, c_void_p],
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -300,8 +310,9 @@ _LIBS_MORE = {
     "vjpflat": ("_vjpflat", "VJPFLAT_", "pre_vjpflat_abi_version", "PRE_VJPFLAT_ABI_VERSION", ()),
     "wgrad": ("_wgrad", "WGRAD_", "pre_wgrad_abi_version", "PRE_WGRAD_ABI_VERSION", ()),
     "cns": ("_cns", "CNS_", "pre_cns_abi_version", "PRE_CNS_ABI_VERSION", ()),
+    "cnsvjp": ("_cnsvjp", "CNSVJP_", "pre_cnsvjp_abi_version", "PRE_CNSVJP_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -390,6 +401,10 @@ def load_wgrad():
 
 def load_cns():
     return _cns or _load("cns")
+
+
+def load_cnsvjp():
+    return _cnsvjp or _load("cnsvjp")
 
 
 def require_gpu():

@@ -27,8 +27,11 @@ Deviation (``param_grads=False``, the default): the operator kernels, ``dx`` and
 reference they carry ``requires_grad=True``, but the module has no ``nn.Parameter`` (``count_params() == 0``) and nothing
 consumes those gradients; a backward through this module then differentiates with respect to ``vars`` only.
 ``param_grads=True`` delivers every gradient the reference would (the operator kernels, hence their ``scale``, and
-``gamma``).  Either way the forward is the fused pass and the backward recomputes the composed expression
-(``_dispatch._Recompute``); a fused backward is not part of this module.
+``gamma``).  Either way the forward is the fused pass.  With ``backward="recompute"`` (the default) the backward recomputes
+the composed expression (``_dispatch._Recompute``).  ``backward="fused"`` opts in to ONE launch of ``libcp_pre_cnsvjp.so``
+(``include/cp_pre_cnsvjp.h``) for the gradient of all four fields; ``step`` is then differentiable with respect to ``vars``
+and ``base`` too, and ``vjp`` is the bare product.  ``param_grads=True`` keeps the recompute route: the fused pass has no
+gradient for the kernels or ``gamma``.  ``last_backward_route()`` says which route the last backward took.
 """
 from __future__ import annotations
 
@@ -44,6 +47,19 @@ from .vector_convops_spatial import Divergence, Gradient, Laplace, _bc_struct, d
 TILE = (_lib.PRE_CNS_TILE_ROWS, _lib.PRE_CNS_TILE_COLS)     # rows x columns a workgroup of the fused pass owns
 
 _last_route = None
+_last_backward_route = None
+
+
+def last_backward_route():
+    """'fused:cns_vjp', 'fused:cns_vjp+axpy' (the epilogue: ``step`` with ``base`` being ``vars``, ``vjp(add_to=...)``) or
+    'fallback:<why>' of the last backward through a module built with ``backward="fused"``, or of its last ``vjp`` call."""
+    return _last_backward_route
+
+
+def _set_backward_route(route):
+    global _last_backward_route
+    _last_backward_route = route
+    return route
 
 
 def last_route():
@@ -68,13 +84,48 @@ def _aligned(t):
     return sy == 1 and t.data_ptr() % 16 == 0 and sc % 4 == 0 and sx % 4 == 0 and (t.shape[0] == 1 or sb % 4 == 0)
 
 
+def _aligned_or_copy(t):
+    """``t`` if the fused passes can read it where it lies, else a dense copy (an allocation of its own is 16-byte aligned;
+    ``contiguous()`` would hand a dense view that starts off a 16-byte boundary straight back)."""
+    return t if _aligned(t) else t.clone(memory_format=torch.contiguous_format)
+
+
+class _FusedVjp(torch.autograd.Function):
+    """Attach the result of the fused forward (``h is None``) or of the fused step ``base + h * rhs(vars)`` to the autograd
+    graph with ONE launch of ``pre_cns_vjp_f32`` as its backward: ``d_vars = J^T g``, or ``h * J^T g`` and ``d_base = g``, or
+    ``g + h * J^T g`` in the launch's epilogue where ``base`` is ``vars`` (``base is None`` here).  ``taps`` are the operators'
+    kernels, the boundary structure and gamma as of the forward call.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, res, module, taps, h, vars, base):
+        ctx.module, ctx.taps, ctx.h, ctx.own_base = module, taps, h, base is not None
+        ctx.save_for_backward(vars)
+        return res.view_as(res)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (vars,) = ctx.saved_tensors
+        d_vars = None
+        if ctx.needs_input_grad[4]:
+            if ctx.h is None:
+                d_vars = ctx.module._vjp_launch(vars, g, ctx.taps)
+            elif ctx.own_base:                                       # (the entry's scale belongs to its epilogue)
+                d_vars = ctx.module._vjp_launch(vars, g, ctx.taps).mul_(ctx.h)
+            else:
+                d_vars = ctx.module._vjp_launch(vars, g, ctx.taps, add_to=g, scale=ctx.h)
+        return None, None, None, None, d_vars, (g if ctx.own_base and ctx.needs_input_grad[5] else None)
+
+
 class Euler_FV_OS_rhs(nn.Module):
     """Compressible Navier-Stokes finite-volume operator-splitting right-hand side (``Active_Learning/CNS.py:6``).
 
-    ``fused=False`` composes the operators as the reference does.  ``param_grads``: see the module docstring."""
+    ``fused=False`` composes the operators as the reference does.  ``param_grads``, ``backward``: see the module docstring."""
 
-    def __init__(self, configuration, device, fused=True, param_grads=False):
+    def __init__(self, configuration, device, fused=True, param_grads=False, backward="recompute"):
         super().__init__()
+        if backward not in ("recompute", "fused"):
+            raise ValueError("backward must be 'recompute' or 'fused'")
         self.dx = torch.tensor(configuration['Physics']['dx'], dtype=torch.float32, requires_grad=True).to(device)
         self.dy = torch.tensor(configuration['Physics']['dy'], dtype=torch.float32, requires_grad=True).to(device)
         self.gamma = torch.tensor(5 / 3, dtype=torch.float32, requires_grad=True).to(device)
@@ -85,6 +136,7 @@ class Euler_FV_OS_rhs(nn.Module):
 
         self.fused = fused
         self.param_grads = param_grads
+        self.backward = backward
         self._gamma_seen = None                 # the value a stream capture is recorded with (as _dispatch.host_kernel)
 
     def count_params(self):
@@ -171,14 +223,16 @@ class Euler_FV_OS_rhs(nn.Module):
         self._gamma_seen = float(self.gamma.detach())
         return self._gamma_seen
 
-    def _launch(self, vars, base=None, h=0.0, out=None):
+    def _taps(self):
+        """(the five kernels as host floats, the boundary structure, gamma) as they are NOW: what one launch is handed."""
+        return [_dispatch.dense9(op.kernel) for op in self._operators()], _bc_struct(self.gradient.bc), self._gamma_host()
+
+    def _launch(self, vars, base=None, h=0.0, out=None, taps=None):
         """One launch of ``pre_cns_rhs_f32``.  Returns (result on the caller's device, None) or (None, why)."""
         why = self._why_not(vars)
         if why is not None:
             return None, why
-        kernels = [_dispatch.dense9(op.kernel) for op in self._operators()]
-        st = _bc_struct(self.gradient.bc)
-        gamma = self._gamma_host()
+        kernels, st, gamma = self._taps() if taps is None else taps
         dev, origin = _dispatch.to_device(vars)
         if not _aligned(dev):
             return None, "misaligned view"
@@ -230,17 +284,108 @@ class Euler_FV_OS_rhs(nn.Module):
 
         ks = [op.kernel for op in self._operators()]
         if self.param_grads:
-            return _dispatch.fused_or_composed(fused, self._expression, vars, *ks, self.gamma)
+            expr = self._expression if self.backward != "fused" else self._noting("param_grads=True", self._expression)
+            return _dispatch.fused_or_composed(fused, expr, vars, *ks, self.gamma)
         consts = [k.detach() for k in ks] + [self.gamma.detach()]
+        if self.backward == "fused" and _dispatch.needs_grad(vars):
+            with torch.no_grad():
+                taps = self._taps()
+                res, why = self._launch(vars, taps=taps)
+            _set_route("fused:cns_rhs" if why is None else "fallback:" + why)
+            if why is None:
+                return _FusedVjp.apply(res, self, taps, None, vars, None)
+            _set_backward_route("fallback:forward fell back: " + why)
+            return self._expression(vars, *consts)
         return _dispatch.fused_or_composed(fused, lambda x: self._expression(x, *consts), vars)
+
+    @staticmethod
+    def _noting(why, fn):
+        """``fn``, noting in ``last_backward_route()`` that the recompute route ran (it is called from the backward)."""
+        def noted(*a):
+            _set_backward_route("fallback:" + why)
+            return fn(*a)
+        return noted
+
+    # ------------------------------------------------------------------------------- the fused backward
+    def plan_backward(self, vars):
+        """The route a backward through ``forward(vars)`` would take, from the host-side checks alone: 'fused:cns_vjp' or
+        'fallback:<why>'."""
+        if self.backward != "fused":
+            return "fallback:backward='recompute'"
+        if self.param_grads:
+            return "fallback:param_grads=True"
+        if not self.fused:
+            return "fallback:fused=False"
+        why = self._why_not(vars)
+        return "fused:cns_vjp" if why is None else "fallback:" + why
+
+    def _vjp_launch(self, vars, cotangent, taps, out=None, add_to=None, scale=1.0):
+        """One launch of ``pre_cns_vjp_f32``: ``J(vars)^T cotangent``, or ``add_to + scale * J^T cotangent``.  A cotangent or an
+        ``add_to`` that is not an aligned view (an expanded one, say) is made contiguous first.  Returns the gradient on
+        ``vars``' device (``out`` itself if given)."""
+        kernels, st, gamma = taps
+        dev, origin = _dispatch.to_device(vars)
+        if tuple(cotangent.shape) != tuple(dev.shape) or cotangent.dtype != torch.float32:
+            raise ValueError("the cotangent must be an fp32 tensor of vars' shape")
+        dev = _aligned_or_copy(dev)
+        cot = _aligned_or_copy(cotangent.detach().to(dev.device))
+        if out is None:
+            res = torch.empty(dev.shape, dtype=torch.float32, device=dev.device)
+        else:
+            if not (out.is_cuda and out.shape == dev.shape and out.dtype == torch.float32 and out.device == dev.device and _aligned(out)):
+                raise ValueError("out must be an fp32 device tensor of vars' shape, unit stride along Ny, 16-byte aligned rows")
+            res = out
+        add = None
+        if add_to is not None:
+            if add_to is cotangent:
+                add = cot
+            elif add_to is out:
+                add = res
+            else:
+                if tuple(add_to.shape) != tuple(dev.shape) or add_to.dtype != torch.float32:
+                    raise ValueError("add_to must be an fp32 tensor of vars' shape")
+                add = _aligned_or_copy(add_to.detach().to(dev.device))
+        with torch.cuda.device(dev.device):
+            rc = _lib.load_cnsvjp().pre_cns_vjp_f32(_planes(dev), _planes(cot), _planes(res), *kernels, ctypes.byref(st), gamma,
+                                                    _planes(add) if add is not None else None, float(scale),
+                                                    dev.shape[0], dev.shape[2], dev.shape[3], 0, _lib.stream())
+        if rc == _lib.PRE_E_RANGE and out is not None:
+            raise ValueError("out must not overlap vars or the cotangent (a tile's halo is another tile's output), and may "
+                             "overlap add_to only by being it")
+        _lib.check(rc, "pre_cns_vjp_f32")
+        _set_backward_route("fused:cns_vjp" if add is None else "fused:cns_vjp+axpy")
+        return res if out is not None else _dispatch.from_device(res, origin)
+
+    def vjp(self, vars, cotangent, out=None, add_to=None, scale=1.0):
+        """The bare product ``J(vars)^T cotangent`` of the right-hand side, no autograd involved: what an adjoint-method
+        stepper calls.  With ``add_to`` the result is ``add_to + scale * J^T cotangent`` in the same launch; ``add_to`` may be
+        ``out`` itself (accumulation) or ``cotangent`` (the adjoint of an Euler step).  ``out``: optional fp32 device tensor to
+        write into; it must not overlap ``vars`` or ``cotangent``.  Whatever the fused pass does not take is an error here."""
+        why = "fused=False" if not self.fused else self._why_not(vars)
+        if why is not None:
+            raise ValueError("vjp: the fused pass does not take this call: " + why)
+        with torch.no_grad():
+            return self._vjp_launch(vars.detach(), cotangent, self._taps(), out, add_to, scale)
 
     def step(self, vars, h, out=None, base=None):
         """``base + h * rhs(vars)`` in the launch that forms the right-hand side; ``base`` defaults to ``vars`` (an explicit
         Euler step), a Runge-Kutta stage passes its own.  ``out``: optional fp32 device tensor of ``vars``' shape to write
-        into; it may be ``base`` itself (an in-place update) but must not overlap ``vars``.  Not differentiable."""
+        into; it may be ``base`` itself (an in-place update) but must not overlap ``vars``.  Not differentiable, unless the
+        module was built with ``backward="fused"``: then it is, with respect to ``vars`` and ``base`` (``d_base = g``,
+        ``d_vars = h * J^T g``; with ``base`` left to ``vars``, ``g + h * J^T g`` in one launch), as long as ``out`` is None."""
         ks = [op.kernel for op in self._operators() if hasattr(op, "kernel")] if self.param_grads else []
         if _dispatch.needs_grad(vars, base, *ks, *([self.gamma] if self.param_grads else [])):
-            raise RuntimeError("step is not differentiable: use vars + h*forward(vars)")
+            if self.backward != "fused" or self.param_grads:
+                raise RuntimeError("step is not differentiable: use vars + h*forward(vars)")
+            if out is not None:
+                raise RuntimeError("step(vars, h, out=...) is not differentiable: leave out to autograd's own tensor")
+            with torch.no_grad():
+                taps = self._taps() if self.fused and self._why_not(vars) is None else None
+                res, why = (None, "fused=False") if not self.fused else self._launch(vars, vars if base is None else base, float(h), taps=taps)
+            if why is None:
+                _set_route("fused:cns_rhs+axpy")
+                return _FusedVjp.apply(res, self, taps, float(h), vars, base)
+            return (vars if base is None else base) + float(h) * self.forward(vars)
         y = vars if base is None else base
         with torch.no_grad():
             res, why = (None, "fused=False") if not self.fused else self._launch(vars, y, float(h), out)

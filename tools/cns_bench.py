@@ -12,7 +12,16 @@ host work): the device time of the launch.  Achieved bytes/s are the algorithmic
 with the epilogue, over that time, next to the copy's 32 B per cell over its time.  (a) and (b) are checked against each
 other before they are timed.  Plain text lines on stdout and in --out.
 
-    python tools/cns_bench.py [--reps 15] [--warmup 3] [--out profiles/cns/cns_bench.txt]
+``--cases vjp`` measures the backward instead, at the same two shapes and interleaved in the same way:
+  (a) the fused VJP launch alone (``libcp_pre_cnsvjp.so``): ``m.vjp(vars, g, out=)`` as the replay of a captured graph;
+  (b) ``rhs.sum().backward()`` through a module built with ``backward="fused"`` (the backward call alone: the forward and
+      the sum are formed before the first event);
+  (c) the same through the default module (``backward="recompute"``, ``_dispatch._Recompute``: the composed expression is
+      run again with grad enabled and autograd walks it backwards);
+  (d) a device copy of the 48 B per cell (a) moves (8 planes read, 4 written): ``dst.copy_(src)`` of a [BS,6,Nx,Ny] tensor.
+(b) and (c) are checked against each other before they are timed.
+
+    python tools/cns_bench.py [--cases forward|vjp] [--reps 15] [--warmup 3] [--out profiles/cns/cns_bench.txt]
 """
 import argparse
 import datetime
@@ -59,12 +68,84 @@ def captured(fn):
     return graph.replay, keep
 
 
+def backward_alone(m, v):
+    """A timed call: ``m(v).sum()`` formed first, then the events around ``backward()`` alone."""
+    def timed():
+        v.grad = None
+        s = m(v).sum()
+        a, b = _ev(), _ev()
+        a.record()
+        s.backward()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+    return timed
+
+
+def vjp_cases(args, dev, g, emit):
+    fused, default = cns.Euler_FV_OS_rhs(CONFIG, dev, backward="fused"), cns.Euler_FV_OS_rhs(CONFIG, dev)
+    for shape in SHAPES:
+        v = torch.rand(*shape, device=dev, generator=g).add_(0.5)
+        cot = torch.randn(*shape, device=dev, generator=g)
+        out = torch.empty_like(v)
+        src = torch.rand(shape[0], 6, shape[2], shape[3], device=dev, generator=g)
+        dst = torch.empty_like(src)
+        x = v.clone().requires_grad_()
+        fused(x).sum().backward()
+        route = cns.last_backward_route()
+        gb = x.grad
+        x.grad = None
+        default(x).sum().backward()
+        gc = x.grad
+        err = max(float((gb[:, c] - gc[:, c]).abs().max() / gc[:, c].abs().max()) for c in range(4))
+        del gb, gc
+        with torch.no_grad():
+            fused.vjp(v, cot, out=out)
+            ga, _ka = captured(lambda: fused.vjp(v, cot, out=out))
+        b, c = backward_alone(fused, x), backward_alone(default, x)
+
+        def event_timed(f):
+            def timed():
+                a, e = _ev(), _ev()
+                a.record()
+                f()
+                e.record()
+                e.synchronize()
+                return a.elapsed_time(e)
+            return timed
+
+        fns = [event_timed(ga), b, c, event_timed(lambda: dst.copy_(src))]
+        names = ("a vjp as graph replay", "b backward, fused", "c backward, recompute", "d device copy 48 B/cell")
+        for _ in range(args.warmup):
+            for f in fns:
+                f()
+        times = [[] for _ in fns]
+        for _ in range(args.reps):
+            for i, f in enumerate(fns):
+                times[i].append(f())
+        res = {n: (sorted(t)[len(t) // 2], min(t), max(t)) for n, t in zip(names, times)}
+        cells = v.numel() // 4
+        emit(f"{list(shape)}: backward route {route}; max channel |fused - recompute| / max = {err:.2e}")
+        for n in names:
+            m, lo, hi = res[n]
+            emit(f"    {n:<24s} {m:8.3f} ms [{lo:.3f}, {hi:.3f}]")
+        ta, tb, tc, td = (res[n][0] for n in names)
+        emit(f"    (c)/(b) = {tc / tb:.2f}x (slowest b {res[names[1]][2]:.3f} ms against fastest c {res[names[2]][1]:.3f} ms); "
+             f"(a)/(d) = {ta / td:.2f}: the launch runs at {td / ta:.2f} of the copy's rate")
+        emit(f"    achieved: (a) 48 B x {cells} cells / replay = {48 * cells / ta / 1e9:.2f} TB/s, copy = {48 * cells / td / 1e9:.2f} TB/s")
+        del v, cot, out, src, dst, x, ga, _ka
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", choices=("forward", "vjp"), default="forward")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cns", "cns_bench.txt"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "cns", "cns_bench.txt" if args.cases == "forward" else "cns_vjp_bench.txt")
     assert torch.cuda.is_available(), "cns_bench needs the MI355X"
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -74,6 +155,14 @@ def main():
         lines.append(s)
         print(s, flush=True)
 
+    if args.cases == "vjp":
+        emit(f"# cns_bench --cases vjp {datetime.date.today().isoformat()} on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; "
+             f"reps {args.reps}, warmup {args.warmup}; median ms [min, max], device events around one call, blocks interleaved")
+        vjp_cases(args, dev, g, emit)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     emit(f"# cns_bench {datetime.date.today().isoformat()} on {torch.cuda.get_device_name(0)}, torch {torch.__version__}; "
          f"reps {args.reps}, warmup {args.warmup}; median ms [min, max], device events around one call, blocks interleaved")
     fused, composed = cns.Euler_FV_OS_rhs(CONFIG, dev), cns.Euler_FV_OS_rhs(CONFIG, dev, fused=False)
