@@ -1,7 +1,7 @@
 // libcp_pre_cns.so (include/cp_pre_cns.h): the right-hand side of the reference's compressible Navier-Stokes module
 // (Active_Learning/CNS.py:6-31) in ONE pass over (rho, u, v, p), with the integrator epilogue out = add_to + step * rhs
 // (gfx950 only).  The expression, its quirks and the contract are stated in the header; this file stands alone (it shares no
-// template with star_march.hip: there is no time march here and no state across launches).
+// template with star_march.h: there is no time march here and no state across launches).
 //
 // The pass.  A workgroup of 256 threads owns a tile of NR = 16 rows x NC = 64 columns of one sample's plane:
 //   * it stages the tile of all four fields in LDS with one halo row above and below and one halo cell left and right
@@ -16,27 +16,13 @@
 // The corner cells of the 3x3 box carry no weight (the host side declines a kernel off the cross).  They are staged and
 // multiplied by zero all the same, so that a NaN or an inf reaches exactly the cells it reaches through the reference's dense
 // F.conv2d, where 0 * inf is NaN: the non-finite footprint of the fused pass is that of the composed route.
-#include "common.h"
-#include "../../include/cp_pre_cns.h"
+#include "cns_common.h"
 
 namespace {
 
-constexpr int NR = PRE_CNS_TILE_ROWS, NC = PRE_CNS_TILE_COLS;
-constexpr int QPR = NC / 4;                            // quads in a tile row
-constexpr int THREADS = 256;
 constexpr int TR = THREADS / QPR;                      // rows the threads cover at once
 constexpr int RPT = NR / TR;                           // quads a thread computes, TR rows apart
-constexpr int LR = NR + 2;                             // staged rows: -1 .. NR
-constexpr int SLOTS = LR * QPR;                        // quads to stage per field
-constexpr int SPT = (SLOTS + THREADS - 1) / THREADS;   // ... per thread
-constexpr int C0 = 4;                                  // tile column j sits at C0 + j of a staged row: quads stay 16-byte aligned
-constexpr int PITCH = NC + 8;                          // left halo at C0 - 1, right halo at C0 + w (w <= NC columns in the grid)
-static_assert(RPT >= 1 && NR == RPT * TR && THREADS >= 2 * LR, "one thread per quad; the halo cells are staged by the first 2 * LR threads");
-
-struct Cross { float c, xm, xp, ym, yp; };             // centre, row -1, row +1, column -1, column +1
-
-// per side: idx >= 0 = the row / column read in place of the one just outside, idx < 0 = the constant val
-struct BC { int xlo, xhi, ylo, yhi; float vxlo, vxhi, vylo, vyhi; };
+static_assert(RPT >= 1 && NR == RPT * TR, "one thread per quad");
 
 struct Args {
     const float *in[4];                                // (batch strides in 64 bits, applied to the workgroup's sample on the scalar
@@ -49,14 +35,14 @@ struct Args {
     long long addB[4];
     int addX[4];
     Cross gx, gy, dx, dy, lap;
-    BC bc;
+    BCInfo bc;
     float gamma, step;
     int X, Y, tilesR, tilesC;
 };
 
 // the cell (gx, gy) of a plane, -1 <= gx <= X, -1 <= gy <= Y, through the boundary mapping.  A corner takes the row side's
 // constant first: BoundaryManager.pad_signal pads the rows last, over the whole padded width
-__device__ __forceinline__ float bc_cell(const float *p, int sX, int gx, int gy, int X, int Y, const BC &bc)
+__device__ __forceinline__ float bc_cell(const float *p, int sX, int gx, int gy, int X, int Y, const BCInfo &bc)
 {
     if (gx < 0) {
         if (bc.xlo < 0) return bc.vxlo;
@@ -276,61 +262,6 @@ __global__ void __launch_bounds__(THREADS) cns_rhs_kernel(const Args a)
     }
 }
 
-// ------------------------------------------------------------------ host side
-bool cross_from_dense9(const float *K, Cross *k)                     // 3x3 kernel, axes (X, Y)
-{
-    if (K[0] != 0.f || K[2] != 0.f || K[6] != 0.f || K[8] != 0.f) return false;
-    *k = Cross{K[4], K[1], K[7], K[3], K[5]};
-    return true;
-}
-
-// pre_bc_t side -> (index to read, constant); n = extent of the axis (the mapping of pre_spatial2d_bc_f32)
-bool bc_side(int mode, float value, int64_t n, bool hi, int *idx, float *val)
-{
-    *val = 0.f;
-    switch (mode) {
-    case PRE_BC_CONSTANT: *idx = -1; *val = value; return true;
-    case PRE_BC_REPLICATE: *idx = hi ? (int)n - 1 : 0; return true;
-    case PRE_BC_PERIODIC: *idx = hi ? 0 : (int)n - 1; return true;
-    case PRE_BC_REFLECT: if (n < 2) return false; *idx = hi ? (int)n - 2 : 1; return true;
-    default: return false;
-    }
-}
-
-struct Span { intptr_t lo, hi; };                                    // byte addresses [lo, hi) a view touches
-
-// false if the view's offsets overflow int64
-bool span_of(const void *ptr, int64_t sB, int64_t sX, int64_t B, int64_t X, int64_t Y, Span *s)
-{
-    int64_t eB, eX;
-    if (__builtin_mul_overflow(sB, B - 1, &eB) || __builtin_mul_overflow(sX, X - 1, &eX)) return false;
-    int64_t lo = 0, hi = Y;
-    if (__builtin_add_overflow(eB < 0 ? lo : hi, eB, eB < 0 ? &lo : &hi)) return false;
-    if (__builtin_add_overflow(eX < 0 ? lo : hi, eX, eX < 0 ? &lo : &hi)) return false;
-    int64_t blo, bhi;
-    if (__builtin_mul_overflow(lo, (int64_t)4, &blo) || __builtin_mul_overflow(hi, (int64_t)4, &bhi)) return false;
-    if (__builtin_add_overflow((int64_t)(intptr_t)ptr, blo, &blo) || __builtin_add_overflow((int64_t)(intptr_t)ptr, bhi, &bhi))
-        return false;
-    s->lo = (intptr_t)blo;
-    s->hi = (intptr_t)bhi;
-    return true;
-}
-
-bool overlaps(const Span &a, const Span &b) { return a.lo < b.hi && b.lo < a.hi; }
-
-// the offsets inside one sample's plane, (X - 1) * sX + Y at the most, are 32-bit in the kernel
-bool plane_fits_int32(int64_t sX, int64_t X, int64_t Y)
-{
-    int64_t e;
-    if (__builtin_mul_overflow(sX, X - 1, &e)) return false;
-    return e > -0x7fffffffLL && e < 0x7fffffffLL - Y;
-}
-
-bool aligned16(const void *ptr, int64_t sB, int64_t sX, int64_t B)
-{
-    return ((uintptr_t)ptr & 15u) == 0 && sX % 4 == 0 && (B == 1 || sB % 4 == 0);
-}
-
 }  // namespace
 
 extern "C" {
@@ -341,48 +272,13 @@ int pre_cns_rhs_f32(const pre_cns_plane_t in[4], const pre_cns_out_t out[4], con
                     const float *K_dx, const float *K_dy, const float *K_lap, const pre_bc_t *bc, float gamma,
                     const pre_cns_plane_t *add_to, float step, int64_t B, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (!in || !out || !K_gx || !K_gy || !K_dx || !K_dy || !K_lap || !bc) return PRE_E_NULL;
-    for (int i = 0; i < 4; ++i)
-        if (!in[i].ptr || !out[i].ptr || (add_to && !add_to[i].ptr)) return PRE_E_NULL;
-    if (B < 1 || X < 1 || Y < 1) return PRE_E_NULL;
-    if (flags != 0) return PRE_E_UNSUPPORTED;
-    if (Y % 4 != 0 || X < 2 || Y < 4) return PRE_E_UNSUPPORTED;
-    for (int i = 0; i < 4; ++i)
-        if (!aligned16(in[i].ptr, in[i].sB, in[i].sX, B) || !aligned16(out[i].ptr, out[i].sB, out[i].sX, B) ||
-            (add_to && !aligned16(add_to[i].ptr, add_to[i].sB, add_to[i].sX, B)))
-            return PRE_E_UNSUPPORTED;
-
     Args a;
-    if (!cross_from_dense9(K_gx, &a.gx) || !cross_from_dense9(K_gy, &a.gy) || !cross_from_dense9(K_dx, &a.dx) ||
-        !cross_from_dense9(K_dy, &a.dy) || !cross_from_dense9(K_lap, &a.lap))
-        return PRE_E_UNSUPPORTED;
-    // top / bottom act on the rows (X), left / right on the columns (Y)
-    if (!bc_side(bc->mode[2], bc->value[2], X, false, &a.bc.xlo, &a.bc.vxlo) || !bc_side(bc->mode[3], bc->value[3], X, true, &a.bc.xhi, &a.bc.vxhi) ||
-        !bc_side(bc->mode[0], bc->value[0], Y, false, &a.bc.ylo, &a.bc.vylo) || !bc_side(bc->mode[1], bc->value[1], Y, true, &a.bc.yhi, &a.bc.vyhi))
-        return PRE_E_RANGE;
-
-    // int32 cell indices with room for the last tile's overhang, one workgroup per tile in a 1-D grid
-    if (B > 0x7fffffff || X > 0x7fffffff - NR || Y > 0x7fffffff - NC) return PRE_E_RANGE;
-    const int64_t tilesR = (X + NR - 1) / NR, tilesC = (Y + NC - 1) / NC;
-    int64_t tiles;
-    if (__builtin_mul_overflow(tilesR, tilesC, &tiles) || __builtin_mul_overflow(tiles, B, &tiles) || tiles > 0x7fffffff)
-        return PRE_E_RANGE;
-
-    Span si[4], so[4], sa[4];
-    for (int i = 0; i < 4; ++i)
-        if (!plane_fits_int32(in[i].sX, X, Y) || !plane_fits_int32(out[i].sX, X, Y) || (add_to && !plane_fits_int32(add_to[i].sX, X, Y)) ||
-            !span_of(in[i].ptr, in[i].sB, in[i].sX, B, X, Y, &si[i]) || !span_of(out[i].ptr, out[i].sB, out[i].sX, B, X, Y, &so[i]) ||
-            (add_to && !span_of(add_to[i].ptr, add_to[i].sB, add_to[i].sX, B, X, Y, &sa[i])))
-            return PRE_E_RANGE;
-    // add_to is either out itself, channel by channel (a thread reads its cell before it writes it), or somewhere else
-    bool in_place = add_to != nullptr;
-    for (int i = 0; add_to && i < 4; ++i)
-        in_place = in_place && add_to[i].ptr == out[i].ptr && (B == 1 || add_to[i].sB == out[i].sB) && add_to[i].sX == out[i].sX;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            if (overlaps(so[i], si[j])) return PRE_E_RANGE;           // a tile's halo is another tile's output
-            if (add_to && !in_place && overlaps(so[i], sa[j])) return PRE_E_RANGE;
-        }
+    const pre_cns_plane_t *rd[1] = {in};
+    const float *K[5] = {K_gx, K_gy, K_dx, K_dy, K_lap};
+    Cross *k[5] = {&a.gx, &a.gy, &a.dx, &a.dy, &a.lap};
+    unsigned grid;
+    const int rc = cns_check(rd, 1, out, add_to, K, k, bc, &a.bc, B, X, Y, flags, &a.tilesR, &a.tilesC, &grid);
+    if (rc) return rc;
 
     for (int i = 0; i < 4; ++i) {
         a.in[i] = in[i].ptr; a.inB[i] = in[i].sB; a.inX[i] = (int)in[i].sX;
@@ -393,9 +289,9 @@ int pre_cns_rhs_f32(const pre_cns_plane_t in[4], const pre_cns_out_t out[4], con
     }
     a.gamma = gamma;
     a.step = step;
-    a.X = (int)X; a.Y = (int)Y; a.tilesR = (int)tilesR; a.tilesC = (int)tilesC;
+    a.X = (int)X; a.Y = (int)Y;
 
-    hipLaunchKernelGGL(cns_rhs_kernel, dim3((unsigned)tiles), dim3(THREADS), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(cns_rhs_kernel, dim3(grid), dim3(THREADS), 0, as_stream(stream), a);
     PRE_LAUNCH_CHECK();
     return PRE_OK;
 }

@@ -26,6 +26,7 @@
 // (dt,dx,dy) order.  The march takes any sB, sX, sY there, as it takes any sB, sT, sX of a Y-fastest view: the cropped view
 // of the reference's scripts, field[:, 0, 1:-1, 1:-1, 1:-1].permute(0, 3, 1, 2), is read where it lies.
 #include "common.h"
+#include "host_checks.h"
 #include "../../include/cp_pre_wgrad.h"
 
 namespace {
@@ -54,7 +55,7 @@ struct WMap {
 };
 
 // (4-byte aligned float4 accesses: gfx950 runs with unaligned access enabled and the compiler still emits one
-// global_load_dwordx4, so pitched and offset rows stream through the same code - as star_march.hip)
+// global_load_dwordx4, so pitched and offset rows stream through the same code - as star_march.h)
 struct __attribute__((aligned(4))) F4u { float x, y, z, w; };
 
 // the cells col .. col+3 of a row of Y cells; only the elements lo <= j < hi, and only those inside the row, are read
@@ -254,21 +255,6 @@ __global__ void __launch_bounds__(256) wgrad_final_kernel(const double *partial,
 }
 
 // ------------------------------------------------------------------ host side
-struct Span { uintptr_t lo, hi; };
-
-Span span_of(const void *ptr, const int64_t s[4], const int64_t n[4])
-{
-    int64_t lo = 0, hi = 0;
-    for (int i = 0; i < 4; ++i) {
-        const int64_t e = s[i] * (n[i] - 1);
-        if (e < 0) lo += e; else hi += e;
-    }
-    const uintptr_t base = (uintptr_t)ptr;
-    return {base + lo * 4, base + hi * 4 + 4};
-}
-
-bool overlaps(const Span &a, const Span &b) { return a.lo < b.hi && b.lo < a.hi; }
-
 bool y_fastest(const pre_field_t *f) { return f->sY == 1; }
 bool nt_fastest(const pre_field_t *f) { return f->sT == 1; }
 
@@ -322,8 +308,8 @@ int pre_wgrad_stencil3d_f32(const pre_field_t *g, const pre_field_t *x, const pr
     const int64_t n[4] = {B, T, X, Y};
     for (int i = 0; i < nf; ++i) {
         const int64_t s[4] = {fs[i]->sB, fs[i]->sT, fs[i]->sX, fs[i]->sY};
-        const Span f = span_of(fs[i]->ptr, s, n);
-        if (overlaps(sk, f) || overlaps(sw, f)) return PRE_E_SHAPE;
+        Span f;
+        if (!span_of(fs[i]->ptr, s, n, 0, &f) || overlaps(sk, f) || overlaps(sw, f)) return PRE_E_SHAPE;
     }
 
     // the kernel's axes: (T,X,Y) as given, or - Nt-fastest - the relabelled array [B,X,Y,T] with the extents permuted

@@ -1,7 +1,7 @@
 // pair_march.hip - data-driven residual scores d = r(a) - r(b) in one streaming pass (libcp_pre_pair.so,
 // include/cp_pre_pair.h).
 //
-// The march of star_march.hip (included for its templates only) evaluates a functor of up to MAXF = 6 field views.  Paired<Fn> is a functor of 2*Fn::F views:
+// The march of star_march.h evaluates a functor of up to MAXF = 6 field views.  Paired<Fn> is a functor of 2*Fn::F views:
 // views [0, F) are the truth set, [F, 2F) the prediction set, and eval = Fn::eval(first half) - Fn::eval(second half).
 // Every layout mode of the march (contiguous, vars[:, i] views, the Nt-fastest relabelling, the flat form, the general
 // star) and every flag (ABS after the subtraction, INTERIOR_T, OUT_INTERIOR_T, HALO_X) comes with it unchanged.
@@ -13,8 +13,7 @@
 #ifndef PRE_PAIR_PART
 #error "PRE_PAIR_PART: 1 or 2 (see the Makefile)"
 #endif
-#define PRE_STAR_MARCH_TEMPLATES_ONLY
-#include "star_march.hip"
+#include "star_march.h"
 #include "../../include/cp_pre_pair.h"
 
 namespace {
@@ -86,33 +85,19 @@ __global__ void pair_star_tail_kernel(const Geom g, const Star s, int y0, long l
     g.out[(long long)b * g.oB + (long long)t * g.oT + (long long)x * g.oX + y] = d;
 }
 
-// Byte range [lo, hi) a strided view addresses (rows -1 and X included under PRE_FLAG_HALO_X for an input).
-struct Span { uintptr_t lo, hi; };
-Span span_of(const void *ptr, const int64_t *s, const int64_t *n, int nd, int64_t halo_x_stride)
-{
-    intptr_t lo = 0, hi = 0;
-    for (int d = 0; d < nd; ++d) {
-        const intptr_t e = (intptr_t)s[d] * (intptr_t)(n[d] - 1);
-        if (e < 0) lo += e; else hi += e;
-    }
-    const intptr_t h = halo_x_stride < 0 ? -halo_x_stride : halo_x_stride;
-    lo -= h; hi += h;
-    const uintptr_t base = (uintptr_t)ptr;
-    return {base + lo * 4, base + hi * 4 + 4};
-}
-
-// PRE_E_SHAPE if `out` overlaps an input view
+// PRE_E_SHAPE if `out` overlaps an input view (rows -1 and X included under PRE_FLAG_HALO_X for an input), or if a view's
+// offsets leave int64
 int check_disjoint(const pre_field_t *const *fs, int nf, const pre_out_t *out, int64_t B, int64_t T, int64_t X, int64_t Y,
                    int flags)
 {
     const int64_t n[4] = {B, T, X, Y};
     const int64_t no[4] = {B, (flags & PRE_FLAG_OUT_INTERIOR_T) ? T - 2 : T, X, Y};
     const int64_t so[4] = {out->sB, out->sT, out->sX, out->sY};
-    const Span o = span_of(out->ptr, so, no, 4, 0);
+    Span o, f;
+    if (!span_of(out->ptr, so, no, 0, &o)) return PRE_E_SHAPE;
     for (int i = 0; i < nf; ++i) {
         const int64_t s[4] = {fs[i]->sB, fs[i]->sT, fs[i]->sX, fs[i]->sY};
-        const Span f = span_of(fs[i]->ptr, s, n, 4, (flags & PRE_FLAG_HALO_X) ? fs[i]->sX : 0);
-        if (o.lo < f.hi && f.lo < o.hi) return PRE_E_SHAPE;
+        if (!span_of(fs[i]->ptr, s, n, (flags & PRE_FLAG_HALO_X) ? fs[i]->sX : 0, &f) || overlaps(o, f)) return PRE_E_SHAPE;
     }
     return PRE_OK;
 }
@@ -126,24 +111,6 @@ int check_sets(const pre_field_t *const *fs, int nf, const pre_out_t *out, int64
         if (!fs[i] || !fs[i]->ptr) return PRE_E_NULL;
     if ((flags & PRE_FLAG_OUT_INTERIOR_T) && T < 3) return PRE_E_UNSUPPORTED;
     return check_disjoint(fs, nf, out, B, T, X, Y, flags);
-}
-
-// the star of a tap list (3 offsets per tap), or false if a tap is off the 7-point star; PRE_E_SHAPE via *rc
-bool star_of_taps(const float *w, const int32_t *off, int ntaps, Star *s, int *rc)
-{
-    float s7[7] = {0, 0, 0, 0, 0, 0, 0};
-    bool star = true;
-    *rc = PRE_OK;
-    for (int i = 0; i < ntaps; ++i) {
-        const int dt = off[3 * i], dx = off[3 * i + 1], dy = off[3 * i + 2];
-        if (dt < -3 || dt > 3 || dx < -3 || dx > 3 || dy < -3 || dy > 3) { *rc = PRE_E_SHAPE; return false; }
-        const int nz = (dt != 0) + (dx != 0) + (dy != 0);
-        if (nz > 1 || dt < -1 || dt > 1 || dx < -1 || dx > 1 || dy < -1 || dy > 1) { star = false; continue; }
-        const int slot = dt ? (dt < 0 ? 1 : 2) : dx ? (dx < 0 ? 3 : 4) : dy ? (dy < 0 ? 5 : 6) : 0;
-        s7[slot] += w[i];
-    }
-    *s = Star{s7[0], s7[1], s7[2], s7[3], s7[4], s7[5], s7[6]};
-    return star;
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // residual_vjp.hip - vector-Jacobian products of the PDE residuals and the deterministic sum of squares of a residual
 // (libcp_pre_vjp.so, include/cp_pre_vjp.h): what a physics-informed loss mean(r^2) needs for its backward pass.
 //
-// star_march.hip is included for its templates only (Star, Nbr, apply<>, the lane shifts, the LDS-only barrier, pick_tseg).
-// Its march has ONE output stream and reads its inputs as stored; the gradient of NS momentum has THREE outputs, and the
+// The march templates are star_march.h's (Star, Nbr, apply<>, the lane shifts, the LDS-only barrier, pick_tseg).
+// The march of that header has ONE output stream and reads its inputs as stored; the gradient of NS momentum has THREE outputs, and the
 // incoming gradient g has to be masked (the loss averages over the cropped interior) and scaled on load.  Hence a march of
 // its own here, same structure: a workgroup of NR x TYQ threads owns NR rows x 4*TYQ columns of one sample and marches over
 // t; every thread keeps planes t-1, t, t+1 (and the in-flight t+2) of its own quad per input stream in registers; the
@@ -12,16 +12,13 @@
 // scaled copy of the residual ever exists in memory.  Widths that are no multiple of 4 are handled in the same launch: the
 // last quad of a row loads and stores element by element.
 //
-// With D(f)(x) = sum_k w_k f(x+k) (zero padding), D^T(g)(x) = sum_k w_k g(x-k): the same star with mirrored taps.  Every
-// functor below gets its stars already mirrored and folded with their scalar factors (host, in double, rounded once).
-#define PRE_STAR_MARCH_TEMPLATES_ONLY
-#include "star_march.hip"
-#include "../../include/cp_pre_vjp.h"
+// The functors of the linear operators and of NS momentum, with the folding of their stars, are vjp_functors.h's (shared
+// with vjp_flat.hip); the Burgers functor has its only user here.
+#include "vjp_functors.h"
 
 namespace {
 
 constexpr int VJP_MAXIN = 3, VJP_MAXOUT = 3;
-enum { CROP_T = 1, CROP_X = 2, CROP_Y = 4 };
 
 struct VGeom {
     const float *f[VJP_MAXIN];
@@ -36,29 +33,7 @@ struct VGeom {
     const float *dev_scale;      // ... times this device scalar, if given (the upstream gradient of loss.backward())
 };
 
-__device__ __forceinline__ float4 mul4(const float4 &a, const float4 &b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ Nbr mul_nbr(const Nbr &a, const Nbr &b)
-{
-    return Nbr{mul4(a.c, b.c), mul4(a.tm, b.tm), mul4(a.tp, b.tp), mul4(a.xm, b.xm), mul4(a.xp, b.xp), mul4(a.ym, b.ym), mul4(a.yp, b.yp)};
-}
-
-// ------------------------------------------------------------------ the functors: n[0] is gg, r[] the gradients
-struct VjpLinear1 {      // df = S^T(gg)
-    static constexpr int FIN = 1, FOUT = 1;
-    struct Params { Star st; };
-    static __device__ __forceinline__ void eval(const Nbr (&n)[1], const Params &p, float4 (&r)[1]) { r[0] = apply<K_STAR7>(p.st, n[0]); }
-};
-
-struct VjpLinear2 {      // r = Sa(a) + ratio*Sb(b):  da = Sa^T(gg), db = ratio*Sb^T(gg)  (ratio folded into bt)
-    static constexpr int FIN = 1, FOUT = 2;
-    struct Params { Star at, bt; };
-    static __device__ __forceinline__ void eval(const Nbr (&n)[1], const Params &p, float4 (&r)[2])
-    {
-        r[0] = apply<K_STAR7>(p.at, n[0]);
-        r[1] = apply<K_STAR7>(p.bt, n[0]);
-    }
-};
-
+// ------------------------------------------------------------------ the functor of Burgers: n[0] is gg, r[] the gradient
 // r = dx*D_t(u) + dt*u*D_x(u) - nu*c3*D_xx(u):  du = (dx*D_t^T - nu*c3*D_xx^T)(gg) + dt*gg*D_x(u) + dt*D_x^T(gg*u)
 struct VjpBurgers {
     static constexpr int FIN = 2, FOUT = 1;
@@ -67,25 +42,6 @@ struct VjpBurgers {
     {
         const Nbr gu = mul_nbr(n[0], n[1]);
         r[0] = apply<K_STAR7>(p.lin, n[0]) + p.dt * (mul4(n[0].c, apply<K_STAR7>(p.Dx, n[1])) + apply<K_STAR7>(p.DxT, gu));
-    }
-};
-
-// NS momentum, a = dx*dy, b = dt*dy, c = dt*dx, n = nu*dt (cp_pre_vjp.h):
-//   du = (a*Dt^T - n*L^T)(gg) + gg*(b*Dx(u) + c*Dx(v)) + b*Dx^T(gg*u) + c*Dy^T(gg*v)
-//   dv = (a*Dt^T - n*L^T)(gg) + gg*(c*Dy(u) + b*Dy(v)) + c*Dx^T(gg*u) + b*Dy^T(gg*v)
-//   dp = (b*Dx^T + c*Dy^T)(gg)
-struct VjpNSMomentum {
-    static constexpr int FIN = 3, FOUT = 3;
-    struct Params { Star lin, pT, Dx, Dy, DxT, DyT; float b, c; };     // lin = a*Dt^T - n*L^T, pT = b*Dx^T + c*Dy^T
-    static __device__ __forceinline__ void eval(const Nbr (&n)[3], const Params &p, float4 (&r)[3])
-    {
-        const Nbr &g = n[0], &u = n[1], &v = n[2];
-        const Nbr gu = mul_nbr(g, u), gv = mul_nbr(g, v);
-        const float4 lin = apply<K_STAR7>(p.lin, g);
-        const float4 X = apply<K_STAR7>(p.DxT, gu), Yv = apply<K_STAR7>(p.DyT, gv);
-        r[0] = lin + mul4(g.c, p.b * apply<K_STAR7>(p.Dx, u) + p.c * apply<K_STAR7>(p.Dx, v)) + p.b * X + p.c * Yv;
-        r[1] = lin + mul4(g.c, p.c * apply<K_STAR7>(p.Dy, u) + p.b * apply<K_STAR7>(p.Dy, v)) + p.c * X + p.b * Yv;
-        r[2] = apply<K_STAR7>(p.pT, g);
     }
 };
 
@@ -254,15 +210,6 @@ __global__ void __launch_bounds__(NR *TYQ) vjp_march_kernel(const VGeom g, const
 }
 
 // ------------------------------------------------------------------ host side
-Star mirrored(const Star &s) { return Star{s.c, s.tp, s.tm, s.xp, s.xm, s.yp, s.ym}; }
-
-// ca*a + cb*b, folded in double and rounded once
-Star combine(double ca, const Star &a, double cb, const Star &b)
-{
-    auto m = [&](float x, float y) { return (float)(ca * (double)x + cb * (double)y); };
-    return Star{m(a.c, b.c), m(a.tm, b.tm), m(a.tp, b.tp), m(a.xm, b.xm), m(a.xp, b.xp), m(a.ym, b.ym), m(a.yp, b.yp)};
-}
-
 template <class Fn, int NR, int TYQ>
 int launch_vjp_tiled(VGeom &g, const typename Fn::Params &prm, hipStream_t st)
 {
@@ -272,7 +219,7 @@ int launch_vjp_tiled(VGeom &g, const typename Fn::Params &prm, hipStream_t st)
     long long tiles = (long long)g.B * g.nXT * g.nYT;
     static const int per_cu = resident_per_cu(vjp_march_kernel<Fn, NR, TYQ>, NR * TYQ);
     int tSeg = pick_tseg(tiles, g.T, (long long)per_cu * chip_cus());
-    if (g.tfree && tSeg > TFREE_TSEG) tSeg = TFREE_TSEG;          // (segments cost no window prologue then: star_march.hip)
+    if (g.tfree && tSeg > TFREE_TSEG) tSeg = TFREE_TSEG;          // (segments cost no window prologue then: star_march.h)
     g.tSeg = tSeg;
     g.nTSeg = (g.T + tSeg - 1) / tSeg;
     tiles *= g.nTSeg;
@@ -289,47 +236,18 @@ int launch_vjp(VGeom &g, const typename Fn::Params &prm, hipStream_t st)
     return launch_vjp_tiled<Fn, 32, 16>(g, prm, st);                     // narrow grids: 32 rows x 64 columns
 }
 
-// Byte range [lo, hi) a strided view addresses
-struct Span { uintptr_t lo, hi; };
-Span span_of(const void *ptr, const int64_t *s, const int64_t *n)
-{
-    intptr_t lo = 0, hi = 0;
-    for (int d = 0; d < 4; ++d) {
-        const intptr_t e = (intptr_t)s[d] * (intptr_t)(n[d] - 1);
-        if (e < 0) lo += e; else hi += e;
-    }
-    const uintptr_t base = (uintptr_t)ptr;
-    return {base + lo * 4, base + hi * 4 + 4};
-}
-
-// Null / empty / layout / overlap checks of everything the entry points hand to a kernel, and the geometry.  An output
-// whose bounding byte range overlaps that of an input is PRE_E_SHAPE (as pair_march.hip); the outputs among themselves may
-// interleave (the slots of one stacked gradient tensor) but may not start at the same address.
+// Null / empty / layout / overlap checks of everything the entry points hand to a kernel, and the geometry.  Views that
+// are not disjoint (vjp_functors.h) are PRE_E_SHAPE, as in pair_march.hip.
 int prepare_vjp(VGeom &g, const pre_field_t *const *fs, int nf, const pre_out_t *const *os, int no, int64_t B, int64_t T,
                 int64_t X, int64_t Y, int crop, float host_scale, const float *dev_scale)
 {
-    if (B <= 0 || T <= 0 || X <= 0 || Y <= 0) return PRE_E_NULL;
-    for (int i = 0; i < nf; ++i)
-        if (!fs[i] || !fs[i]->ptr) return PRE_E_NULL;
-    for (int k = 0; k < no; ++k)
-        if (!os[k] || !os[k]->ptr) return PRE_E_NULL;
+    if (!vjp_views_given(fs, nf, os, no, B, T, X, Y)) return PRE_E_NULL;
     if (B > 0x7fffffff || T > 0x7fffffff || X > 0x7fffffff || Y > 0x7fffffff - 8) return PRE_E_SHAPE;
     for (int i = 0; i < nf; ++i)
         if (fs[i]->sY != 1) return PRE_E_UNSUPPORTED;              // (Nt-fastest views and the like: the caller falls back)
     for (int k = 0; k < no; ++k)
         if (os[k]->sY != 1) return PRE_E_UNSUPPORTED;
-    const int64_t n[4] = {B, T, X, Y};
-    for (int k = 0; k < no; ++k) {
-        const int64_t so[4] = {os[k]->sB, os[k]->sT, os[k]->sX, os[k]->sY};
-        const Span o = span_of(os[k]->ptr, so, n);
-        for (int i = 0; i < nf; ++i) {
-            const int64_t s[4] = {fs[i]->sB, fs[i]->sT, fs[i]->sX, fs[i]->sY};
-            const Span f = span_of(fs[i]->ptr, s, n);
-            if (o.lo < f.hi && f.lo < o.hi) return PRE_E_SHAPE;
-        }
-        for (int j = 0; j < k; ++j)
-            if (os[j]->ptr == os[k]->ptr) return PRE_E_SHAPE;
-    }
+    if (!vjp_views_disjoint(fs, nf, os, no, B, T, X, Y)) return PRE_E_SHAPE;
     for (int i = 0; i < VJP_MAXIN; ++i) {
         const bool on = i < nf;
         g.f[i] = on ? fs[i]->ptr : nullptr;
@@ -349,30 +267,6 @@ int prepare_vjp(VGeom &g, const pre_field_t *const *fs, int nf, const pre_out_t 
 }
 
 bool has_t(const Star &s) { return s.tm != 0.f || s.tp != 0.f; }
-
-// the star of a tap list (3 offsets per tap); false if a tap is off the 7-point star; PRE_E_SHAPE via *rc
-bool star_of_taps(const float *w, const int32_t *off, int ntaps, Star *s, int *rc)
-{
-    float s7[7] = {0, 0, 0, 0, 0, 0, 0};
-    bool star = true;
-    *rc = PRE_OK;
-    for (int i = 0; i < ntaps; ++i) {
-        const int dt = off[3 * i], dx = off[3 * i + 1], dy = off[3 * i + 2];
-        if (dt < -3 || dt > 3 || dx < -3 || dx > 3 || dy < -3 || dy > 3) { *rc = PRE_E_SHAPE; return false; }
-        const int nz = (dt != 0) + (dx != 0) + (dy != 0);
-        if (nz > 1 || dt < -1 || dt > 1 || dx < -1 || dx > 1 || dy < -1 || dy > 1) { star = false; continue; }
-        const int slot = dt ? (dt < 0 ? 1 : 2) : dx ? (dx < 0 ? 3 : 4) : dy ? (dy < 0 ? 5 : 6) : 0;
-        s7[slot] += w[i];
-    }
-    *s = Star{s7[0], s7[1], s7[2], s7[3], s7[4], s7[5], s7[6]};
-    return star;
-}
-
-int crop_of(int flags, bool view3d)
-{
-    if (!(flags & PRE_VJP_CROP)) return 0;
-    return view3d ? (CROP_X | CROP_Y) : (CROP_T | CROP_X | CROP_Y);     // [B,T,X] is marched as [1,B,T,X]
-}
 
 // ------------------------------------------------------------------ sum(m * r^2): two stages, fixed order, fp64
 constexpr int SUMSQ_WAVES = 4;

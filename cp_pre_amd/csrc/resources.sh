@@ -2,6 +2,8 @@
 # Compact per-kernel resource table (VGPR / spill / scratch / LDS / occupancy) from hipcc remarks.
 # HIPCC_EXTRA: flags the Makefile adds for an object (vjp_flat.hip: HIPCC_EXTRA='-mllvm -disable-vector-combine').
 cd "$(dirname "$0")"
+# A file of this directory that includes star_march.h (star_march.hip, pair_march.hip, residual_vjp.hip, screen_*.hip,
+# vjp_flat.hip) lists the instantiations of that header's kernels it launches beside its own.
 for f in "${@:-star_march.hip calib.hip stencil_generic.hip}"; do
   for src in $f; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage $HIPCC_EXTRA -c $src -o /dev/null 2>&1 |

@@ -2,17 +2,16 @@
 // (libcp_pre_screenflat.so, include/cp_pre_screenflat.h): per sample, max |r| / m and the number of cells with
 // |r| <= q_k * m at up to 16 levels, in the launch that evaluates the residual r, for fields whose memory is [B,Nx,Ny,Nt].
 //
-// star_march.hip is included for its templates only (Star, Nbr, the functors with their Staged / XMASK masks, the lane
+// The march templates are star_march.h's (Star, Nbr, the functors with their Staged / XMASK masks, the lane
 // shifts, the LDS-only barrier, the buffer descriptors, pick_tseg).  The march below is flat_march_kernel's up to Fn::eval:
-// the kernel axes are relabelled as star_march.hip's prepare() relabels them for an Nt-fastest view (marched axis = Nx,
+// the kernel axes are relabelled as star_march.h's prepare() relabels them for an Nt-fastest view (marched axis = Nx,
 // x = Ny, y = Nt), Ny and Nt are merged into one row of L = Ny*Nt cells, a workgroup owns a chunk of that row of ONE sample
 // and marches a segment of Nx with planes t-1, t, t+1 and the in-flight t+2 of its own quads in registers.  x-neighbours
 // are Nt cells back / ahead in the merged row, y-neighbours the adjacent cell, masked at row ends.  Only the fields a
 // functor reads x-neighbours of go through LDS (halo: ceil(Nt/4) quads per side); the MHD functors stage nothing and run
 // without LDS and without a barrier, NS momentum stages u and v.
 //
-// In place of the store comes screen_march.hip's end of a plane (restated below: that file is a translation unit of
-// libcp_pre_screen.so): the crop is a select, the score uses the guarded divide of the joint score pass, hw = q_k * m is one
+// In place of the store comes screen_march.hip's end of a plane (screen_plane.h): the crop is a select, the score uses the guarded divide of the joint score pass, hw = q_k * m is one
 // fp32 multiply with contraction off by pragma (the rest of this file keeps star_march.o's flags, so that the functors
 // round as the residual pass does), the counts go compare -> wave mask -> population count -> scalar add.  Marched planes
 // outside the crop are not evaluated.  Counted-ness is per LOGICAL cell: a merged-row position m is (y, t) = (m / Nt,
@@ -23,19 +22,16 @@
 // The modulation m[T,X,Y] with memory [X,Y,T] is one more float4 stream in the same merged order, loaded only by lanes
 // with a counted cell and only for counted planes.
 //
-// The split (restated in tests/screenflat_helpers.py, which names the test seams from it):
+// The split (tests/screenflat_helpers.py states it again and names the test seams from it):
 //   chunk   flat_chunk(): 512 quads of the merged row per workgroup, or 448 ... 256 when that saves FLAT_NT_GAIN per cent
 //           of chunks x (chunk + staged halo quads); the staged halo is 2 * min(32, ceil(Nt/4)) quads for a functor that
 //           stages a field, none otherwise (launch_flat's rule);
 //   march   pick_tseg(B * chunks, Nx, resident workgroups): the marched axis in segments of tSeg planes.
-#define PRE_STAR_MARCH_TEMPLATES_ONLY
-#include "star_march.hip"
+#include "screen_plane.h"
 #include "../../include/cp_pre_screenflat.h"
 
 namespace {
 
-static_assert(PRE_SCREEN_MAX_LEVELS == 16, "the level loop of flat_epilogue is unrolled 16 times");
-constexpr int NKMAX = PRE_SCREEN_MAX_LEVELS;
 constexpr int FLAT_NW = FLAT_NT / 64;        // most waves per workgroup
 
 // Kernel axes: T = the marched axis (logical Nx), X = logical Ny, Y = logical Nt; a plane is one row of X * Y cells.
@@ -52,48 +48,6 @@ struct FGeom {
     int tSeg, nTSeg, nCh;
     int cT, cX, cY, nk;                  // cells per side left out of the counted region, on the kernel's axes
 };
-
-// screen_march.hip's score_update (calib.hip's js_update), restated: the running maximum m of av / sv, bitwise what
-// dividing every element gives; only a candidate that can raise the maximum pays for the IEEE division.
-__device__ __forceinline__ void score_update(float av, float sv, float &m, float &thr, bool &nan)
-{
-    if (!(av <= thr * sv) || sv < 1.17549435e-38f) {
-        const float qt = av / sv;
-        if (qt != qt) nan = true;
-        else if (qt > m) { m = qt; thr = m * 0.99999905f; }
-    }
-}
-
-// The end of one plane: screen_march.hip's screen_plane, restated.  No fma contraction in here: hw = q * m rounds as
-// coverage_levels.o's product does, whatever the flags of the rest of this file (those of star_march.o).
-__device__ __forceinline__ void flat_epilogue(const float4 &r, const float4 &mm, const bool (&keep)[4], int nk,
-                                              const float (&qk)[NKMAX], unsigned int (&cnt)[NKMAX], float &m, float &thr, bool &nan)
-{
-#pragma clang fp contract(off)
-    const float rv[4] = {r.x, r.y, r.z, r.w}, mv[4] = {mm.x, mm.y, mm.z, mm.w};
-    float ac[4], sv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float a = fabsf(rv[j]);
-        // a cell outside the counted region: |r| = 0 over m = 1 for the score (never a candidate), NaN for the counts
-        // (outside at every level) - selects, so that whatever it holds stays where it is
-        sv[j] = keep[j] ? mv[j] : 1.0f;
-        score_update(keep[j] ? a : 0.0f, sv[j], m, thr, nan);
-        ac[j] = keep[j] ? a : __builtin_nanf("");
-    }
-#pragma unroll
-    for (int k = 0; k < NKMAX; ++k) {
-        if (k < nk) {                                        // (wave-uniform)
-            unsigned int c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float hw = qk[k] * sv[j];
-                c += (unsigned int)__popcll(__builtin_amdgcn_fcmpf(ac[j], hw, 5));      // 5: ordered <= (NaN: outside)
-            }
-            cnt[k] += c;
-        }
-    }
-}
 
 // Waves per SIMD the register allocator leaves room for.  The forward pass caps NS momentum in this layout at 128
 // registers (NSMomentum::MIN_WAVES, a few dwords spilled); with the epilogue's live values that cap would mean scratch inside
@@ -262,7 +216,7 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
             n[i].yp = make_float4(rok[0] ? C[i].y : 0.f, rok[1] ? C[i].z : 0.f, rok[2] ? C[i].w : 0.f, rok[3] ? rgt : 0.f);
         }
         const float4 r = Fn::eval(n, prm);
-        flat_epilogue(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+        screen_plane(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
     };
 
     float4 w0[F], w1[F], w2[F], w3[F], md0, md1;
@@ -306,17 +260,6 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
 }
 
 // ------------------------------------------------------------------ host side
-// launch_flat's chunk rule: 512 quads per workgroup, or 448 / 384 / 320 / 256 when that leaves fewer idle lanes in the row's
-// last chunk; cost of a row = chunks x (quads + the halo quads staged per chunk); ties go to the wider chunk
-int flat_chunk(long long quads, int Ty, bool staged)
-{
-    const int halo = staged ? 2 * ((Ty + 3) / 4 < FLAT_H ? (Ty + 3) / 4 : FLAT_H) : 0;
-    int nt = staged ? FLAT_NT : FLAT_NOLDS_NT;
-    for (int c = nt - 64; c >= 256; c -= 64)
-        if ((quads + c - 1) / c * (c + halo) * 100 < (quads + nt - 1) / nt * (nt + halo) * (100 - FLAT_NT_GAIN)) nt = c;
-    return nt;
-}
-
 template <class Fn>
 int launch_screen_flat(FGeom &g, const typename Fn::Params &prm, hipStream_t st)
 {
@@ -325,20 +268,11 @@ int launch_screen_flat(FGeom &g, const typename Fn::Params &prm, hipStream_t st)
     const long long quads = (long long)g.X * g.Y / 4;
     const int nt = flat_chunk(quads, g.Y, Staged<Fn>::count > 0);
     g.nCh = (int)((quads + nt - 1) / nt);
-    long long tiles = (long long)g.B * g.nCh;
-    // (by chunk width; 0 = not asked yet.  Host threads may race to fill a slot: they write the same value)
-    static std::atomic<int> per_cu[FLAT_NT / 64 + 1] = {};
-    int occ = per_cu[nt / 64].load(std::memory_order_relaxed);
-    if (!occ) {
-        occ = resident_per_cu(screen_flat_kernel<Fn>, nt);
-        per_cu[nt / 64].store(occ, std::memory_order_relaxed);
-    }
-    const int tSeg = pick_tseg(tiles, g.T, (long long)occ * chip_cus());
-    g.tSeg = tSeg;
-    g.nTSeg = (g.T + tSeg - 1) / tSeg;
-    tiles *= g.nTSeg;
-    if (tiles <= 0 || tiles * nt > 0xffffffffLL) return PRE_E_SHAPE;       // the dispatch packet counts work-items in 32 bits
-    hipLaunchKernelGGL((screen_flat_kernel<Fn>), dim3((unsigned)tiles), dim3(nt), 0, st, g, prm);
+    static std::atomic<int> per_cu[FLAT_NT / 64 + 1] = {};         // (by chunk width)
+    unsigned grid;
+    const int rc = flat_split(screen_flat_kernel<Fn>, nt, per_cu, g, (long long)g.B * g.nCh, g.T, &grid);
+    if (rc) return rc;
+    hipLaunchKernelGGL((screen_flat_kernel<Fn>), dim3(grid), dim3(nt), 0, st, g, prm);
     PRE_LAUNCH_CHECK();
     return PRE_OK;
 }
@@ -357,13 +291,8 @@ int launch_screen_flat_mode(int mode, FGeom &g, const P &prm, hipStream_t st)
 int prepare_flat(FGeom &g, const pre_field_t *const *fs, int nf, const pre_screenflat_t *s, int64_t B, int64_t T, int64_t X,
                  int64_t Y, int flags)
 {
-    if (!s || !s->q || !s->score || !s->count || B <= 0 || T <= 0 || X <= 0 || Y <= 0) return PRE_E_NULL;
-    for (int i = 0; i < nf; ++i)
-        if (!fs[i] || !fs[i]->ptr) return PRE_E_NULL;
-    if (s->nk < 1 || s->nk > PRE_SCREEN_MAX_LEVELS || s->ct < 0 || s->cx < 0 || s->cy < 0) return PRE_E_RANGE;
-    if (s->count_ld < B) return PRE_E_NULL;
-    if (B > 0x7fffffff || T > 0x7fffffff || X > 0x7fffffff || Y > 0x7fffffff) return PRE_E_SHAPE;
-    if ((double)T * (double)X * (double)Y >= 4294967296.0) return PRE_E_SHAPE;           // the counts are 32-bit
+    const int rc = screen_args(fs, nf, s, NKMAX, B, T, X, Y, 0);
+    if (rc) return rc;
     if (flags & ~PRE_FLAG_INTERIOR_T) return PRE_E_UNSUPPORTED;                          // (PRE_FLAG_HALO_X among them)
     // the layout pre_residual_* takes its flat form on after relabelling: T contiguous, Y's stride == T, a short T
     if (T >= FLAT_MAX_Y || Y <= 1 || (Y * T) % 4 != 0) return PRE_E_UNSUPPORTED;
@@ -396,25 +325,6 @@ void relabel_stars(Star *const *stars, int n)
     }
 }
 
-// screen_march.hip's screen_star_of_taps, restated: the star of a tap list (3 offsets per tap); false if a tap is off the
-// 7-point star; PRE_E_SHAPE via *rc
-bool flat_star_of_taps(const float *w, const int32_t *off, int ntaps, Star *s, int *rc)
-{
-    float s7[7] = {0, 0, 0, 0, 0, 0, 0};
-    bool star = true;
-    *rc = PRE_OK;
-    for (int i = 0; i < ntaps; ++i) {
-        const int dt = off[3 * i], dx = off[3 * i + 1], dy = off[3 * i + 2];
-        if (dt < -3 || dt > 3 || dx < -3 || dx > 3 || dy < -3 || dy > 3) { *rc = PRE_E_SHAPE; return false; }
-        const int nz = (dt != 0) + (dx != 0) + (dy != 0);
-        if (nz > 1 || dt < -1 || dt > 1 || dx < -1 || dx > 1 || dy < -1 || dy > 1) { star = false; continue; }
-        const int slot = dt ? (dt < 0 ? 1 : 2) : dx ? (dx < 0 ? 3 : 4) : dy ? (dy < 0 ? 5 : 6) : 0;
-        s7[slot] += w[i];
-    }
-    *s = Star{s7[0], s7[1], s7[2], s7[3], s7[4], s7[5], s7[6]};
-    return star;
-}
-
 }  // namespace
 
 extern "C" {
@@ -431,7 +341,7 @@ int pre_screenflat_stencil3d_f32(const pre_field_t *f, const float *tap_w, const
     int rc = prepare_flat(g, fs, 1, s, B, T, X, Y, flags);
     if (rc) return rc;
     Linear1::Params p;
-    if (!flat_star_of_taps(tap_w, tap_off, ntaps, &p.s, &rc)) return rc ? rc : PRE_E_UNSUPPORTED;
+    if (!star_of_taps(tap_w, tap_off, ntaps, &p.s, &rc)) return rc ? rc : PRE_E_UNSUPPORTED;
     Star *stars[1] = {&p.s};
     relabel_stars(stars, 1);
     return launch_screen_flat<Linear1>(g, p, as_stream(stream));

@@ -2,11 +2,11 @@
 // include/cp_pre_screen.h): per sample, max |r| / m and the number of cells with |r| <= q_k * m at up to 16 levels, in the
 // launch that evaluates the residual r.
 //
-// star_march.hip is included for its templates only (Geom's field layout, Star, Nbr, the functors with their Staged /
+// The march templates are star_march.h's (Geom's field layout, Star, Nbr, the functors with their Staged /
 // XMASK masks, the lane shifts, the LDS-only barrier, the buffer descriptors, the XCD remap, pick_tseg).  The march below is
 // march_kernel's: a workgroup of NR x TYQ threads owns NR rows x 4*TYQ columns of ONE sample and marches over a t segment,
 // planes t-1, t, t+1 and the in-flight t+2 of its own quads in registers, the current plane staged through LDS for the
-// x-neighbours, the y-neighbours from the adjacent lane.  What differs is the end of a plane: nothing is stored.  The four
+// x-neighbours, the y-neighbours from the adjacent lane.  What differs is the end of a plane (screen_plane.h): nothing is stored.  The four
 // residual values are masked by the crop (a select), scored against the modulation with the guarded divide of the joint
 // score pass (calib.hip: js_update) and counted per level by compare -> wave mask -> population count -> scalar add, as
 // coverage_levels.hip counts.  A workgroup works on one sample only, so at the end of its segment its waves are combined
@@ -19,14 +19,9 @@
 // by the other seven: at most an eighth of 4 B per cell from HBM even if nothing of it survives until the next sample,
 // while the field halos keep meeting in one L2.  (Sample-fastest order would hold a modulation tile in L2 across samples
 // but put neighbouring tiles of a sample far apart: every halo row, 2/NR of the input, would be fetched twice.)
-#define PRE_STAR_MARCH_TEMPLATES_ONLY
-#include "star_march.hip"
-#include "../../include/cp_pre_screen.h"
+#include "screen_plane.h"
 
 namespace {
-
-static_assert(PRE_SCREEN_MAX_LEVELS == 16, "the level loop of screen_plane is unrolled 16 times");
-constexpr int NKMAX = PRE_SCREEN_MAX_LEVELS;
 
 struct SGeom {
     const float *f[MAXF];
@@ -43,52 +38,6 @@ struct SGeom {
     int tfree;                   // no operator has a tap along the marched axis: a segment loads its own planes only
     int ct, cx, cy, nk;
 };
-
-// calib.hip's js_update, restated (that file is a translation unit of libcp_pre_hip.so): the running maximum m of av / sv,
-// bitwise what dividing every element gives.  Only a candidate that can raise the maximum pays for the IEEE division: a
-// quotient that rounds above m always fails `av <= thr * sv` with thr = m(1 - 2^-20).  A NaN av or sv fails it too and
-// reaches the divide, 0/0 reaches it through the subnormal test; a NaN quotient sets the sticky flag.
-__device__ __forceinline__ void score_update(float av, float sv, float &m, float &thr, bool &nan)
-{
-    if (!(av <= thr * sv) || sv < 1.17549435e-38f) {
-        const float qt = av / sv;
-        if (qt != qt) nan = true;
-        else if (qt > m) { m = qt; thr = m * 0.99999905f; }
-    }
-}
-
-// The end of one plane.  r: the residual quad, mm: its modulation, keep[j]: cell j is counted.  qk / cnt: the levels and
-// their wave-wide counts, both wave-uniform (scalar registers: no vector register per level).
-// No fma contraction in here: hw = q * m rounds as coverage_levels.o's product does (csrc/Makefile), whatever the flags of
-// the rest of this file, which must stay those of star_march.o so that the functors round as the residual passes do.
-__device__ __forceinline__ void screen_plane(const float4 &r, const float4 &mm, const bool (&keep)[4], int nk,
-                                             const float (&qk)[NKMAX], unsigned int (&cnt)[NKMAX], float &m, float &thr, bool &nan)
-{
-#pragma clang fp contract(off)
-    const float rv[4] = {r.x, r.y, r.z, r.w}, mv[4] = {mm.x, mm.y, mm.z, mm.w};
-    float ac[4], sv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float a = fabsf(rv[j]);
-        // a cell outside the counted region: |r| = 0 over m = 1 for the score (never a candidate), NaN for the counts
-        // (outside at every level) - selects, so that whatever it holds stays where it is
-        sv[j] = keep[j] ? mv[j] : 1.0f;
-        score_update(keep[j] ? a : 0.0f, sv[j], m, thr, nan);
-        ac[j] = keep[j] ? a : __builtin_nanf("");
-    }
-#pragma unroll
-    for (int k = 0; k < NKMAX; ++k) {
-        if (k < nk) {                                        // (wave-uniform)
-            unsigned int c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float hw = qk[k] * sv[j];
-                c += (unsigned int)__popcll(__builtin_amdgcn_fcmpf(ac[j], hw, 5));      // 5: ordered <= (NaN: outside)
-            }
-            cnt[k] += c;
-        }
-    }
-}
 
 template <class Fn, int NR, int TYQ>
 __global__ void __launch_bounds__(NR *TYQ, MinWaves<Fn>::value)
@@ -325,7 +274,7 @@ int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st
 template <class Fn>
 int launch_screen(SGeom &g, const typename Fn::Params &prm, hipStream_t st)
 {
-    // the tiles of star_march.hip's launch()
+    // the tiles of star_march.h's launch()
     if (g.Y >= 192) return launch_screen_tiled<Fn, 8, 64>(g, prm, st);
     if (g.Y >= 96) return launch_screen_tiled<Fn, 16, 32>(g, prm, st);
     return launch_screen_tiled<Fn, 32, 16>(g, prm, st);
@@ -344,13 +293,8 @@ int launch_screen_mode(int mode, SGeom &g, const P &prm, hipStream_t st)
 int prepare_screen(SGeom &g, const pre_field_t *const *fs, int nf, const pre_screen_t *s, int64_t B, int64_t T, int64_t X,
                    int64_t Y, int flags)
 {
-    if (!s || !s->q || !s->score || !s->count || B <= 0 || T <= 0 || X <= 0 || Y <= 0) return PRE_E_NULL;
-    for (int i = 0; i < nf; ++i)
-        if (!fs[i] || !fs[i]->ptr) return PRE_E_NULL;
-    if (s->nk < 1 || s->nk > PRE_SCREEN_MAX_LEVELS || s->ct < 0 || s->cx < 0 || s->cy < 0) return PRE_E_RANGE;
-    if (s->count_ld < B) return PRE_E_NULL;
-    if (B > 0x7fffffff || T > 0x7fffffff || X > 0x7fffffff || Y > 0x7fffffff - 8) return PRE_E_SHAPE;
-    if ((double)T * (double)X * (double)Y >= 4294967296.0) return PRE_E_SHAPE;           // the counts are 32-bit
+    const int rc = screen_args(fs, nf, s, NKMAX, B, T, X, Y, 8);
+    if (rc) return rc;
     if (flags & ~(PRE_FLAG_HALO_X | PRE_FLAG_INTERIOR_T)) return PRE_E_UNSUPPORTED;
     for (int i = 0; i < nf; ++i)
         if (fs[i]->sY != 1) return PRE_E_UNSUPPORTED;              // (Nt-fastest views and the like: the caller falls back)
@@ -369,24 +313,6 @@ int prepare_screen(SGeom &g, const pre_field_t *const *fs, int nf, const pre_scr
     return PRE_OK;
 }
 
-// the star of a tap list (3 offsets per tap); false if a tap is off the 7-point star; PRE_E_SHAPE via *rc
-bool screen_star_of_taps(const float *w, const int32_t *off, int ntaps, Star *s, int *rc)
-{
-    float s7[7] = {0, 0, 0, 0, 0, 0, 0};
-    bool star = true;
-    *rc = PRE_OK;
-    for (int i = 0; i < ntaps; ++i) {
-        const int dt = off[3 * i], dx = off[3 * i + 1], dy = off[3 * i + 2];
-        if (dt < -3 || dt > 3 || dx < -3 || dx > 3 || dy < -3 || dy > 3) { *rc = PRE_E_SHAPE; return false; }
-        const int nz = (dt != 0) + (dx != 0) + (dy != 0);
-        if (nz > 1 || dt < -1 || dt > 1 || dx < -1 || dx > 1 || dy < -1 || dy > 1) { star = false; continue; }
-        const int slot = dt ? (dt < 0 ? 1 : 2) : dx ? (dx < 0 ? 3 : 4) : dy ? (dy < 0 ? 5 : 6) : 0;
-        s7[slot] += w[i];
-    }
-    *s = Star{s7[0], s7[1], s7[2], s7[3], s7[4], s7[5], s7[6]};
-    return star;
-}
-
 }  // namespace
 
 extern "C" {
@@ -403,7 +329,7 @@ int pre_screen_stencil3d_f32(const pre_field_t *f, const float *tap_w, const int
     int rc = prepare_screen(g, fs, 1, s, B, T, X, Y, flags);
     if (rc) return rc;
     Linear1::Params p;
-    if (!screen_star_of_taps(tap_w, tap_off, ntaps, &p.s, &rc)) return rc ? rc : PRE_E_UNSUPPORTED;
+    if (!star_of_taps(tap_w, tap_off, ntaps, &p.s, &rc)) return rc ? rc : PRE_E_UNSUPPORTED;
     Star *stars[1] = {&p.s};
     g.tfree = no_t_taps(stars, 1);
     return launch_screen<Linear1>(g, p, as_stream(stream));

@@ -2,7 +2,7 @@
 // sample of a [B,Nt,Nx] batch, max |r| / m and the number of cells with |r| <= q_k * m at up to 16 levels, in the launch
 // that evaluates the residual r (a ConvOperator of convops_1d, the advection residual, the Burgers residual).
 //
-// star_march.hip is included for its templates only (Star, Nbr, apply<>, Linear1, Burgers<MODE>, the lane shifts, the buffer
+// The march templates are star_march.h's (Star, Nbr, apply<>, Linear1, Burgers<MODE>, the lane shifts, the buffer
 // descriptors' idiom, the XCD remap, star_from_dense27, shape_of, resident_per_cu, chip_cus).  screen_march_kernel treats
 // [B,T,X] as [1,B,T,X] and marches over the batch: one workgroup would span many samples.  Here a sample is a PLANE of
 // R rows x C columns, C the axis with unit stride (Nx-fastest: R = Nt, C = Nx; Nt-fastest: R = Nx, C = Nt), and a workgroup
@@ -13,8 +13,7 @@
 //     the wave's first and last lane fetch one edge scalar; tm / tp are zeros (apply<K_STAR7> does not multiply a zero
 //     weight along that axis); rows and columns outside the sample are zero padding, what the residual passes compute;
 //   * no LDS and no barrier inside the march: waves meet once, at the end.
-// The end of a row is screen_march.hip's end of a plane (screen_plane, restated below: that file is a translation unit of
-// libcp_pre_screen.so): crop by select, guarded divide, hw = q_k * m without contraction, compare -> wave mask ->
+// The end of a row is screen_march.hip's end of a plane (screen_plane.h): crop by select, guarded divide, hw = q_k * m without contraction, compare -> wave mask ->
 // population count -> scalar add per level.  The waves of a workgroup are combined through LDS and the workgroup issues
 // ONE integer atomicMax on the score's bits and nk integer atomicAdds for its sample: order-independent, so repeated
 // calls and overlapping row slabs compose exactly and every run gives the same bytes.
@@ -36,14 +35,11 @@
 // The modulation m[R,C] is one more float4 stream through its own descriptor, shared by all samples: only lanes with a
 // counted cell load it, and only for counted rows.  Block order: chunks and column tiles of a sample contiguous per XCD,
 // the sample the slowest index (as screen_march_kernel: the XCDs walk different samples through the same rows).
-#define PRE_STAR_MARCH_TEMPLATES_ONLY
-#include "star_march.hip"
+#include "screen_plane.h"
 #include "../../include/cp_pre_screen1d.h"
 
 namespace {
 
-static_assert(PRE_SCREEN_MAX_LEVELS == 16, "the level loop of rows_epilogue is unrolled 16 times");
-constexpr int NKMAX = PRE_SCREEN_MAX_LEVELS;
 constexpr int ROWS_NW = 4;                   // waves per workgroup
 constexpr int ROWS_MINSEG = 8;               // fewest rows per wave segment the split goes down to
 
@@ -76,48 +72,6 @@ RSplit rows_split(long long B, int R, int C, long long slots)
     s.nChunk = (R + rc - 1) / rc;
     s.rSeg = (rc + nseg - 1) / nseg;
     return s;
-}
-
-// screen_march.hip's score_update (calib.hip's js_update), restated: the running maximum m of av / sv, bitwise what
-// dividing every element gives; only a candidate that can raise the maximum pays for the IEEE division.
-__device__ __forceinline__ void score_update(float av, float sv, float &m, float &thr, bool &nan)
-{
-    if (!(av <= thr * sv) || sv < 1.17549435e-38f) {
-        const float qt = av / sv;
-        if (qt != qt) nan = true;
-        else if (qt > m) { m = qt; thr = m * 0.99999905f; }
-    }
-}
-
-// The end of one row: screen_march.hip's screen_plane, restated.  No fma contraction in here: hw = q * m rounds as
-// coverage_levels.o's product does, whatever the flags of the rest of this file (those of star_march.o).
-__device__ __forceinline__ void rows_epilogue(const float4 &r, const float4 &mm, const bool (&keep)[4], int nk,
-                                              const float (&qk)[NKMAX], unsigned int (&cnt)[NKMAX], float &m, float &thr, bool &nan)
-{
-#pragma clang fp contract(off)
-    const float rv[4] = {r.x, r.y, r.z, r.w}, mv[4] = {mm.x, mm.y, mm.z, mm.w};
-    float ac[4], sv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float a = fabsf(rv[j]);
-        // a cell outside the counted region: |r| = 0 over m = 1 for the score (never a candidate), NaN for the counts
-        // (outside at every level) - selects, so that whatever it holds stays where it is
-        sv[j] = keep[j] ? mv[j] : 1.0f;
-        score_update(keep[j] ? a : 0.0f, sv[j], m, thr, nan);
-        ac[j] = keep[j] ? a : __builtin_nanf("");
-    }
-#pragma unroll
-    for (int k = 0; k < NKMAX; ++k) {
-        if (k < nk) {                                        // (wave-uniform)
-            unsigned int c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float hw = qk[k] * sv[j];
-                c += (unsigned int)__popcll(__builtin_amdgcn_fcmpf(ac[j], hw, 5));      // 5: ordered <= (NaN: outside)
-            }
-            cnt[k] += c;
-        }
-    }
 }
 
 template <class Fn>
@@ -212,7 +166,7 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm)
             n[0].ym = make_float4(lft, C.x, C.y, C.z);
             n[0].yp = make_float4(C.y, C.z, C.w, rgt);
             const float4 res = Fn::eval(n, prm);
-            rows_epilogue(res, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+            screen_plane(res, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
         };
 
         float4 w0, w1, w2, w3, m0, m1;

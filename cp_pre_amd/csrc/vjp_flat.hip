@@ -2,9 +2,9 @@
 // (libcp_pre_vjpflat.so, include/cp_pre_vjpflat.h): the backward pass of a physics-informed loss on fields whose memory is
 // [B,Nx,Ny,Nt] - the view the reference's training scripts pass (Physics_Informed/Wave_FNO_PISL.py:209-217).
 //
-// star_march.hip is included for its templates only (Star, Nbr, apply<>, the LDS-only barrier, the buffer descriptors,
-// pick_tseg).  The march below is flat_march_kernel's (screen_flat.hip's) up to the functor: the kernel axes are relabelled
-// as star_march.hip's prepare() relabels them for an Nt-fastest view (marched axis = Nx, x = Ny, y = Nt), Ny and Nt are
+// The march templates are star_march.h's (Star, Nbr, apply<>, the LDS-only barrier, the buffer descriptors, flat_split),
+// the functors vjp_functors.h's.  The march below is flat_march_kernel's (screen_flat.hip's) up to the functor: the kernel
+// axes are relabelled as star_march.h's prepare() relabels them for an Nt-fastest view (marched axis = Nx, x = Ny, y = Nt), Ny and Nt are
 // merged into one row of L = Ny*Nt cells, a workgroup owns a chunk of that row of ONE sample and marches a segment of Nx
 // with planes t-1, t, t+1 and the in-flight t+2 of its own quads in registers.  x-neighbours are Nt cells back / ahead in
 // the merged row, through LDS with a halo of ceil(Nt/4) quads per side; y-neighbours are the adjacent cell of the same LDS
@@ -19,12 +19,11 @@
 // zero (the adjoint of a zero-padded correlation).  Up to three output streams in the same merged order; marched planes
 // are not cut by the crop: a rim plane's gradient is generally non-zero.  No atomics.
 //
-// The split (restated in tests/vjpflat_helpers.py, which names the test seams from it):
+// The split (tests/vjpflat_helpers.py states it again and names the test seams from it):
 //   chunk   flat_chunk(): 512 quads of the merged row per workgroup, or 448 ... 256 when that saves FLAT_NT_GAIN per cent
 //           of chunks x (chunk + staged halo quads); the staged halo is 2 * min(32, ceil(Nt/4)) quads;
 //   march   pick_tseg(B * chunks, Nx, resident workgroups): the marched axis in segments of tSeg planes.
-#define PRE_STAR_MARCH_TEMPLATES_ONLY
-#include "star_march.hip"
+#include "vjp_functors.h"
 #include "../../include/cp_pre_vjpflat.h"
 
 // 0: the NS-momentum instantiation is not built and its entry returns PRE_E_UNSUPPORTED (the project's rule for an
@@ -48,49 +47,6 @@ struct FVGeom {
     int crop;                    // cells per side the loss does not average over, on every axis (0 or 1)
     float scale;                 // host factor of g ...
     const float *dev_scale;      // ... times this device scalar, if given (the upstream gradient of loss.backward())
-};
-
-__device__ __forceinline__ float4 mul4(const float4 &a, const float4 &b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ Nbr mul_nbr(const Nbr &a, const Nbr &b)
-{
-    return Nbr{mul4(a.c, b.c), mul4(a.tm, b.tm), mul4(a.tp, b.tp), mul4(a.xm, b.xm), mul4(a.xp, b.xp), mul4(a.ym, b.ym), mul4(a.yp, b.yp)};
-}
-
-// ------------------------------------------------------------------ the functors of residual_vjp.hip, restated (that file
-// is a translation unit of libcp_pre_vjp.so): n[0] is gg, r[] the gradients; every star arrives mirrored, folded, relabelled
-struct VjpLinear1 {      // df = S^T(gg)
-    static constexpr int FIN = 1, FOUT = 1;
-    struct Params { Star st; };
-    static __device__ __forceinline__ void eval(const Nbr (&n)[1], const Params &p, float4 (&r)[1]) { r[0] = apply<K_STAR7>(p.st, n[0]); }
-};
-
-struct VjpLinear2 {      // r = Sa(a) + ratio*Sb(b):  da = Sa^T(gg), db = ratio*Sb^T(gg)  (ratio folded into bt)
-    static constexpr int FIN = 1, FOUT = 2;
-    struct Params { Star at, bt; };
-    static __device__ __forceinline__ void eval(const Nbr (&n)[1], const Params &p, float4 (&r)[2])
-    {
-        r[0] = apply<K_STAR7>(p.at, n[0]);
-        r[1] = apply<K_STAR7>(p.bt, n[0]);
-    }
-};
-
-// NS momentum, a = dx*dy, b = dt*dy, c = dt*dx, n = nu*dt (cp_pre_vjp.h):
-//   du = (a*Dt^T - n*L^T)(gg) + gg*(b*Dx(u) + c*Dx(v)) + b*Dx^T(gg*u) + c*Dy^T(gg*v)
-//   dv = (a*Dt^T - n*L^T)(gg) + gg*(c*Dy(u) + b*Dy(v)) + c*Dx^T(gg*u) + b*Dy^T(gg*v)
-//   dp = (b*Dx^T + c*Dy^T)(gg)
-struct VjpNSMomentum {
-    static constexpr int FIN = 3, FOUT = 3;
-    struct Params { Star lin, pT, Dx, Dy, DxT, DyT; float b, c; };     // lin = a*Dt^T - n*L^T, pT = b*Dx^T + c*Dy^T
-    static __device__ __forceinline__ void eval(const Nbr (&n)[3], const Params &p, float4 (&r)[3])
-    {
-        const Nbr &g = n[0], &u = n[1], &v = n[2];
-        const Nbr gu = mul_nbr(g, u), gv = mul_nbr(g, v);
-        const float4 lin = apply<K_STAR7>(p.lin, g);
-        const float4 X = apply<K_STAR7>(p.DxT, gu), Yv = apply<K_STAR7>(p.DyT, gv);
-        r[0] = lin + mul4(g.c, p.b * apply<K_STAR7>(p.Dx, u) + p.c * apply<K_STAR7>(p.Dx, v)) + p.b * X + p.c * Yv;
-        r[1] = lin + mul4(g.c, p.c * apply<K_STAR7>(p.Dy, u) + p.b * apply<K_STAR7>(p.Dy, v)) + p.c * X + p.b * Yv;
-        r[2] = apply<K_STAR7>(p.pT, g);
-    }
 };
 
 // ------------------------------------------------------------------ the march
@@ -243,30 +199,9 @@ __global__ void __launch_bounds__(FLAT_NT) vjp_flat_kernel(const FVGeom g, const
 }
 
 // ------------------------------------------------------------------ host side
-Star mirrored(const Star &s) { return Star{s.c, s.tp, s.tm, s.xp, s.xm, s.yp, s.ym}; }
-
-// ca*a + cb*b, folded in double and rounded once
-Star combine(double ca, const Star &a, double cb, const Star &b)
-{
-    auto m = [&](float x, float y) { return (float)(ca * (double)x + cb * (double)y); };
-    return Star{m(a.c, b.c), m(a.tm, b.tm), m(a.tp, b.tp), m(a.xm, b.xm), m(a.xp, b.xp), m(a.ym, b.ym), m(a.yp, b.yp)};
-}
-
 // prepare()'s relabelling of the star weights for kernel axes (X, Y, T): the logical x-taps sit on the marched axis, the
 // y-taps on the kernel's x, the t-taps on its y
 Star relabelled(const Star &o) { return Star{o.c, o.xm, o.xp, o.ym, o.yp, o.tm, o.tp}; }
-
-// launch_flat's chunk rule (every stream is staged): 512 quads per workgroup, or 448 / 384 / 320 / 256 when that leaves fewer
-// idle lanes in the row's last chunk; cost of a row = chunks x (quads + the halo quads staged per chunk); ties go to the
-// wider chunk
-int flat_chunk(long long quads, int Ty)
-{
-    const int halo = 2 * ((Ty + 3) / 4 < FLAT_H ? (Ty + 3) / 4 : FLAT_H);
-    int nt = FLAT_NT;
-    for (int c = nt - 64; c >= 256; c -= 64)
-        if ((quads + c - 1) / c * (c + halo) * 100 < (quads + nt - 1) / nt * (nt + halo) * (100 - FLAT_NT_GAIN)) nt = c;
-    return nt;
-}
 
 template <class Fn>
 int launch_vjp_flat(FVGeom &g, const typename Fn::Params &prm, hipStream_t st)
@@ -274,37 +209,15 @@ int launch_vjp_flat(FVGeom &g, const typename Fn::Params &prm, hipStream_t st)
     static_assert(2 * Fn::FIN * (FLAT_NT + 2 * FLAT_H) * 16 <= 64 * 1024, "static LDS of a workgroup");
     static_assert(FLAT_MAX_Y <= 4 * FLAT_H, "an x-neighbour must lie inside the staged halo");
     const long long quads = (long long)g.X * g.Y / 4;
-    const int nt = flat_chunk(quads, g.Y);
+    const int nt = flat_chunk(quads, g.Y, true);                   // (every stream is staged)
     g.nCh = (int)((quads + nt - 1) / nt);
-    long long tiles = (long long)g.B * g.nCh;
-    // (by chunk width; 0 = not asked yet.  Host threads may race to fill a slot: they write the same value)
-    static std::atomic<int> per_cu[FLAT_NT / 64 + 1] = {};
-    int occ = per_cu[nt / 64].load(std::memory_order_relaxed);
-    if (!occ) {
-        occ = resident_per_cu(vjp_flat_kernel<Fn>, nt);
-        per_cu[nt / 64].store(occ, std::memory_order_relaxed);
-    }
-    const int tSeg = pick_tseg(tiles, g.T, (long long)occ * chip_cus());
-    g.tSeg = tSeg;
-    g.nTSeg = (g.T + tSeg - 1) / tSeg;
-    tiles *= g.nTSeg;
-    if (tiles <= 0 || tiles * nt > 0xffffffffLL) return PRE_E_SHAPE;       // the dispatch packet counts work-items in 32 bits
-    hipLaunchKernelGGL((vjp_flat_kernel<Fn>), dim3((unsigned)tiles), dim3(nt), 0, st, g, prm);
+    static std::atomic<int> per_cu[FLAT_NT / 64 + 1] = {};         // (by chunk width)
+    unsigned grid;
+    const int rc = flat_split(vjp_flat_kernel<Fn>, nt, per_cu, g, (long long)g.B * g.nCh, g.T, &grid);
+    if (rc) return rc;
+    hipLaunchKernelGGL((vjp_flat_kernel<Fn>), dim3(grid), dim3(nt), 0, st, g, prm);
     PRE_LAUNCH_CHECK();
     return PRE_OK;
-}
-
-// Byte range [lo, hi) a strided view addresses
-struct Span { uintptr_t lo, hi; };
-Span span_of(const void *ptr, const int64_t *s, const int64_t *n)
-{
-    intptr_t lo = 0, hi = 0;
-    for (int d = 0; d < 4; ++d) {
-        const intptr_t e = (intptr_t)s[d] * (intptr_t)(n[d] - 1);
-        if (e < 0) lo += e; else hi += e;
-    }
-    const uintptr_t base = (uintptr_t)ptr;
-    return {base + lo * 4, base + hi * 4 + 4};
 }
 
 // Null / empty / layout / overlap checks of everything the entry points hand to the kernel (residual_vjp.hip's
@@ -313,11 +226,7 @@ Span span_of(const void *ptr, const int64_t *s, const int64_t *n)
 int prepare_vjp_flat(FVGeom &g, const pre_field_t *const *fs, int nf, const pre_out_t *const *os, int no, int64_t B, int64_t T,
                      int64_t X, int64_t Y, int flags, float host_scale, const float *dev_scale)
 {
-    if (B <= 0 || T <= 0 || X <= 0 || Y <= 0) return PRE_E_NULL;
-    for (int i = 0; i < nf; ++i)
-        if (!fs[i] || !fs[i]->ptr) return PRE_E_NULL;
-    for (int k = 0; k < no; ++k)
-        if (!os[k] || !os[k]->ptr) return PRE_E_NULL;
+    if (!vjp_views_given(fs, nf, os, no, B, T, X, Y)) return PRE_E_NULL;
     if (B > 0x7fffffff || T > 0x7fffffff || X > 0x7fffffff || Y > 0x7fffffff) return PRE_E_SHAPE;
     if (flags & ~PRE_VJP_CROP) return PRE_E_UNSUPPORTED;
     // the flat form's layout: T contiguous and short, dense rows, whole quads
@@ -327,18 +236,7 @@ int prepare_vjp_flat(FVGeom &g, const pre_field_t *const *fs, int nf, const pre_
     for (int k = 0; k < no; ++k)
         if (os[k]->sT != 1 || os[k]->sY != T || os[k]->sX != Y * T) return PRE_E_UNSUPPORTED;
     if (Y * T >= (1LL << 30)) return PRE_E_SHAPE;                  // a thread's place in a plane is a 32-bit byte offset
-    const int64_t n[4] = {B, T, X, Y};
-    for (int k = 0; k < no; ++k) {
-        const int64_t so[4] = {os[k]->sB, os[k]->sT, os[k]->sX, os[k]->sY};
-        const Span o = span_of(os[k]->ptr, so, n);
-        for (int i = 0; i < nf; ++i) {
-            const int64_t s[4] = {fs[i]->sB, fs[i]->sT, fs[i]->sX, fs[i]->sY};
-            const Span f = span_of(fs[i]->ptr, s, n);
-            if (o.lo < f.hi && f.lo < o.hi) return PRE_E_SHAPE;
-        }
-        for (int j = 0; j < k; ++j)
-            if (os[j]->ptr == os[k]->ptr) return PRE_E_SHAPE;
-    }
+    if (!vjp_views_disjoint(fs, nf, os, no, B, T, X, Y)) return PRE_E_SHAPE;
     for (int i = 0; i < VF_MAXIN; ++i) {
         const bool on = i < nf;
         g.f[i] = on ? fs[i]->ptr : nullptr;
@@ -354,24 +252,6 @@ int prepare_vjp_flat(FVGeom &g, const pre_field_t *const *fs, int nf, const pre_
     g.scale = host_scale;
     g.dev_scale = dev_scale;
     return PRE_OK;
-}
-
-// the star of a tap list (3 offsets per tap); false if a tap is off the 7-point star; PRE_E_SHAPE via *rc
-bool star_of_taps(const float *w, const int32_t *off, int ntaps, Star *s, int *rc)
-{
-    float s7[7] = {0, 0, 0, 0, 0, 0, 0};
-    bool star = true;
-    *rc = PRE_OK;
-    for (int i = 0; i < ntaps; ++i) {
-        const int dt = off[3 * i], dx = off[3 * i + 1], dy = off[3 * i + 2];
-        if (dt < -3 || dt > 3 || dx < -3 || dx > 3 || dy < -3 || dy > 3) { *rc = PRE_E_SHAPE; return false; }
-        const int nz = (dt != 0) + (dx != 0) + (dy != 0);
-        if (nz > 1 || dt < -1 || dt > 1 || dx < -1 || dx > 1 || dy < -1 || dy > 1) { star = false; continue; }
-        const int slot = dt ? (dt < 0 ? 1 : 2) : dx ? (dx < 0 ? 3 : 4) : dy ? (dy < 0 ? 5 : 6) : 0;
-        s7[slot] += w[i];
-    }
-    *s = Star{s7[0], s7[1], s7[2], s7[3], s7[4], s7[5], s7[6]};
-    return star;
 }
 
 }  // namespace

@@ -6,7 +6,7 @@
  *   ncf_scores = np.abs(cal_out_residual - cal_pred_residual)                              Marginal/NS_Residuals_CP.py:289
  *   modulation = modulation_func(cal_out_residual, cal_pred_residual)                      Joint/Burgers_Residuals_CP.py:219-220
  * Every score the scripts form (|a - b|, std(a - b), max |a - b| / sigma) depends on d = r(a) - r(b) only.  The entries
- * below read BOTH field sets in one pass of the star march (star_march.hip) and write d (or |d| under PRE_FLAG_ABS):
+ * below read BOTH field sets in one pass of the star march (star_march.h) and write d (or |d| under PRE_FLAG_ABS):
  * 4*(2F + 1) bytes per cell instead of 4*(F + 1) twice plus 12 for the difference pass.
  *
  * Conventions (those of cp_pre_hip.h, whose types, flags and error codes this header uses):
@@ -24,7 +24,8 @@
  *     ranges (first to last element each view addresses, the halo rows included under PRE_FLAG_HALO_X), not the
  *     elements touched: an `out` interleaved with the inputs - one slot of a stacked buffer that also holds them - is
  *     refused although it shares no element with them, where the single-set twin accepts it.  Write into a separate
- *     buffer, or run the two single-set passes.
+ *     buffer, or run the two single-set passes.  A view whose offsets, in elements or in bytes, leave int64 (or whose
+ *     range leaves the address space) is PRE_E_SHAPE too: it has no range to compare;
  * Non-finite values reach the cells they reach through the two single-set passes; inf - inf = NaN as in numpy.
  */
 #ifndef CP_PRE_PAIR_H

@@ -22,7 +22,7 @@
  *     D_y == D_t construction quirk is inherited); a kernel with weight off the 7-point star: PRE_E_UNSUPPORTED;
  *   - PRE_E_NULL for a null pointer or an empty extent; PRE_E_SHAPE for an output whose bounding byte range overlaps
  *     that of an input, or two outputs with one base address (outputs may otherwise interleave: the slots of one
- *     stacked gradient tensor);
+ *     stacked gradient tensor), or a view whose offsets, in elements or in bytes, leave int64;
  *   - nothing allocates, nothing synchronises, all work is enqueued on `stream`.
  */
 #ifndef CP_PRE_VJP_H

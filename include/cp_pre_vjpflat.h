@@ -19,7 +19,8 @@
  *     (Y * T) % 4 == 0 and T < 96; everything else - a unit-stride last axis included: that is libcp_pre_vjp.so's - is
  *     PRE_E_UNSUPPORTED before any launch, as are operator weight off the 7-point star and any flag but PRE_VJP_CROP;
  *   - PRE_E_NULL for a null pointer or an empty extent; PRE_E_SHAPE for an output whose bounding byte range overlaps that
- *     of an input, two outputs with one base address, a merged row beyond 2^30 cells or a tap offset beyond +-3;
+ *     of an input, two outputs with one base address, a view whose offsets, in elements or in bytes, leave int64, a
+ *     merged row beyond 2^30 cells or a tap offset beyond +-3;
  *   - no atomics: the same view gives the same bytes on every run; nothing allocates, nothing synchronises, all work is
  *     enqueued on `stream`.
  */

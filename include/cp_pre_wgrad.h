@@ -23,7 +23,8 @@
  *   - kernel extents kt, kx, ky in {1, 3}; dk is the dense [kt][kx][ky] device array in the LOGICAL order whatever the
  *     layout; other extents, other flags: PRE_E_UNSUPPORTED;
  *   - PRE_E_NULL for a null pointer or an empty extent; PRE_E_SHAPE for an extent beyond int32 or a dk / workspace whose
- *     byte range overlaps that of an input (or each other);
+ *     byte range overlaps that of an input (or each other), or an input view whose offsets, in elements or in bytes,
+ *     leave int64;
  *   - deterministic: the grid is a function of the shape alone, every workgroup writes one fp64 partial per tap to
  *     `workspace`, a second stage adds them in a fixed order, applies the scale in fp64 and rounds ONCE to fp32.  No
  *     floating-point atomics, no atomics on dk: the same views give the same bytes every time, on any stream;

@@ -109,7 +109,7 @@ def test_c3_interior_row_slabs_and_c4_equations():
     other = 64 * 512
     assert bench.resident_bytes(4096, 510, 128, other) == ((4096 + 3) * 3 * 130 + 4096 * 128) * other * 4 + 4096 * 256
     fields = {"continuity": 3, "momentum": 6, "energy": 6, "induction": 4, "gauss": 2}
-    src = open(os.path.join(ROOT, "cp_pre_amd", "csrc", "star_march.hip")).read()
+    src = open(os.path.join(ROOT, "cp_pre_amd", "csrc", "star_march.h")).read()          # (the functors of star_march.hip's entries)
     for eq, f in fields.items():
         cfg = bench.mhd_config(eq)
         assert cfg["bpc"] == 4 * (f + 1) and cfg["equation"] == eq and cfg["shape"] == (1024, 64, 256, 256)

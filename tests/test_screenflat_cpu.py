@@ -94,9 +94,10 @@ def test_screenflat_c_client_compiles_against_the_header(tmp_path):
 
 
 def test_screenflat_translation_unit_and_makefile_target():
-    """the new translation unit includes star_march.hip for its templates only and its own header"""
+    """the translation unit takes the march templates through the screens' shared header, and includes its own header"""
     src = open(os.path.join(ROOT, "cp_pre_amd", "csrc", "screen_flat.hip")).read()
-    assert "#define PRE_STAR_MARCH_TEMPLATES_ONLY" in src and '#include "star_march.hip"' in src
+    assert '#include "screen_plane.h"' in src and "PRE_STAR_MARCH_TEMPLATES_ONLY" not in src and "star_march.hip" not in src
+    assert '#include "star_march.h"' in open(os.path.join(ROOT, "cp_pre_amd", "csrc", "screen_plane.h")).read()
     assert '#include "../../include/cp_pre_screenflat.h"' in src
     mk = open(os.path.join(ROOT, "cp_pre_amd", "csrc", "Makefile")).read()
     assert "screenflat_OBJS := screen_flat.o" in mk and re.search(r"^LIBS\s+:=.*\bscreenflat\b", mk, flags=re.M)

@@ -92,11 +92,17 @@ def test_vjpflat_header_and_c_client_compile_as_c99(tmp_path):
 
 def test_vjpflat_translation_unit_and_makefile_target():
     src = open(os.path.join(ROOT, "cp_pre_amd", "csrc", "vjp_flat.hip")).read()
-    assert "#define PRE_STAR_MARCH_TEMPLATES_ONLY" in src and '#include "star_march.hip"' in src
-    assert '#include "../../include/cp_pre_vjpflat.h"' in src and "atomic" not in src.split("// ---")[2]      # (the march)
+    assert '#include "vjp_functors.h"' in src and "PRE_STAR_MARCH_TEMPLATES_ONLY" not in src and "star_march.hip" not in src
+    assert '#include "star_march.h"' in open(os.path.join(ROOT, "cp_pre_amd", "csrc", "vjp_functors.h")).read()
+    march = src.split("// ---")[1]
+    assert "vjp_flat_kernel" in march and "lds_barrier" in march and "atomic" not in march
+    assert '#include "../../include/cp_pre_vjpflat.h"' in src
     mk = open(os.path.join(ROOT, "cp_pre_amd", "csrc", "Makefile")).read()
     assert "vjpflat_OBJS := vjp_flat.o" in mk and re.search(r"^LIBS\s+:=.*\bvjpflat\b", mk, flags=re.M)
-    assert re.search(r"^vjp_flat\.o: star_march\.hip$", mk, flags=re.M)
+    shared = re.search(r"^SHARED_OBJS := ((?:.*\\\n)*.*)$", mk, flags=re.M).group(1)
+    assert "$(vjpflat_OBJS)" in shared and re.search(r"^\$\(SHARED_OBJS\): \$\(SHARED_HDRS\)$", mk, flags=re.M)
+    assert re.search(r"^SHARED_HDRS := .*\bstar_march\.h\b.*\bvjp_functors\.h\b", mk, flags=re.M)
+    assert "star_march.hip" not in mk and mk.count("-disable-vector-combine") == 1      # (no hand-written line, flags once)
     assert re.search(r"^\$\(vjpflat_OBJS\): \$\(INC\)/cp_pre_vjpflat\.h \$\(INC\)/cp_pre_vjp\.h$", mk, flags=re.M)
 
 
