@@ -68,6 +68,19 @@ def taps_of(karr):
     return w, off.astype(np.int32)
 
 
+def is_star(off):
+    """Do the tap offsets [n, nd] all lie on an axis: the 7-point star in 3-D, the 5-point star in 2-D?"""
+    return not len(off) or not (np.count_nonzero(off, axis=1) > 1).any()
+
+
+def tap_args(w, off):
+    """(weights, offsets, count) of ``taps_of`` as the C signatures take them; a kernel without taps still hands the
+    library two valid pointers."""
+    if not len(w):
+        return (ctypes.c_float * 1)(), (ctypes.c_int32 * 1)(), 0
+    return _lib.farr(w), _lib.iarr32(off.reshape(-1)), len(w)
+
+
 def to_device(t):
     """(device tensor, original device).  Raises without a GPU: no CPU fallback.
 
@@ -249,15 +262,13 @@ def _xcorr_run(fields, kernel, nd, flags, out, load, name):
         raise ValueError("out must be an fp32 device tensor of the field's shape")
     if out.numel() == 0:
         return _lib.PRE_OK, out, origin
-    wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
-    ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
     views.append(out)
     if nd == 3:                                 # PreField arguments in 3-D, pointer + stride array in 2-D; the output last
         args = [ctypes.byref(_lib.field(v)) for v in views]
     else:
         args = [x for v in views for x in (_lib.ptr(v), _lib.iarr64(v.stride()))]
     with torch.cuda.device(dev.device):
-        return getattr(lib, name)(*args, wv, ov, len(w), *dev.shape, flags, _lib.stream()), out, origin
+        return getattr(lib, name)(*args, *tap_args(w, off), *dev.shape, flags, _lib.stream()), out, origin
 
 
 def _xcorr_impl(field, kernel, nd, flags=0, out=None):

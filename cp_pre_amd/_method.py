@@ -1,0 +1,156 @@
+"""One residual method, resolved once for everything that launches on it.
+
+``losses`` (the fused VJPs) and ``screen`` (the fused screens) ask the same questions of a ``ConvOperator`` or a bound
+residual method of ``cp_pre_amd.residuals``: which residual is it, which operators, channels and scalars does it read, and
+can a fused launch take this input?  ``Method`` answers them: the class / name ladder is the table ``_LADDER``, what a
+residual reads is ``_READS``, its scalars in the order of the C signatures are ``_SCALARS``.  A consumer subclasses it with
+three small tables - ``KIND`` (residual -> its fused kind), ``ROWS_KIND`` (the fused kind of the 1-D family's own library)
+and ``WHY`` (residual -> why it has no fused kind); a residual in none of them is a ``TypeError`` - and keeps its own
+``prepare*`` (the ORDER of the reasons is behaviour) and launchers.  Host only: nothing here loads a library.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _dispatch, _lib
+from . import residuals as R
+from .convops_1d import ConvOperator as ConvOperator1D
+from .convops_2d import ConvOperator as ConvOperator2D
+
+FLAT_MAX_NT = 96             # star_march.hip's FLAT_MAX_Y: the merged-row forms' own bound on the contiguous extent
+
+MHD_EQ = ("continuity", "momentum", "energy", "induction")       # ``eq`` 0..3 of pre_screen_mhd_f32
+MHD_ROWS = tuple("mhd_" + e for e in MHD_EQ) + ("mhd_gauss", "mhd_any")
+JOREK_ROWS = ("jorek", "jorek_any")
+
+# (class, method name -> residual, the residual of any other bound method of the class or None)
+_LADDER = (
+    (R.NavierStokes, {"residual_momentum": "ns_momentum", "residual": "ns_momentum", "residual_continuity": "ns_continuity"}, None),
+    (R.MHD, {"residual_gauss": "mhd_gauss", "residual": "mhd_induction",     # (PRE_MHD.residual is the induction equation)
+             **{"residual_" + e: "mhd_" + e for e in MHD_EQ}}, "mhd_any"),
+    (R.PRE_Wave, {"residual": "wave"}, None),
+    (R.Advection, {"residual": "advection"}, None),
+    (R.Burgers, {"residual": "burgers"}, None),
+    (R.JOREK, {"residual_continuity": "jorek", "residual_temperature": "jorek"}, "jorek_any"),
+)
+# residual -> (residual axes, channels of a stacked [BS,F,...] input it reads (None: the input is the field itself;
+# (): a stacked input whose channels are not checked here), its operators as attributes of the object)
+_READS = {
+    "ns_momentum": (3, (0, 1, 2), ("D_t", "D_x", "D_y", "D_xx_yy")),
+    "ns_continuity": (3, (0, 1), ("D_x", "D_y")),
+    "mhd_continuity": (3, (0, 1, 2), ("D_t", "D_x", "D_y")),
+    "mhd_momentum": (3, tuple(range(6)), ("D_t", "D_x", "D_y")),
+    "mhd_energy": (3, tuple(range(6)), ("D_t", "D_x", "D_y")),
+    "mhd_induction": (3, (1, 2, 4, 5), ("D_t", "D_x", "D_y")),
+    "mhd_gauss": (3, (4, 5), ("D_x", "D_y")),
+    "mhd_any": (3, (), ()),
+    "wave": (3, None, ("D",)),
+    "advection": (2, None, ("D",)),
+    "burgers": (2, None, ("D_t", "D_x", "D_xx")),
+    "jorek": (3, (), ()),                                 # (JOREK's own layout [BS,F,Nx,Ny,Nt]: ``field_shape``)
+    "jorek_any": (3, (), ()),
+}
+# residual -> the floats its launches take after the operator kernels, in the order of the C signatures
+_SCALARS = {
+    "ns_momentum": lambda o: (float(o.dt), float(o.dx), float(o.dy), float(o.nu)),
+    "ns_continuity": lambda o: (float(o.dx / o.dy),),
+    "mhd_gauss": lambda o: (1.0,),
+    # 2 dt / dx evaluated as Burgers.residual evaluates it (in fp32 where dt and dx are fp32), then widened: every launch
+    # on a Burgers residual takes the same rounding of that factor as the reference
+    "burgers": lambda o: (float(o.dx), float(o.dt), float(o.nu), float(2 * o.dt / o.dx)),
+    **{"mhd_" + e: (lambda o: (float(o.gamma),)) for e in MHD_EQ},
+}
+_NOT_A_METHOD = "residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator"
+
+
+class Method:
+    """``method`` resolved: ``obj`` (the operator, or the object the method is bound to), ``is_op``, ``row`` (the residual:
+    a key of ``_READS``, or 'op3d' / 'op2d' / 'spectral' for a ``ConvOperator``), ``nd`` residual axes, ``ops`` (a tuple,
+    () where there is none), ``chan``, and by the consumer's tables ``kind`` (None: no fused launch), ``rows_kind`` and
+    ``why`` a fallback is taken."""
+    KIND, ROWS_KIND, WHY = {}, {}, {}
+
+    def __init__(self, method):
+        self.method = method
+        self.is_op = isinstance(method, (ConvOperator1D, ConvOperator2D))
+        self.obj = obj = method if self.is_op else getattr(method, "__self__", None)
+        if self.is_op:
+            # ``ops`` is (method,) for a spectral operator too - for the screens as well, which had () there: no launch
+            # reads it (``kind`` is None), and ``kernel_vjp`` finds the kernel of every operator at ``ops[0]``
+            self.nd, self.chan, self.ops = (2 if isinstance(method, ConvOperator1D) else 3), None, (method,)
+            self.row = "spectral" if getattr(method, "conv", None) != method.convolution else "op%dd" % self.nd
+        elif obj is None or not callable(method):
+            raise TypeError(_NOT_A_METHOD)
+        else:
+            name = getattr(method, "__name__", "")
+            self.row = next((names.get(name, other) for cls, names, other in _LADDER if isinstance(obj, cls)), None)
+            if self.row is None:
+                raise TypeError(_NOT_A_METHOD)
+            self.nd, self.chan, ops = _READS[self.row]
+            self.ops = tuple(getattr(obj, a) for a in ops)
+        self.kind, self.rows_kind, self.why = self.KIND.get(self.row), self.ROWS_KIND.get(self.row), None
+        if self.kind is None:
+            if self.row not in self.WHY:
+                raise TypeError(_NOT_A_METHOD)
+            self.why = self.WHY[self.row].format(cls=type(obj).__name__)
+
+    # -------- shapes (host only)
+    def field_shape(self, x):
+        """Shape of the uncropped residual of input ``x``; raises on a rank the method does not take."""
+        if isinstance(self.obj, R.JOREK):
+            if x.dim() != 5:
+                raise ValueError(f"expected vars [BS,F,Nx,Ny,Nt], got {tuple(x.shape)}")
+            return (x.shape[0], x.shape[4], x.shape[2], x.shape[3])
+        if self.chan is not None:
+            need = max(self.chan, default=-1) + 1
+            if x.dim() != 5 or x.shape[1] < need:
+                raise ValueError(f"expected vars [BS,F>={need},Nt,Nx,Ny], got {tuple(x.shape)}")
+            return (x.shape[0],) + tuple(x.shape[2:])
+        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5:
+            return (x.shape[0],) + tuple(x.shape[2:])
+        if self.rows_kind is not None and x.dim() == 4 and x.shape[1] == 1:
+            return (x.shape[0],) + tuple(x.shape[2:])             # ([BS,1,Nt,Nx]: screened as x[:, 0], three-pass)
+        if x.dim() != self.nd + 1:
+            raise ValueError(f"expected a {self.nd + 1}-D field, got {tuple(x.shape)}")
+        return tuple(x.shape)
+
+    def fields(self, x):
+        """The [BS,Nt,Nx,Ny] views of ``x`` the residual reads."""
+        if self.chan is not None:
+            return [x[:, i] for i in self.chan]
+        return [x[:, 0] if x.dim() == 5 else x]
+
+    def scalars(self):
+        """The floats a launch on this residual takes after the operator kernels, in the order of the C signature."""
+        return _SCALARS[self.row](self.obj) if self.row in _SCALARS else ()
+
+    # -------- can a fused launch run?
+    def declined(self, x, yy=None, kernel_trains=False):
+        """What keeps a fused launch from running whatever the layout (no download), or None.  ``yy``: data the launch
+        does not differentiate; ``kernel_trains``: a kernel that requires grad is the caller's to train."""
+        if getattr(self.obj, "fused", True) is False:
+            return "fused=False"
+        if yy is not None and yy.requires_grad and torch.is_grad_enabled():
+            return "yy requires grad"
+        if not kernel_trains and _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
+            return "operator kernel requires grad"
+        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
+            return "multi-channel wave input"
+        return None
+
+    def star_kernels(self, kind, points=7):
+        """(why, kernels): ONE download of every operator kernel (``_dispatch.host_kernel``: a launch applies the kernels
+        the operators hold now); ``why`` if one has weight off the star - the name says ``points``.  ``kernels`` is what
+        the launch of ``kind`` takes: the taps (w, off) of a kind that is one operator, dense 3^nd floats per operator of
+        a kind that is several."""
+        why = "operator kernel off the %d-point star" % points
+        ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
+        if kind.startswith("stencil"):
+            if ks[0].ndim != self.nd or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
+                return why, ()
+            w, off = _dispatch.taps_of(ks[0])
+            return (None, (w, off)) if _dispatch.is_star(off) else (why, ())
+        if any(k.shape != (3,) * self.nd or not _dispatch.is_star(np.argwhere(k != 0) - 1) for k in ks):
+            return why, ()
+        return None, tuple(_lib.farr(k.reshape(-1)) for k in ks)

@@ -33,9 +33,9 @@ autograd.  ``last_route()`` says which route the last call took.
 reference's scripts pass, ``field[:, 0, 1:-1, 1:-1, 1:-1].permute(0, 3, 1, 2)``.  The forward pass is the one above (it
 already evaluates such views in their memory order); the sum of squares reads that residual where it lies, and ONE launch
 of the merged-row VJP writes the gradient, dense in the input's memory order.  Routes ``fused:flat_stencil3d``,
-``fused:flat_linear2``, ``fused:flat_ns_momentum``; whatever the library or the host checks decline (Nt >= 96, a merged
-row Ny*Nt that is no multiple of 4, u / v whose rows are not dense, the 1-D family, everything that falls back above)
-takes the fallback with its reason.
+``fused:flat_linear2``, ``fused:flat_ns_momentum``; whatever the library or the host checks decline (Nt at or above
+``FLAT_MAX_NT``, a merged row Ny*Nt that is no multiple of 4, u / v whose rows are not dense, the 1-D family, everything
+that falls back above) takes the fallback with its reason.
 
 ``wgrad=True`` (off by default: nothing above changes, ``libcp_pre_wgrad.so`` is never loaded) lets the operator kernel
 itself be trained, as the reference's wave scripts do (``Physics_Informed/Wave_FNO_PI.py:202-210``:
@@ -47,18 +47,21 @@ same ``backward`` ONE launch of ``pre_wgrad_stencil3d_f32`` (``include/cp_pre_wg
 ``fused:stencil3d+wgrad``, ``fused:stencil2d+wgrad``, ``fused:flat_stencil3d+wgrad``.  NS momentum, NS continuity and
 Burgers (several operators, or a non-linear residual), any residual where several operator kernels require grad, and
 ``residual_vjp`` keep ``fallback:operator kernel requires grad``.  ``kernel_vjp`` is the same launch for a general g.
+
+Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
+``_method.Method`` (shared with ``screen``); ``_Spec`` adds the kinds that have a fused VJP, the order of the reasons of
+``prepare`` / ``prepare_flat`` and ONE launcher (``vjp``; ``flat=True``: the merged-row library).  ``_LossFn`` is the one
+``autograd.Function`` of every fused route.
 """
 from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _dispatch, _lib
 from . import residuals as R
-from .convops_1d import ConvOperator as ConvOperator1D
-from .convops_2d import ConvOperator as ConvOperator2D
+from ._method import FLAT_MAX_NT, JOREK_ROWS, MHD_ROWS, Method
 
 _last_route = None
 
@@ -70,56 +73,18 @@ def last_route():
 
 
 # ------------------------------------------------------------------------------------------- what a method is
-class _Spec:
-    """One residual method, resolved: ``kind`` (None: no fused VJP), ``nd`` residual axes, ``chan`` - the channels of a
-    stacked ``[BS,F,...]`` input the residual reads (None: the input is the field itself), ``why`` a fallback is taken."""
+class _Spec(Method):
+    """One residual method, resolved (``_method.Method``) for the fused VJPs: ``kind`` (None: no fused VJP), ``nd``
+    residual axes, ``chan`` - the channels of a stacked ``[BS,F,...]`` input the residual reads (None: the input is the
+    field itself), ``why`` a fallback is taken."""
+    KIND = {"op3d": "stencil3d", "op2d": "stencil2d", "wave": "stencil3d", "advection": "stencil2d",
+            "ns_momentum": "ns_momentum", "ns_continuity": "linear2", "burgers": "burgers"}
+    WHY = {"spectral": "spectral operator", **dict.fromkeys(MHD_ROWS + JOREK_ROWS, "no fused VJP for {cls}")}
 
     def __init__(self, method):
-        self.method, self.kind, self.why, self.chan, self.nd = method, None, None, None, 3
-        self.is_op = isinstance(method, (ConvOperator1D, ConvOperator2D))
-        obj = method if self.is_op else getattr(method, "__self__", None)
-        name = getattr(method, "__name__", "")
-        self.obj = obj
-        if self.is_op:
-            self.nd = 2 if isinstance(method, ConvOperator1D) else 3
-            if getattr(method, "conv", None) != method.convolution:
-                self.why = "spectral operator"
-            else:
-                self.kind, self.ops = "stencil%dd" % self.nd, (method,)
-        elif obj is None or not callable(method):
-            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
-        elif isinstance(obj, R.NavierStokes) and name in ("residual_momentum", "residual"):
-            self.kind, self.chan, self.ops = "ns_momentum", (0, 1, 2), (obj.D_t, obj.D_x, obj.D_y, obj.D_xx_yy)
-        elif isinstance(obj, R.NavierStokes) and name == "residual_continuity":
-            self.kind, self.chan, self.ops = "linear2", (0, 1), (obj.D_x, obj.D_y)
-        elif isinstance(obj, R.Burgers) and name == "residual":
-            self.kind, self.nd, self.ops = "burgers", 2, (obj.D_t, obj.D_x, obj.D_xx)
-        elif isinstance(obj, R.PRE_Wave) and name == "residual":
-            self.kind, self.ops = "stencil3d", (obj.D,)
-        elif isinstance(obj, R.Advection) and name == "residual":
-            self.kind, self.nd, self.ops = "stencil2d", 2, (obj.D,)
-        elif isinstance(obj, (R.MHD, R.JOREK)):
-            self.why = "no fused VJP for " + type(obj).__name__
-            self.chan = ()                                        # (stacked input; JOREK's own layout: shapes not checked here)
-        else:
-            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
-
-    # -------- shapes (host only)
-    def field_shape(self, x):
-        """Shape of the uncropped residual of input ``x``; raises on a rank the method does not take."""
-        if isinstance(self.obj, R.JOREK):
-            if x.dim() != 5:
-                raise ValueError(f"expected vars [BS,F,Nx,Ny,Nt], got {tuple(x.shape)}")
-            return (x.shape[0], x.shape[4], x.shape[2], x.shape[3])
-        if self.chan is not None:
-            if x.dim() != 5 or x.shape[1] < len(self.chan):
-                raise ValueError(f"expected vars [BS,F>={len(self.chan)},Nt,Nx,Ny], got {tuple(x.shape)}")
-            return (x.shape[0],) + tuple(x.shape[2:])
-        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5:
-            return (x.shape[0],) + tuple(x.shape[2:])
-        if x.dim() != self.nd + 1:
-            raise ValueError(f"expected a {self.nd + 1}-D field, got {tuple(x.shape)}")
-        return tuple(x.shape)
+        super().__init__(method)
+        if self.kind is None and not self.is_op:
+            self.chan, self.ops = (), ()                         # (no launch reads them: a stacked input, shapes not checked here)
 
     def out_shape(self, x, boundary):
         s = self.field_shape(x)
@@ -150,65 +115,25 @@ class _Spec:
         """(why, kernels): ``why`` is None if the fused VJP can run on ``x`` - ``kernels`` are then the host copies of the
         operator kernels the launch takes - else the reason for the fallback.  Changes nothing on ``self``.  ``wgrad``: a
         kernel that requires grad does not decline a kind that is one linear operator."""
-        why, kernels = self.why, ()
         if self.kind is None:
-            return why, kernels
+            return self.why, ()
         if not x.is_cuda or (minus is not None and not minus.is_cuda):
-            why = "input on the CPU"
-        elif x.numel() == 0:
-            why = "empty input"
-        elif x.stride(-1) != 1 or (minus is not None and minus.stride(-1) != 1):
-            why = "no unit stride on the last axis"
-        else:
-            why = self._declined(x, minus, wgrad)
-            if why is None:
-                why, kernels = self._host_kernels()
-        return why, kernels
+            return "input on the CPU", ()
+        if x.numel() == 0:
+            return "empty input", ()
+        if x.stride(-1) != 1 or (minus is not None and minus.stride(-1) != 1):
+            return "no unit stride on the last axis", ()
+        why = self.declined(x, minus, wgrad and self.trains_kernel())
+        return (why, ()) if why is not None else self.star_kernels(self.kind)
 
     def trains_kernel(self):
         """Is this ONE linear operator whose kernel requires grad - what ``wgrad=True`` hands to ``pre_wgrad_stencil3d_f32``?"""
         return self.kind in ("stencil3d", "stencil2d") and len(self.ops) == 1 and _dispatch.needs_grad(self.ops[0].kernel)
 
-    def _declined(self, x, minus, wgrad=False):
-        """What keeps a fused VJP from running whatever the layout (no download), or None."""
-        if getattr(self.obj, "fused", True) is False:
-            return "fused=False"
-        if minus is not None and minus.requires_grad and torch.is_grad_enabled():
-            return "yy requires grad"
-        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]) and not (wgrad and self.trains_kernel()):
-            return "operator kernel requires grad"
-        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
-            return "multi-channel wave input"
-        return None
-
-    def _host_kernels(self):
-        """(why, kernels): one download of the operator kernels; ``why`` if they have weight off the 7-point star."""
-        why, kernels = None, ()
-        ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
-        if self.kind.startswith("stencil"):
-            if ks[0].ndim != self.nd or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
-                why = "operator kernel off the 7-point star"
-            else:
-                w, off = _dispatch.taps_of(ks[0])
-                if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
-                    why = "operator kernel off the 7-point star"
-                kernels = (w, off)
-        else:
-            if any(k.shape != (3,) * self.nd or not _is_star(k) for k in ks):
-                why = "operator kernel off the 7-point star"
-            kernels = tuple(_lib.farr(k.reshape(-1)) for k in ks)
-        return why, kernels
-
     # -------- flat=True: an input without unit stride on its last axis (host checks + one download)
     def wants_flat(self, x):
         """Is ``x`` an input ``flat=True`` offers to the merged-row VJP at all?  (Everything else: ``prepare``.)"""
         return x.is_cuda and x.numel() > 0 and x.dim() > 0 and x.stride(-1) != 1
-
-    def fields(self, x):
-        """The [BS,Nt,Nx,Ny] views of ``x`` the residual reads."""
-        if self.chan is not None:
-            return [x[:, i] for i in self.chan]
-        return [x[:, 0] if x.dim() == 5 else x]
 
     def prepare_flat(self, x, minus=None, wgrad=False):
         """``prepare`` for the merged-row VJP of ``libcp_pre_vjpflat.so``: (why, kernels).  The layout conditions are the
@@ -217,7 +142,7 @@ class _Spec:
             return self.why, ()
         if self.nd != 3:
             return "no flat VJP for the 1-D family", ()
-        why = self._declined(x, minus, wgrad)
+        why = self.declined(x, minus, wgrad and self.trains_kernel())
         if why is not None:
             return why, ()
         f = self.fields(x)
@@ -225,92 +150,47 @@ class _Spec:
         if f[0].stride(1) != 1:
             return "the unit-stride axis is not Nt", ()
         if Nt >= FLAT_MAX_NT:
-            return "Nt >= 96", ()
+            return "Nt >= %d" % FLAT_MAX_NT, ()
         if (Ny * Nt) % 4 != 0:
             return "merged row Ny*Nt not a multiple of 4", ()
         if self.kind == "ns_momentum" and any(v.stride(1) != 1 or v.stride(3) != Nt or v.stride(2) != Ny * Nt for v in f[:2]):
             return "rows of u, v not dense", ()
-        return self._host_kernels()
+        return self.star_kernels(self.kind)
 
-    # -------- the VJP launch: gfull [BS,*field] (unit stride last) -> gradient of x's shape
-    def vjp(self, kernels, gfull, x, crop, host_scale, dev_scale):
-        """``kernels``: what ``prepare`` returned.  None if the library declines."""
-        lib = _lib.load_vjp()
-        grad = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        flags = _lib.PRE_VJP_CROP if crop else 0
-        scale = (float(host_scale), _lib.ptr(dev_scale))
-        if gfull.stride(-1) != 1:
+    # -------- the VJP launch: gfull [BS,*field] -> gradient of x's shape
+    def vjp(self, kernels, gfull, x, crop, host_scale, dev_scale, flat=False):
+        """``kernels``: what ``prepare`` returned; ``gfull`` [BS,*field] (copied unless its last axis has unit stride).
+        ``flat``: the merged-row launch - ``kernels``: what ``prepare_flat`` returned; ``gfull`` [BS,Nt,Nx,Ny], dense in
+        memory order [BS,Nx,Ny,Nt]; the gradient is dense in ``x``'s memory order.  None if the library declines."""
+        lib = _lib.load_vjpflat() if flat else _lib.load_vjp()
+        name = ("pre_vjpflat_" if flat else "pre_vjp_") + self.kind + "_f32"
+        grad = _lib.empty_like_layout(x) if flat else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        if not flat and gfull.stride(-1) != 1:
             gfull = gfull.contiguous()
-        name = "pre_vjp_" + self.kind + "_f32"
+        if self.kind == "ns_momentum":
+            views = [gfull, R._arr([x[:, 0], x[:, 1]]), R._arr([grad[:, 0], grad[:, 1], grad[:, 2]])]
+        elif self.kind == "linear2":
+            views = [gfull, R._arr([grad[:, 0], grad[:, 1]])]
+        elif self.kind == "burgers":
+            views = [gfull, x, grad]
+        else:
+            views, kernels = [gfull, grad[:, 0] if grad.dim() == self.nd + 2 else grad], _dispatch.tap_args(*kernels)
+        if self.nd == 3:                                 # PreField arguments in 3-D, pointer + stride array in 2-D
+            args = [ctypes.byref(_lib.field(v)) if isinstance(v, torch.Tensor) else v for v in views]
+        else:
+            args = [a for v in views for a in (_lib.ptr(v), _lib.iarr64(v.stride()))]
         with torch.cuda.device(x.device):
-            st = _lib.stream()
-            if self.kind == "ns_momentum":
-                obj = self.obj
-                if x.shape[1] > 3:
-                    grad[:, 3:].zero_()
-                rc = lib.pre_vjp_ns_momentum_f32(
-                    ctypes.byref(_lib.field(gfull)), R._arr([x[:, 0], x[:, 1]]), R._arr([grad[:, 0], grad[:, 1], grad[:, 2]]),
-                    *kernels, float(obj.dt), float(obj.dx), float(obj.dy), float(obj.nu), *scale, *gfull.shape, flags, st)
-            elif self.kind == "linear2":
-                if x.shape[1] > 2:
-                    grad[:, 2:].zero_()
-                rc = lib.pre_vjp_linear2_f32(ctypes.byref(_lib.field(gfull)), R._arr([grad[:, 0], grad[:, 1]]), *kernels,
-                                             float(self.obj.dx / self.obj.dy), *scale, *gfull.shape, flags, st)
-            elif self.kind == "burgers":
-                obj = self.obj
-                rc = lib.pre_vjp_burgers_f32(
-                    *[a for t in (gfull, x, grad) for a in (_lib.ptr(t), _lib.iarr64(t.stride()))], *kernels,
-                    float(obj.dx), float(obj.dt), float(obj.nu), float(2 * obj.dt / obj.dx), *scale, *gfull.shape, flags, st)
-            else:
-                w, off = kernels
-                wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
-                ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
-                out = grad[:, 0] if grad.dim() == self.nd + 2 else grad
-                if self.nd == 3:
-                    rc = lib.pre_vjp_stencil3d_f32(ctypes.byref(_lib.field(gfull)), ctypes.byref(_lib.field(out)), wv, ov, len(w),
-                                                   *scale, *gfull.shape, flags, st)
-                else:
-                    rc = lib.pre_vjp_stencil2d_f32(_lib.ptr(gfull), _lib.iarr64(gfull.stride()), _lib.ptr(out),
-                                                   _lib.iarr64(out.stride()), wv, ov, len(w), *scale, *gfull.shape, flags, st)
-        if rc == _lib.PRE_E_UNSUPPORTED:
-            return None
-        _lib.check(rc, name)
-        return grad
-
-
-    # -------- the merged-row VJP launch: gfull [BS,Nt,Nx,Ny], dense in memory order [BS,Nx,Ny,Nt] -> gradient of x's shape
-    def vjp_flat(self, kernels, gfull, x, crop, host_scale, dev_scale):
-        """``kernels``: what ``prepare_flat`` returned.  The gradient is dense in ``x``'s memory order.  None if the
-        library declines."""
-        lib = _lib.load_vjpflat()
-        grad = _lib.empty_like_layout(x)
-        flags = _lib.PRE_VJP_CROP if crop else 0
-        scale = (float(host_scale), _lib.ptr(dev_scale))
-        name = "pre_vjpflat_" + self.kind + "_f32"
-        gf = ctypes.byref(_lib.field(gfull))
-        with torch.cuda.device(x.device):
-            st = _lib.stream()
-            if self.kind == "ns_momentum":
-                obj = self.obj
-                rc = lib.pre_vjpflat_ns_momentum_f32(
-                    gf, R._arr([x[:, 0], x[:, 1]]), R._arr([grad[:, 0], grad[:, 1], grad[:, 2]]), *kernels,
-                    float(obj.dt), float(obj.dx), float(obj.dy), float(obj.nu), *scale, *gfull.shape, flags, st)
-            elif self.kind == "linear2":
-                rc = lib.pre_vjpflat_linear2_f32(gf, R._arr([grad[:, 0], grad[:, 1]]), *kernels,
-                                                 float(self.obj.dx / self.obj.dy), *scale, *gfull.shape, flags, st)
-            else:
-                w, off = kernels
-                wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
-                ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
-                out = grad[:, 0] if grad.dim() == 5 else grad
-                rc = lib.pre_vjpflat_stencil3d_f32(gf, ctypes.byref(_lib.field(out)), wv, ov, len(w), *scale, *gfull.shape, flags, st)
+            rc = getattr(lib, name)(*args, *kernels, *self.scalars(), float(host_scale), _lib.ptr(dev_scale), *gfull.shape,
+                                    _lib.PRE_VJP_CROP if crop else 0, _lib.stream())
         if rc == _lib.PRE_E_UNSUPPORTED:
             return None
         _lib.check(rc, name)
         if self.chan is not None and x.shape[1] > len(self.chan):
-            grad[:, len(self.chan):].zero_()
+            grad[:, len(self.chan):].zero_()                       # (after the launch, which writes the other channels)
         return grad
 
+    def vjp_flat(self, kernels, gfull, x, crop, host_scale, dev_scale):
+        return self.vjp(kernels, gfull, x, crop, host_scale, dev_scale, True)
 
     # -------- the kernel-gradient launch: g [BS,*field], x (and minus) where they lie -> d / d kernel, on x's device
     def wgrad(self, g, x, minus, crop, host_scale, dev_scale):
@@ -338,17 +218,9 @@ class _Spec:
         return dk
 
 
-FLAT_MAX_NT = 96             # star_march.hip's FLAT_MAX_Y: the merged-row form's own bound on the contiguous extent
-
-
 def _nt_fastest_dense(r):
     """Is the [BS,Nt,Nx,Ny] tensor ``r`` dense in memory order [BS,Nx,Ny,Nt]?"""
     return r.dim() == 4 and r.permute(0, 2, 3, 1).is_contiguous()
-
-
-def _is_star(k):
-    idx = np.argwhere(k != 0) - 1
-    return not len(idx) or not (np.count_nonzero(idx, axis=1) > 1).any()
 
 
 # ------------------------------------------------------------------------------------------- validation (host only)
@@ -400,56 +272,6 @@ def _recompute_grad(spec, x, minus, boundary, g):
         return torch.autograd.grad(y, v, g.to(y.device))[0]
 
 
-class _LossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, spec, kernels, yy, boundary):
-        r = spec.full(pred, yy)
-        loss, n = _mean_sq(r, boundary)
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(r, pred)              # r: the one new tensor kept; pred is the caller's
-            ctx.spec, ctx.kernels, ctx.yy, ctx.boundary, ctx.n = spec, kernels, yy, boundary, n
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        # (once_differentiable: the VJP launch builds no graph, so create_graph=True raises instead of returning a gradient
-        # that silently has none)
-        r, pred = ctx.saved_tensors
-        spec, n = ctx.spec, ctx.n
-        up = gout.detach().to(device=pred.device, dtype=torch.float32).reshape(1)
-        grad = spec.vjp(ctx.kernels, r, pred, not ctx.boundary, 2.0 / n if n else 0.0, up)
-        if grad is None:                                 # (not expected after prepare(): the library declined)
-            m = r if ctx.boundary else r[(Ellipsis,) + (slice(1, -1),) * spec.nd]
-            grad = _recompute_grad(spec, pred, ctx.yy, ctx.boundary, (2.0 / max(n, 1)) * up * m)
-        return grad, None, None, None, None
-
-
-class _FlatLossFn(torch.autograd.Function):
-    """``_LossFn`` for ``flat=True``: ``r`` arrives evaluated (the caller has checked where it lies), the backward pass is
-    the merged-row launch."""
-
-    @staticmethod
-    def forward(ctx, pred, spec, kernels, yy, boundary, r):
-        loss, n = _mean_sq(r, boundary, where_it_lies=True)
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(r, pred)
-            ctx.spec, ctx.kernels, ctx.yy, ctx.boundary, ctx.n = spec, kernels, yy, boundary, n
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        r, pred = ctx.saved_tensors
-        spec, n = ctx.spec, ctx.n
-        up = gout.detach().to(device=pred.device, dtype=torch.float32).reshape(1)
-        grad = spec.vjp_flat(ctx.kernels, r, pred, not ctx.boundary, 2.0 / n if n else 0.0, up)
-        if grad is None:                                 # (not expected after prepare_flat(): the library declined)
-            m = r if ctx.boundary else r[(Ellipsis,) + (slice(1, -1),) * spec.nd]
-            grad = _recompute_grad(spec, pred, ctx.yy, ctx.boundary, (2.0 / max(n, 1)) * up * m)
-        return grad, None, None, None, None, None
-
-
 def _recompute_kernel_grad(spec, x, minus, boundary, g):
     """d <g, method(x) - method(minus)> / d kernel by the route that ran before: the composed expression on a fresh leaf
     in the operator's ``kernel`` slot, differentiated by torch."""
@@ -467,9 +289,11 @@ def _recompute_kernel_grad(spec, x, minus, boundary, g):
         return torch.autograd.grad(y, k, g.to(y.device))[0]
 
 
-class _KernelLossFn(torch.autograd.Function):
-    """``_LossFn`` / ``_FlatLossFn`` (``flat``: r arrives evaluated) with the operator kernel as a second input: the same
-    forward launches, the same field VJP launch, and ``pre_wgrad_stencil3d_f32`` for the kernel in the same backward."""
+class _LossFn(torch.autograd.Function):
+    """The loss of a fused route.  ``kernel``: the operator kernel where it trains (``wgrad=True``), else None; ``r``: the
+    residual where the caller has evaluated it already (``flat``: it has checked where r lies, and the backward pass is
+    the merged-row launch).  One field VJP launch for ``pred``, and ``pre_wgrad_stencil3d_f32`` for a kernel that trains,
+    in the same backward."""
 
     @staticmethod
     def forward(ctx, pred, kernel, spec, kernels, yy, boundary, flat, r):
@@ -477,28 +301,30 @@ class _KernelLossFn(torch.autograd.Function):
             r = spec.full(pred, yy)
         loss, n = _mean_sq(r, boundary, where_it_lies=flat)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            ctx.save_for_backward(r, pred, kernel)
+            ctx.save_for_backward(r, pred, *(() if kernel is None else (kernel,)))     # r: the one new tensor kept
             ctx.spec, ctx.kernels, ctx.yy, ctx.boundary, ctx.n, ctx.flat = spec, kernels, yy, boundary, n, flat
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        r, pred, kernel = ctx.saved_tensors
+        # (once_differentiable: the VJP launch builds no graph, so create_graph=True raises instead of returning a gradient
+        # that silently has none)
+        r, pred = ctx.saved_tensors[:2]
         spec, n = ctx.spec, ctx.n
         up = gout.detach().to(device=pred.device, dtype=torch.float32).reshape(1)
         scale = 2.0 / n if n else 0.0
         composed_g = lambda: (2.0 / max(n, 1)) * up * (r if ctx.boundary else r[(Ellipsis,) + (slice(1, -1),) * spec.nd])  # noqa: E731
         grad = gk = None
         if ctx.needs_input_grad[0]:
-            grad = (spec.vjp_flat if ctx.flat else spec.vjp)(ctx.kernels, r, pred, not ctx.boundary, scale, up)
+            grad = spec.vjp(ctx.kernels, r, pred, not ctx.boundary, scale, up, ctx.flat)
             if grad is None:                             # (not expected after prepare(): the library declined)
                 grad = _recompute_grad(spec, pred, ctx.yy, ctx.boundary, composed_g())
         if ctx.needs_input_grad[1]:
             gk = spec.wgrad(r, pred, ctx.yy, not ctx.boundary, scale, up)
             if gk is None:                               # the library declined (a layout it does not take): composed
                 gk = _recompute_kernel_grad(spec, pred, ctx.yy, ctx.boundary, composed_g())
-            gk = gk.to(kernel.device)
+            gk = gk.to(ctx.saved_tensors[2].device)
         return grad, gk, None, None, None, None, None, None
 
 
@@ -509,31 +335,22 @@ def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False):
     spec.field_shape(pred)                               # (called for its raise: a rank the method does not take)
     if yy is not None:
         _check_like(yy, pred, "yy")
-    if flat and spec.wants_flat(pred):
+    data = None if yy is None else yy.detach()
+    flat, r = bool(flat and spec.wants_flat(pred)), None
+    if flat:
         why, kernels = spec.prepare_flat(pred, yy, wgrad)
         if why is None:
-            r = spec.full(pred, None if yy is None else yy.detach())
+            r = spec.full(pred, data)
             if not _nt_fastest_dense(r):
                 why = "the forward pass returned the residual in another memory order"
-        if why is not None:
-            _last_route = "fallback:" + why
-            return spec.call(pred, boundary, yy).pow(2).mean()
-        if wgrad and spec.trains_kernel():
-            _last_route = "fused:flat_" + spec.kind + "+wgrad"
-            return _KernelLossFn.apply(pred, spec.ops[0].kernel, spec, kernels, None if yy is None else yy.detach(),
-                                       bool(boundary), True, r)
-        _last_route = "fused:flat_" + spec.kind
-        return _FlatLossFn.apply(pred, spec, kernels, None if yy is None else yy.detach(), bool(boundary), r)
-    why, kernels = spec.prepare(pred, yy, wgrad)
+    else:
+        why, kernels = spec.prepare(pred, yy, wgrad)
     if why is not None:
         _last_route = "fallback:" + why
         return spec.call(pred, boundary, yy).pow(2).mean()
-    if wgrad and spec.trains_kernel():
-        _last_route = "fused:" + spec.kind + "+wgrad"
-        return _KernelLossFn.apply(pred, spec.ops[0].kernel, spec, kernels, None if yy is None else yy.detach(),
-                                   bool(boundary), False, None)
-    _last_route = "fused:" + spec.kind
-    return _LossFn.apply(pred, spec, kernels, None if yy is None else yy.detach(), bool(boundary))
+    trains = wgrad and spec.trains_kernel()
+    _last_route = "fused:" + ("flat_" if flat else "") + spec.kind + ("+wgrad" if trains else "")
+    return _LossFn.apply(pred, spec.ops[0].kernel if trains else None, spec, kernels, data, bool(boundary), flat, r)
 
 
 def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False):
@@ -618,28 +435,25 @@ def kernel_vjp(residual_method, vars, g, boundary=False, minus=None):
     _check_like(g, vars, "g", spec.out_shape(vars, boundary))
     if minus is not None:
         _check_like(minus, vars, "minus")
-    kernel = (spec.method if spec.is_op else spec.obj.D).kernel
+    kernel = spec.ops[0].kernel
     why = spec.why
     if why is None:
         if not vars.is_cuda:
             why = "input on the CPU"
         elif vars.numel() == 0:
             why = "empty input"
-        elif getattr(spec.obj, "fused", True) is False:
-            why = "fused=False"
-        elif isinstance(spec.obj, R.PRE_Wave) and vars.dim() == 5 and vars.shape[1] != 1:
-            why = "multi-channel wave input"
-        elif any(s not in (1, 3) for s in kernel.shape) or kernel.dim() != spec.nd:
-            why = "operator kernel extents other than 1 and 3"
         else:
-            f = spec.fields(vars)[0]
-            m = None if minus is None else spec.fields(minus)[0]
-            if not (all(v.stride(-1) == 1 for v in (f, m) if v is not None) or
-                    (spec.nd == 3 and all(v.stride(1) == 1 for v in (f, m) if v is not None))):
-                why = "no unit stride on the last axis or on Nt"
+            why = spec.declined(vars, kernel_trains=True)
+    if why is None:
+        f = spec.fields(vars)[0]
+        m = None if minus is None else spec.fields(minus)[0]
+        if any(s not in (1, 3) for s in kernel.shape) or kernel.dim() != spec.nd:
+            why = "operator kernel extents other than 1 and 3"
+        elif not (all(v.stride(-1) == 1 for v in (f, m) if v is not None) or
+                  (spec.nd == 3 and all(v.stride(1) == 1 for v in (f, m) if v is not None))):
+            why = "no unit stride on the last axis or on Nt"
     if why is not None:
         _last_route = "fallback:" + why
-        spec.ops = (spec.method if spec.is_op else spec.obj.D,)          # (a spectral operator resolves to no kind)
         return _recompute_kernel_grad(spec, vars, minus, boundary, g).to(kernel.device)
     flat = f.stride(-1) != 1
     _last_route = "fused:" + ("flat_" if flat else "") + spec.kind + "+wgrad"

@@ -34,9 +34,13 @@ Nt-fastest views of the 2-D residuals - ``pred.permute(0,1,4,2,3)`` of the surro
 ``Joint/NS_Residuals_CP.py:282-305`` and ``Joint/MHD_Residuals_CP.py:326-346`` pass - have a fused route as well
 (``libcp_pre_screenflat.so``, ``include/cp_pre_screenflat.h``): the merged-row march of the residual pass's flat form with
 the same end of a plane.  Routes ``fused:flat_<kind>``; taken when the rows are dense (``stride(Ny) == Nt``), ``Ny*Nt`` is a
-multiple of 4 and ``Nt < 96``, else the three-pass route says why.  ``halo_x`` on such a view behaves as before.
+multiple of 4 and ``Nt < FLAT_MAX_NT``, else the three-pass route says why.  ``halo_x`` on such a view behaves as before.
 
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
+
+Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
+``_method.Method`` (shared with ``losses``); ``_Spec`` adds the kinds that have a fused screen, the order of the reasons of
+``prepare`` / ``prepare_flat`` / ``prepare_rows`` and ONE launcher for the three libraries (``launch``, by ``form``).
 """
 from __future__ import annotations
 
@@ -48,9 +52,7 @@ import torch
 from . import _dispatch, _lib
 from . import inductive_cp as icp
 from . import residuals as R
-from .convops_1d import ConvOperator as ConvOperator1D
-from .convops_2d import ConvOperator as ConvOperator2D
-from .losses import _is_star
+from ._method import FLAT_MAX_NT, MHD_EQ, Method
 
 _last_route = None
 
@@ -102,74 +104,41 @@ class Screened:
 
 
 # ------------------------------------------------------------------------------------------- what a method is
-_MHD_EQ = {"residual_continuity": 0, "residual_momentum": 1, "residual_energy": 2, "residual_induction": 3}
-_MHD_CHAN = {0: (0, 1, 2), 1: tuple(range(6)), 2: tuple(range(6)), 3: (1, 2, 4, 5)}
+def _input_declined(x, minus, qhats, modulation):
+    """What keeps a call from every fused screen, whatever the method and the layout, or None."""
+    if minus is not None:
+        return "minus="
+    if not x.is_cuda:
+        return "input on the CPU"
+    if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
+        return "float64 levels or modulation"
+    return None
 
 
-class _Spec:
-    """One residual method, resolved as ``losses._Spec`` resolves it: ``kind`` (None: no fused screen), ``chan`` - the
-    channels of a stacked ``[BS,F,...]`` input the residual reads (None: the input is the field itself), ``rows_kind`` -
-    the fused screen of the 1-D family ('stencil2d', 'burgers'; None: none), which ``kind`` and ``why`` do not speak of."""
+# form of the fused screen -> (its loader in ``_lib``, the prefix of its entry points, the prefix of its route)
+_FORMS = {"": ("load_screen", "pre_screen_", ""), "flat": ("load_screenflat", "pre_screenflat_", "flat_"),
+          "rows": ("load_screen1d", "pre_screen1d_", "rows_")}
+# the four MHD kinds share ONE entry point, pre_screen[flat]_mhd_f32: kind -> the ``eq`` it takes first
+_MHD_EQ = {"mhd_" + e: i for i, e in enumerate(MHD_EQ)}
+
+
+class _Spec(Method):
+    """One residual method, resolved (``_method.Method``) for the fused screens: ``kind`` (None: no fused screen of the
+    2-D family), ``chan`` - the channels of a stacked ``[BS,F,...]`` input the residual reads (None: the input is the field
+    itself), ``rows_kind`` - the fused screen of the 1-D family ('stencil2d', 'burgers'; None: none), which ``kind`` and
+    ``why`` do not speak of; ``eq`` (the MHD equations) and ``ratio`` (``linear2``) as the launches take them."""
+    KIND = {"op3d": "stencil3d", "wave": "stencil3d", "ns_momentum": "ns_momentum", "ns_continuity": "linear2",
+            "mhd_gauss": "linear2", **{k: k for k in _MHD_EQ}}
+    ROWS_KIND = {"op2d": "stencil2d", "advection": "stencil2d", "burgers": "burgers"}
+    WHY = {"spectral": "spectral operator", "jorek": "no fused screen for JOREK",
+           **dict.fromkeys(ROWS_KIND, "1-D family: the marched axis is the batch")}
 
     def __init__(self, method):
-        self.method, self.kind, self.why, self.chan, self.nd, self.ops = method, None, None, None, 3, ()
-        self.rows_kind = None
-        self.is_op = isinstance(method, (ConvOperator1D, ConvOperator2D))
-        obj = method if self.is_op else getattr(method, "__self__", None)
-        name = getattr(method, "__name__", "")
-        self.obj = obj
-        if self.is_op:
-            self.nd = 2 if isinstance(method, ConvOperator1D) else 3
-            if getattr(method, "conv", None) != method.convolution:
-                self.why = "spectral operator"
-            elif self.nd == 2:
-                self.why = "1-D family: the marched axis is the batch"
-                self.rows_kind, self.ops = "stencil2d", (method,)
-            else:
-                self.kind, self.ops = "stencil3d", (method,)
-        elif obj is None or not callable(method):
-            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
-        elif isinstance(obj, R.NavierStokes) and name in ("residual_momentum", "residual"):
-            self.kind, self.chan, self.ops = "ns_momentum", (0, 1, 2), (obj.D_t, obj.D_x, obj.D_y, obj.D_xx_yy)
-        elif isinstance(obj, R.NavierStokes) and name == "residual_continuity":
-            self.kind, self.chan, self.ops, self.ratio = "linear2", (0, 1), (obj.D_x, obj.D_y), obj.dx / obj.dy
-        elif isinstance(obj, R.MHD) and name == "residual_gauss":
-            self.kind, self.chan, self.ops, self.ratio = "linear2", (4, 5), (obj.D_x, obj.D_y), 1.0
-        elif isinstance(obj, R.MHD) and (name in _MHD_EQ or name == "residual"):
-            self.eq = _MHD_EQ.get(name, 3)                        # (PRE_MHD.residual is the induction equation)
-            self.kind = "mhd_" + ("continuity", "momentum", "energy", "induction")[self.eq]
-            self.chan, self.ops = _MHD_CHAN[self.eq], (obj.D_t, obj.D_x, obj.D_y)
-        elif isinstance(obj, R.PRE_Wave) and name == "residual":
-            self.kind, self.ops = "stencil3d", (obj.D,)
-        elif isinstance(obj, (R.Burgers, R.Advection)) and name == "residual":
-            self.nd, self.why = 2, "1-D family: the marched axis is the batch"
-            if isinstance(obj, R.Burgers):
-                self.rows_kind, self.ops = "burgers", (obj.D_t, obj.D_x, obj.D_xx)
-            else:
-                self.rows_kind, self.ops = "stencil2d", (obj.D,)
-        elif isinstance(obj, R.JOREK) and name in ("residual_continuity", "residual_temperature"):
-            self.why, self.chan = "no fused screen for JOREK", ()
-        else:
-            raise TypeError("residual_method must be a bound residual method of cp_pre_amd.residuals or a ConvOperator")
-
-    def field_shape(self, x):
-        """Shape of the uncropped residual of input ``x``; raises on a rank the method does not take."""
-        if isinstance(self.obj, R.JOREK):
-            if x.dim() != 5:
-                raise ValueError(f"expected vars [BS,F,Nx,Ny,Nt], got {tuple(x.shape)}")
-            return (x.shape[0], x.shape[4], x.shape[2], x.shape[3])
-        if self.chan is not None:
-            need = max(self.chan) + 1
-            if x.dim() != 5 or x.shape[1] < need:
-                raise ValueError(f"expected vars [BS,F>={need},Nt,Nx,Ny], got {tuple(x.shape)}")
-            return (x.shape[0],) + tuple(x.shape[2:])
-        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5:
-            return (x.shape[0],) + tuple(x.shape[2:])
-        if self.rows_kind is not None and x.dim() == 4 and x.shape[1] == 1:
-            return (x.shape[0],) + tuple(x.shape[2:])             # ([BS,1,Nt,Nx]: screened as x[:, 0], three-pass)
-        if x.dim() != self.nd + 1:
-            raise ValueError(f"expected a {self.nd + 1}-D field, got {tuple(x.shape)}")
-        return tuple(x.shape)
+        super().__init__(method)
+        if self.kind == "linear2":
+            self.ratio, = self.scalars()
+        elif self.kind in _MHD_EQ:
+            self.eq = _MHD_EQ[self.kind]
 
     def reads_halo(self):
         """Does the method's own residual pass take ``halo_x``?  (A ``ConvOperator`` call, NS continuity and MHD gauss do
@@ -191,163 +160,93 @@ class _Spec:
                 return r if minus is None else r - self.method(minus)
             return self.method(x, boundary=True, **kw)
 
-    def fields(self, x):
-        if self.chan is None:
-            return [x[:, 0] if x.dim() == 5 else x]
-        return [x[:, i] for i in self.chan]
+    # -------- can a fused screen run?  input, then layout, then what declines whatever the layout, then the kernels
+    def _prepare(self, layout, kind, points, x, minus, qhats, modulation):
+        why = _input_declined(x, minus, qhats, modulation) or layout(x) or self.declined(x)
+        if why is None and kind in _MHD_EQ and x.shape[1] < 6:
+            why = "fewer than six MHD channels"                  # (pre_screen_mhd_f32 takes the six views)
+        return (why, ()) if why is not None else self.star_kernels(kind, points)
 
     def prepare(self, x, minus, qhats, modulation):
         """(why, kernels): ``why`` is None if the fused screen can run; host checks and one download of the operator
         kernels (``_dispatch.host_kernel`` on every call: a screen applies the kernels its operators hold now)."""
         if self.kind is None:
             return self.why, ()
-        if minus is not None:
-            return "minus=", ()
-        if not x.is_cuda:
-            return "input on the CPU", ()
-        if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
-            return "float64 levels or modulation", ()
-        if x.stride(-1) != 1:
-            return "no unit stride on the last axis", ()
-        if x.shape[-1] % 4 != 0:
-            return "row width not a multiple of 4", ()
-        if getattr(self.obj, "fused", True) is False:
-            return "fused=False", ()
-        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
-            return "operator kernel requires grad", ()
-        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
-            return "multi-channel wave input", ()
-        if self.kind.startswith("mhd_") and x.shape[1] < 6:
-            return "fewer than six MHD channels", ()              # (pre_screen_mhd_f32 takes the six views)
-        return self._star_kernels()
+        return self._prepare(self._layout, self.kind, 7, x, minus, qhats, modulation)
 
-    def _star_kernels(self):
-        """(why, kernels) of the 2-D family: one download of the operator kernels, all weight on the 7-point star."""
-        ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
-        if self.kind == "stencil3d":
-            if ks[0].ndim != 3 or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
-                return "operator kernel off the 7-point star", ()
-            w, off = _dispatch.taps_of(ks[0])
-            if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
-                return "operator kernel off the 7-point star", ()
-            return None, (w, off)
-        if any(k.shape != (3, 3, 3) or not _is_star(k) for k in ks):
-            return "operator kernel off the 7-point star", ()
-        return None, tuple(_lib.farr(k.reshape(-1)) for k in ks)
+    def prepare_flat(self, x, minus, qhats, modulation):
+        """``prepare`` for the fused screen of Nt-fastest views (``nt_fastest(x)``): (why, kernels)."""
+        return self._prepare(self._layout_flat, self.kind, 7, x, minus, qhats, modulation)
+
+    def prepare_rows(self, x, minus, qhats, modulation):
+        """``prepare`` for the fused screen of the 1-D family (``rows_kind``): (why, kernels)."""
+        return self._prepare(self._layout_rows, self.rows_kind, 5, x, minus, qhats, modulation)
+
+    @staticmethod
+    def _layout(x):
+        if x.stride(-1) != 1:
+            return "no unit stride on the last axis"
+        if x.shape[-1] % 4 != 0:
+            return "row width not a multiple of 4"
+        return None
 
     def nt_fastest(self, x):
         """Is ``x`` an Nt-fastest view of a 2-D residual's input (unit stride on Nt, not on Ny)?"""
         return self.kind is not None and x.dim() >= 4 and x.stride(-3) == 1 and x.stride(-1) != 1
 
-    def prepare_flat(self, x, minus, qhats, modulation):
-        """``prepare`` for the fused screen of Nt-fastest views (``nt_fastest(x)``): (why, kernels)."""
-        if minus is not None:
-            return "minus=", ()
-        if not x.is_cuda:
-            return "input on the CPU", ()
-        if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
-            return "float64 levels or modulation", ()
+    @staticmethod
+    def _layout_flat(x):
         T, Y = x.shape[-3], x.shape[-1]
-        if T >= 96:
-            return "Nt >= 96", ()                                   # (FLAT_MAX_Y: the residual pass leaves its flat form there too)
+        if T >= FLAT_MAX_NT:
+            return "Nt >= %d" % FLAT_MAX_NT                       # (the residual pass leaves its flat form there too)
         if (Y * T) % 4 != 0:
-            return "merged row Ny*Nt not a multiple of 4", ()
+            return "merged row Ny*Nt not a multiple of 4"
         if Y <= 1 or x.stride(-1) != T:
-            return "rows not dense", ()                               # (a t-slab of an Nt-fastest tensor)
-        if getattr(self.obj, "fused", True) is False:
-            return "fused=False", ()
-        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
-            return "operator kernel requires grad", ()
-        if isinstance(self.obj, R.PRE_Wave) and x.dim() == 5 and x.shape[1] != 1:
-            return "multi-channel wave input", ()
-        if self.kind.startswith("mhd_") and x.shape[1] < 6:
-            return "fewer than six MHD channels", ()
-        return self._star_kernels()
+            return "rows not dense"                               # (a t-slab of an Nt-fastest tensor)
+        return None
+
+    @staticmethod
+    def _layout_rows(x):
+        if x.dim() == 4:
+            return "[BS,1,Nt,Nx] input"
+        if x.stride(2) != 1 and x.stride(1) != 1:
+            return "no unit-stride axis"
+        if x.shape[2 if x.stride(2) == 1 else 1] % 4 != 0:
+            return "contiguous-axis length not a multiple of 4"
+        return None
+
+    # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
+    def entry(self, form):
+        """The entry point of this method's fused screen in the library of ``form``."""
+        kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
+        return _FORMS[form][1] + kind + "_f32"
+
+    def route(self, form):
+        return "fused:" + _FORMS[form][2] + (self.rows_kind if form == "rows" else self.kind)
+
+    def launch(self, kernels, x, st, flags, form=""):
+        """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code."""
+        assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
+        lib = getattr(_lib, _FORMS[form][0])()
+        kind = self.rows_kind if form == "rows" else self.kind
+        if form == "rows":
+            views, shape = (_lib.ptr(x), _lib.iarr64(x.stride())), x.shape
+        else:
+            fs = self.fields(x)
+            shape = fs[0].shape
+            if kind in _MHD_EQ:
+                views = (self.eq, R._arr([x[:, i] for i in range(6)]))
+            else:
+                views = [ctypes.byref(_lib.field(f)) for f in fs]
+        if kind.startswith("stencil"):
+            kernels = _dispatch.tap_args(*kernels)
+        return getattr(lib, self.entry(form))(*views, *kernels, *self.scalars(), ctypes.byref(st), *shape, flags, _lib.stream())
 
     def launch_flat(self, kernels, x, st, flags):
-        """The fused launch on Nt-fastest device views; returns the library's code."""
-        lib = _lib.load_screenflat()
-        fs = self.fields(x)
-        tail = (ctypes.byref(st), *fs[0].shape, flags, _lib.stream())
-        if self.kind == "stencil3d":
-            w, off = kernels
-            wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
-            ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
-            return lib.pre_screenflat_stencil3d_f32(ctypes.byref(_lib.field(fs[0])), wv, ov, len(w), *tail)
-        if self.kind == "linear2":
-            return lib.pre_screenflat_linear2_f32(ctypes.byref(_lib.field(fs[0])), ctypes.byref(_lib.field(fs[1])), *kernels,
-                                                  float(self.ratio), *tail)
-        if self.kind == "ns_momentum":
-            o = self.obj
-            return lib.pre_screenflat_ns_momentum_f32(*[ctypes.byref(_lib.field(f)) for f in fs], *kernels, float(o.dt),
-                                                      float(o.dx), float(o.dy), float(o.nu), *tail)
-        six = R._arr([x[:, i] for i in range(6)])
-        return lib.pre_screenflat_mhd_f32(self.eq, six, *kernels, float(self.obj.gamma), *tail)
-
-    def prepare_rows(self, x, minus, qhats, modulation):
-        """``prepare`` for the fused screen of the 1-D family (``rows_kind``): (why, kernels)."""
-        if minus is not None:
-            return "minus=", ()
-        if not x.is_cuda:
-            return "input on the CPU", ()
-        if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
-            return "float64 levels or modulation", ()
-        if x.dim() == 4:
-            return "[BS,1,Nt,Nx] input", ()
-        if x.stride(2) != 1 and x.stride(1) != 1:
-            return "no unit-stride axis", ()
-        if x.shape[2 if x.stride(2) == 1 else 1] % 4 != 0:
-            return "contiguous-axis length not a multiple of 4", ()
-        if getattr(self.obj, "fused", True) is False:
-            return "fused=False", ()
-        if _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):
-            return "operator kernel requires grad", ()
-        ks = [_dispatch.host_kernel(o.kernel) for o in self.ops]
-        if self.rows_kind == "stencil2d":
-            if ks[0].ndim != 2 or any(s > 3 or s % 2 == 0 for s in ks[0].shape):
-                return "operator kernel off the 5-point star", ()
-            w, off = _dispatch.taps_of(ks[0])
-            if len(off) and (np.count_nonzero(off, axis=1) > 1).any():
-                return "operator kernel off the 5-point star", ()
-            return None, (w, off)
-        if any(k.shape != (3, 3) or k[0, 0] or k[0, 2] or k[2, 0] or k[2, 2] for k in ks):
-            return "operator kernel off the 5-point star", ()
-        return None, tuple(_lib.farr(k.reshape(-1)) for k in ks)
+        return self.launch(kernels, x, st, flags, "flat")
 
     def launch_rows(self, kernels, x, st, flags):
-        """The fused launch of the 1-D family on a [BS,Nt,Nx] device view; returns the library's code."""
-        lib = _lib.load_screen1d()
-        head = (_lib.ptr(x), _lib.iarr64(x.stride()))
-        tail = (ctypes.byref(st), *x.shape, flags, _lib.stream())
-        if self.rows_kind == "stencil2d":
-            w, off = kernels
-            wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
-            ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
-            return lib.pre_screen1d_stencil2d_f32(*head, wv, ov, len(w), *tail)
-        o = self.obj
-        return lib.pre_screen1d_burgers_f32(*head, *kernels, float(o.dx), float(o.dt), float(o.nu), float(2 * o.dt / o.dx),
-                                            *tail)               # (2 dt / dx in fp32, as Burgers.residual)
-
-    def launch(self, kernels, x, st, flags):
-        """The fused launch on device views; returns the library's code."""
-        lib = _lib.load_screen()
-        fs = self.fields(x)
-        shape = tuple(fs[0].shape)
-        tail = (ctypes.byref(st), *shape, flags, _lib.stream())
-        if self.kind == "stencil3d":
-            w, off = kernels
-            wv = _lib.farr(w) if len(w) else (ctypes.c_float * 1)()
-            ov = _lib.iarr32(off.reshape(-1)) if len(w) else (ctypes.c_int32 * 1)()
-            return lib.pre_screen_stencil3d_f32(ctypes.byref(_lib.field(fs[0])), wv, ov, len(w), *tail)
-        if self.kind == "linear2":
-            return lib.pre_screen_linear2_f32(ctypes.byref(_lib.field(fs[0])), ctypes.byref(_lib.field(fs[1])), *kernels,
-                                              float(self.ratio), *tail)
-        if self.kind == "ns_momentum":
-            o = self.obj
-            return lib.pre_screen_ns_momentum_f32(*[ctypes.byref(_lib.field(f)) for f in fs], *kernels, float(o.dt), float(o.dx),
-                                                  float(o.dy), float(o.nu), *tail)
-        six = R._arr([x[:, i] for i in range(6)])
-        return lib.pre_screen_mhd_f32(self.eq, six, *kernels, float(self.obj.gamma), *tail)
+        return self.launch(kernels, x, st, flags, "rows")
 
 
 # ------------------------------------------------------------------------------------------- validation (host only)
@@ -462,21 +361,16 @@ class Screen:
                 st = _lib.PreScreen(_lib.ptr(q), self.nk, _lib.ptr(mod), mod.stride(0) if mod is not None else 0,
                                     mod.stride(1) if mod is not None else 0, crop[0], crop[1], 0 if rows else crop[2],
                                     ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
+            form = "rows" if rows else "flat" if flat else ""
             with torch.no_grad(), torch.cuda.device(vars_slab.device):
-                if rows:
-                    rc = spec.launch_rows(kernels, vars_slab, st, 0)
-                elif flat:
-                    rc = spec.launch_flat(kernels, vars_slab, st, 0)
-                else:
-                    rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0)
+                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x and form == "" else 0, form)
             if rc == _lib.PRE_E_UNSUPPORTED:
                 why = "declined by the library"
                 if halo_x and not spec.reads_halo():
                     raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
             else:
-                _lib.check(rc, "pre_screen1d_" + spec.rows_kind + "_f32" if rows else
-                           ("pre_screenflat_" if flat else "pre_screen_") + spec.kind.split("_")[0] + "_f32")
-                _last_route = "fused:" + ("rows_" + spec.rows_kind if rows else "flat_" + spec.kind if flat else spec.kind)
+                _lib.check(rc, spec.entry(form))
+                _last_route = spec.route(form)
                 self.cells += cells
                 return
         _last_route = "fallback:" + why
