@@ -285,6 +285,20 @@ CNSVJP_SIGNATURES = {
                         c_float] + [c_int64] * 3 + [c_int, c_void_p],
 }
 
+# libcp_pre_vjpmhd.so (include/cp_pre_vjpmhd.h): the vector-Jacobian products of the ideal-MHD residuals (the march of libcp_pre_vjp.so)
+VJPMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpmhd.so")
+PRE_VJPMHD_ABI_VERSION = 1
+_mhdvjp = [_fld, POINTER(PreField), POINTER(PreField)] + [POINTER(c_float)] * 3          # g, fields, out, K_t, K_x, K_y
+_mhdtail = _scale + [c_int64] * 4 + [c_int, c_void_p]
+VJPMHD_SIGNATURES = {
+    "pre_vjpmhd_abi_version": [],
+    "pre_vjpmhd_supported": [c_int] + [POINTER(c_float)] * 3,
+    "pre_vjpmhd_continuity_f32": _mhdvjp + _mhdtail,
+    "pre_vjpmhd_induction_f32": _mhdvjp + _mhdtail,
+    "pre_vjpmhd_momentum_f32": _mhdvjp + _mhdtail,
+    "pre_vjpmhd_energy_f32": _mhdvjp + [c_double] + _mhdtail,
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -311,8 +325,9 @@ _LIBS_MORE = {
     "wgrad": ("_wgrad", "WGRAD_", "pre_wgrad_abi_version", "PRE_WGRAD_ABI_VERSION", ()),
     "cns": ("_cns", "CNS_", "pre_cns_abi_version", "PRE_CNS_ABI_VERSION", ()),
     "cnsvjp": ("_cnsvjp", "CNSVJP_", "pre_cnsvjp_abi_version", "PRE_CNSVJP_ABI_VERSION", ()),
+    "vjpmhd": ("_vjpmhd", "VJPMHD_", "pre_vjpmhd_abi_version", "PRE_VJPMHD_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -405,6 +420,10 @@ def load_cns():
 
 def load_cnsvjp():
     return _cnsvjp or _load("cnsvjp")
+
+
+def load_vjpmhd():
+    return _vjpmhd or _load("vjpmhd")
 
 
 def require_gpu():

@@ -48,6 +48,16 @@ same ``backward`` ONE launch of ``pre_wgrad_stencil3d_f32`` (``include/cp_pre_wg
 Burgers (several operators, or a non-linear residual), any residual where several operator kernels require grad, and
 ``residual_vjp`` keep ``fallback:operator kernel requires grad``.  ``kernel_vjp`` is the same launch for a general g.
 
+``mhd=True`` (off by default: nothing above changes, ``libcp_pre_vjpmhd.so`` is never loaded) gives the ideal-MHD residuals
+a fused backward pass (``include/cp_pre_vjpmhd.h``): on a CUDA ``[BS,F>=6,Nt,Nx,Ny]`` input with unit stride on Ny,
+``MHD.residual_continuity`` and ``residual_induction`` (``PRE_MHD.residual``) are ONE launch, ``residual_momentum`` and
+``residual_energy`` TWO, split by output group (in one they need scratch), ``residual_gauss`` is ``pre_vjp_linear2_f32``.
+Routes ``fused:mhd_continuity``, ``fused:mhd_induction``, ``fused:mhd_momentum``, ``fused:mhd_energy``, ``fused:linear2``.
+The forward pass is the fused MHD residual as before.  The kernels are built for the tap structures of the forward march;
+with operators that are general stars only momentum is built, the others take ``fallback:declined by the library``.
+Together with ``flat=True`` an Nt-fastest input takes ``fallback:no flat VJP for MHD``.  The channels an equation does not
+read get a zero gradient.
+
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
 ``_method.Method`` (shared with ``screen``); ``_Spec`` adds the kinds that have a fused VJP, the order of the reasons of
 ``prepare`` / ``prepare_flat`` and ONE launcher (``vjp``; ``flat=True``: the merged-row library).  ``_LossFn`` is the one
@@ -61,14 +71,14 @@ import torch
 
 from . import _dispatch, _lib
 from . import residuals as R
-from ._method import FLAT_MAX_NT, JOREK_ROWS, MHD_ROWS, Method
+from ._method import FLAT_MAX_NT, JOREK_ROWS, MHD_EQ, MHD_ROWS, Method
 
 _last_route = None
 
 
 def last_route():
     """'fused:<kind>' (kind: stencil3d, stencil2d, linear2, burgers, ns_momentum; with ``flat=True`` also flat_stencil3d,
-    flat_linear2, flat_ns_momentum) or 'fallback:<why>' of the last ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
+    flat_linear2, flat_ns_momentum; with ``mhd=True`` also mhd_continuity, mhd_induction, mhd_momentum, mhd_energy) or 'fallback:<why>' of the last ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
     return _last_route
 
 
@@ -80,9 +90,14 @@ class _Spec(Method):
     KIND = {"op3d": "stencil3d", "op2d": "stencil2d", "wave": "stencil3d", "advection": "stencil2d",
             "ns_momentum": "ns_momentum", "ns_continuity": "linear2", "burgers": "burgers"}
     WHY = {"spectral": "spectral operator", **dict.fromkeys(MHD_ROWS + JOREK_ROWS, "no fused VJP for {cls}")}
+    # ``mhd=True``: the kinds of libcp_pre_vjpmhd.so (gauss is two linear operators: ``pre_vjp_linear2_f32``)
+    MHD_KIND = {**{"mhd_" + e: "mhd_" + e for e in MHD_EQ}, "mhd_gauss": "linear2"}
 
-    def __init__(self, method):
+    def __init__(self, method, mhd=False):
         super().__init__(method)
+        self.mhd = bool(mhd) and self.row in self.MHD_KIND
+        if self.mhd:
+            self.kind, self.why = self.MHD_KIND[self.row], None
         if self.kind is None and not self.is_op:
             self.chan, self.ops = (), ()                         # (no launch reads them: a stacked input, shapes not checked here)
 
@@ -124,7 +139,14 @@ class _Spec(Method):
         if x.stride(-1) != 1 or (minus is not None and minus.stride(-1) != 1):
             return "no unit stride on the last axis", ()
         why = self.declined(x, minus, wgrad and self.trains_kernel())
-        return (why, ()) if why is not None else self.star_kernels(self.kind)
+        if why is not None:
+            return why, ()
+        why, kernels = self.star_kernels(self.kind)
+        if why is None and self.kind.startswith("mhd_"):         # a tap structure the library has no instantiation for
+            eq = MHD_EQ.index(self.kind[4:])
+            if _lib.load_vjpmhd().pre_vjpmhd_supported(eq, *kernels) == _lib.PRE_E_UNSUPPORTED:
+                return "declined by the library", ()
+        return why, kernels
 
     def trains_kernel(self):
         """Is this ONE linear operator whose kernel requires grad - what ``wgrad=True`` hands to ``pre_wgrad_stencil3d_f32``?"""
@@ -140,6 +162,8 @@ class _Spec(Method):
         library's own (include/cp_pre_vjpflat.h), stated here so that the reason has a name."""
         if self.kind is None:
             return self.why, ()
+        if self.mhd:
+            return "no flat VJP for MHD", ()
         if self.nd != 3:
             return "no flat VJP for the 1-D family", ()
         why = self.declined(x, minus, wgrad and self.trains_kernel())
@@ -162,15 +186,19 @@ class _Spec(Method):
         """``kernels``: what ``prepare`` returned; ``gfull`` [BS,*field] (copied unless its last axis has unit stride).
         ``flat``: the merged-row launch - ``kernels``: what ``prepare_flat`` returned; ``gfull`` [BS,Nt,Nx,Ny], dense in
         memory order [BS,Nx,Ny,Nt]; the gradient is dense in ``x``'s memory order.  None if the library declines."""
-        lib = _lib.load_vjpflat() if flat else _lib.load_vjp()
-        name = ("pre_vjpflat_" if flat else "pre_vjp_") + self.kind + "_f32"
+        mhd = self.kind.startswith("mhd_")
+        lib = _lib.load_vjpflat() if flat else _lib.load_vjpmhd() if mhd else _lib.load_vjp()
+        name = ("pre_vjpmhd_" + self.kind[4:] if mhd else ("pre_vjpflat_" if flat else "pre_vjp_") + self.kind) + "_f32"
+        scalars = self.scalars() if not mhd or self.kind == "mhd_energy" else ()
         grad = _lib.empty_like_layout(x) if flat else torch.empty(x.shape, dtype=torch.float32, device=x.device)
         if not flat and gfull.stride(-1) != 1:
             gfull = gfull.contiguous()
         if self.kind == "ns_momentum":
             views = [gfull, R._arr([x[:, 0], x[:, 1]]), R._arr([grad[:, 0], grad[:, 1], grad[:, 2]])]
+        elif mhd:                                        # the fields the equation reads, a gradient slot for each
+            views = [gfull, R._arr([x[:, c] for c in self.chan]), R._arr([grad[:, c] for c in self.chan])]
         elif self.kind == "linear2":
-            views = [gfull, R._arr([grad[:, 0], grad[:, 1]])]
+            views = [gfull, R._arr([grad[:, c] for c in self.chan])]
         elif self.kind == "burgers":
             views = [gfull, x, grad]
         else:
@@ -180,12 +208,15 @@ class _Spec(Method):
         else:
             args = [a for v in views for a in (_lib.ptr(v), _lib.iarr64(v.stride()))]
         with torch.cuda.device(x.device):
-            rc = getattr(lib, name)(*args, *kernels, *self.scalars(), float(host_scale), _lib.ptr(dev_scale), *gfull.shape,
+            rc = getattr(lib, name)(*args, *kernels, *scalars, float(host_scale), _lib.ptr(dev_scale), *gfull.shape,
                                     _lib.PRE_VJP_CROP if crop else 0, _lib.stream())
         if rc == _lib.PRE_E_UNSUPPORTED:
             return None
         _lib.check(rc, name)
-        if self.chan is not None and x.shape[1] > len(self.chan):
+        if self.chan is not None and self.chan != tuple(range(len(self.chan))):
+            for c in set(range(x.shape[1])) - set(self.chan):      # (MHD induction, gauss: the channels read are no prefix)
+                grad[:, c].zero_()
+        elif self.chan is not None and x.shape[1] > len(self.chan):
             grad[:, len(self.chan):].zero_()                       # (after the launch, which writes the other channels)
         return grad
 
@@ -328,9 +359,9 @@ class _LossFn(torch.autograd.Function):
         return grad, gk, None, None, None, None, None, None
 
 
-def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False):
+def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False, mhd=False):
     global _last_route
-    spec = _Spec(residual_method)
+    spec = _Spec(residual_method, mhd)
     _check_tensor(pred, "pred")
     spec.field_shape(pred)                               # (called for its raise: a rank the method does not take)
     if yy is not None:
@@ -353,7 +384,7 @@ def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False):
     return _LossFn.apply(pred, spec.ops[0].kernel if trains else None, spec, kernels, data, bool(boundary), flat, r)
 
 
-def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False):
+def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False, mhd=False):
     """``residual_method(pred, boundary).pow(2).mean()`` (``PI_loss``, Physics_Informed/Wave_FNO_PISL.py:213-214) as a
     0-d fp32 tensor on ``pred``'s device, differentiable with respect to ``pred``.  ``residual_method``: a bound
     ``residual*`` method of a class of ``cp_pre_amd.residuals``, or a ``ConvOperator`` (2-D: [BS,Nt,Nx,Ny], 1-D:
@@ -363,24 +394,25 @@ def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False):
     single linear operator (a ``ConvOperator``, ``PRE_Wave.residual``, ``Advection.residual``) whose kernel requires grad
     keeps the fused route and gets ``kernel.grad`` from one launch of ``pre_wgrad_stencil3d_f32`` (route ``...+wgrad``);
     NS momentum, NS continuity, Burgers and any residual where several operator kernels require grad keep
-    ``fallback:operator kernel requires grad``."""
-    return _loss(residual_method, pred, None, boundary, flat, wgrad)
+    ``fallback:operator kernel requires grad``.  ``mhd=True``: the ideal-MHD residuals take the fused backward passes of
+    ``libcp_pre_vjpmhd.so`` (module docstring)."""
+    return _loss(residual_method, pred, None, boundary, flat, wgrad, mhd)
 
 
-def pisl_loss(residual_method, pred, yy, boundary=False, flat=False, wgrad=False):
+def pisl_loss(residual_method, pred, yy, boundary=False, flat=False, wgrad=False, mhd=False):
     """``(residual(pred) - residual(yy)).pow(2).mean()`` (``PISL``, Physics_Informed/Wave_FNO_PISL.py:216-217).  ``yy``
     (``pred``'s shape, dtype and device) is data: the fused route does not differentiate it (one that requires grad takes
-    the fallback, which does).  ``flat`` and ``wgrad`` as on ``pi_loss`` (the kernel gradient reads ``pred - yy``)."""
-    return _loss(residual_method, pred, yy, boundary, flat, wgrad)
+    the fallback, which does).  ``flat``, ``wgrad`` and ``mhd`` as on ``pi_loss`` (the kernel gradient reads ``pred - yy``)."""
+    return _loss(residual_method, pred, yy, boundary, flat, wgrad, mhd)
 
 
-def residual_vjp(residual_method, vars, g, boundary=False, flat=False):
+def residual_vjp(residual_method, vars, g, boundary=False, flat=False, mhd=False):
     """The vector-Jacobian product ``d <g, residual_method(vars, boundary)> / d vars`` for a general upstream gradient
     ``g`` (the shape of the method's result), by the kernels the losses use.  Returns a tensor of ``vars``' shape.
-    ``flat`` as on ``pi_loss`` (the gradient is then dense in ``vars``' memory order).  Operator kernels that require grad
-    take ``fallback:operator kernel requires grad`` here (their own gradient: ``kernel_vjp``)."""
+    ``flat`` and ``mhd`` as on ``pi_loss`` (``flat``: the gradient is then dense in ``vars``' memory order).  Operator
+    kernels that require grad take ``fallback:operator kernel requires grad`` here (their own gradient: ``kernel_vjp``)."""
     global _last_route
-    spec = _Spec(residual_method)
+    spec = _Spec(residual_method, mhd)
     _check_tensor(vars, "vars")
     _check_like(g, vars, "g", spec.out_shape(vars, boundary))
     if flat and spec.wants_flat(vars):

@@ -20,9 +20,17 @@ Cases ``wave_kgrad`` and ``wave_ntfast_kgrad`` are the shapes of ``wave`` and ``
 field VJP and ONE ``pre_wgrad_stencil3d_f32`` launch of ``libcp_pre_wgrad.so``) against the same call without ``wgrad`` (the
 route ``fallback:operator kernel requires grad``), alternating in one process.  They run only when named in --cases.
 
+Cases ``mhd_continuity``, ``mhd_induction``, ``mhd_momentum`` and ``mhd_energy`` time ``pi_loss(..., mhd=True)`` + ``backward()``
+(the fused backward of ``libcp_pre_vjpmhd.so``: one launch for continuity and induction, two for momentum and energy) against
+the same call with ``mhd=False`` (the parent's route, ``fallback:no fused VJP for MHD``: the composed expression under
+autograd) on a C4-shard-like [16,6,64,256,256], alternating in one process, with the peak memory of both; then the VJP
+launches alone (``residual_vjp`` with a full-grid g) against a device copy of the six fields timed in the same run and against
+the algorithmic bytes of the equation (28, 36, 56 and 60 B per cell).  They run only when named in --cases.
+
     python tools/loss_bench.py [--reps 7] [--warmup 2] [--out profiles/loss/loss_bench.txt] [--max-batch 16]
     python tools/loss_bench.py --cases wave_ntfast,ns_momentum_ntfast --out profiles/losses/loss_bench_ntfast.txt
     python tools/loss_bench.py --cases wave_kgrad,wave_ntfast_kgrad --out profiles/losses/loss_bench_kgrad.txt
+    python tools/loss_bench.py --cases mhd_continuity,mhd_induction,mhd_momentum,mhd_energy --out profiles/losses/loss_bench_mhd.txt
     rocprofv3 --kernel-trace --stats -- python tools/loss_bench.py --vjp-only      # the VJP kernel under the profiler
 """
 import argparse
@@ -157,6 +165,47 @@ def kgrad_case(name, bs, rand, reps, warmup, emit):
          f"{err:.2e}, max |dK True - False| / max = {kerr:.2e}")
 
 
+MHD_BYTES = {"continuity": 28, "induction": 36, "momentum": 56, "energy": 60}      # algorithmic bytes per cell of the VJP launches
+
+
+def mhd_case(name, bs, rand, reps, warmup, emit):
+    """``mhd=True`` against ``mhd=False`` (the parent's route) on [bs,6,64,256,256], interleaved; the VJP launches alone"""
+    eq = name[4:]
+    method = getattr(R.MHD(), "residual_" + eq)
+    pred = rand(bs, 6, 64, 256, 256).requires_grad_(True)
+    routes = {}
+
+    def step(mhd):
+        def f():
+            pred.grad = None
+            losses.pi_loss(method, pred, mhd=mhd).backward()
+            routes[mhd] = losses.last_route()
+        return f
+    a, b = step(True), step(False)
+    a()
+    ga = pred.grad.clone()
+    b()
+    err = float((ga - pred.grad).abs().max() / pred.grad.abs().max())
+    del ga
+    pa, pb = peak_of(a), peak_of(b)
+    (ma, la, ha), (mb, lb, hb) = alternate_spread([a, b], reps, warmup)
+    cells = pred.numel() // 6
+    field = cells * 4
+    emit(f"{name}: shape {list(pred.shape)}; mhd=True route {routes[True]} {ma:.3f} ms [{la:.3f}, {ha:.3f}], mhd=False route "
+         f"{routes[False]} {mb:.3f} ms [{lb:.3f}, {hb:.3f}], False/True = {mb / ma:.2f}x; peak memory mhd=True {pa / field:.2f} fields "
+         f"({pa / 2**30:.2f} GiB), mhd=False {pb / field:.2f} fields ({pb / 2**30:.2f} GiB); max |grad True - grad False| / max |grad False| "
+         f"= {err:.2e}")
+    pred.grad = None
+    vd, gg, dst = pred.detach(), rand(bs, 64, 256, 256), torch.empty_like(pred)
+    (mv, lv, hv), (mc, lc, hc) = alternate_spread([lambda: losses.residual_vjp(method, vd, gg, boundary=True, mhd=True),
+                                                   lambda: dst.copy_(vd)], reps, warmup)
+    nb = MHD_BYTES[eq] * cells
+    emit(f"{name} VJP launches alone (route fused:{name}, device events around the call, the zeroing of "
+         f"unread channels included): {mv:.3f} ms [{lv:.3f}, {hv:.3f}], {MHD_BYTES[eq]} B x {cells} cells / time = {nb / (mv * 1e-3) / 1e12:.2f} TB/s = "
+         f"{nb / (mv * 1e-3) / HBM:.3f} of 8 TB/s; device copy of the six fields (48 B per cell) {mc:.3f} ms [{lc:.3f}, {hc:.3f}] = "
+         f"{48 * cells / (mc * 1e-3) / 1e12:.2f} TB/s: the launches move their bytes at {nb / mv / (48 * cells / mc):.2f} of the copy's rate")
+
+
 def steps(method, v):
     def a():
         v.grad = None
@@ -177,7 +226,7 @@ def main():
     ap.add_argument("--vjp-only", action="store_true", help="only a few NS momentum VJP launches (for a profiler)")
     ap.add_argument("--cases", default="ns_momentum,burgers,wave",
                     help="comma-separated: ns_momentum, burgers, wave, wave_ntfast, ns_momentum_ntfast, wave_kgrad, "
-                         "wave_ntfast_kgrad")
+                         "wave_ntfast_kgrad, mhd_continuity, mhd_induction, mhd_momentum, mhd_energy")
     args = ap.parse_args()
     wanted = [c for c in args.cases.split(",") if c]
     assert torch.cuda.is_available(), "loss_bench needs the MI355X"
@@ -211,6 +260,9 @@ def main():
         ("wave", lambda bs: rand(bs, 64, 512, 512), R.PRE_Wave(0.01, 1 / 512).residual, args.max_batch, 5),
     ]
     for name in wanted:
+        if name.startswith("mhd_"):
+            mhd_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
+            torch.cuda.empty_cache()
         if name.endswith("_kgrad"):
             kgrad_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
             torch.cuda.empty_cache()
