@@ -46,6 +46,16 @@ inline bool plane_fits_int32(int64_t sX, int64_t X, int64_t Y)
     return e > -0x7fffffffLL && e < 0x7fffffffLL - Y;
 }
 
+// The marched kernels address a thread's place in one sample's plane as an UNSIGNED 32-bit byte offset into a buffer
+// descriptor: `rows` rows of stride sX >= 0 floats (the tile's overhang and the halo rows included), Y columns, and the 8
+// floats a quad and an edge scalar reach past their own cell.  True iff (rows * sX + Y + 8) * 4 < 2^32.
+inline bool plane_offsets_fit_u32(int64_t sX, int64_t rows, int64_t Y)
+{
+    int64_t e;
+    if (sX < 0 || rows < 0 || Y < 0 || __builtin_mul_overflow(rows, sX, &e) || __builtin_add_overflow(e, Y, &e)) return false;
+    return e < (int64_t)(1LL << 30) - 8;
+}
+
 // 16-byte loads and stores along the unit-stride axis: base, row stride and (B > 1) batch stride are whole quads
 inline bool aligned16(const void *ptr, int64_t sB, int64_t sX, int64_t B)
 {

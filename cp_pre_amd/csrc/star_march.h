@@ -41,6 +41,8 @@ struct Geom {
     int flags;
     int flat;                    // 1: short contiguous axis merged with the next one (flat_march_kernel)
     int tfree;                   // 1: no operator of the functor has a tap along the marched axis (set by the entry points)
+    int obuf;                    // 1 (MARCH_ST_SC1 only): a thread's place in an output plane fits a 32-bit byte offset, the residual
+                                 // leaves through a buffer descriptor with the write-through policy (set by launch_tiled / launch_flat)
 };
 
 // c, t-, t+, x-, x+, y-, y+
@@ -134,6 +136,7 @@ struct NSMomentum {    // Marginal/NS_Residuals_CP.py:231-240
     // spills 0-6 dwords and runs 4 waves/SIMD: +11 % (4.7-5.0 TB/s).  The same cap on the MHD induction kernel
     // (146 VGPRs, 17 dwords spilled) was -30 %: scratch traffic inside the plane loop.
     static constexpr int MIN_WAVES = MODE >= 3 ? 4 : 1;
+    static constexpr bool HALO_LEAD = MODE == 0;        // (the one tap structure it was measured on: 116 VGPRs, no scratch)
     static constexpr unsigned XMASK = xmask_of<MODE>(O_DT | O_DX | O_DY | O_LAP, O_DT | O_DX | O_DY | O_LAP, O_DX | O_DY);
     using Params = NSParams;
     static __device__ __forceinline__ float4 eval(const Nbr (&n)[3], const Params &p)
@@ -325,6 +328,22 @@ __device__ __forceinline__ float4 ldg4(const float *p)
 }
 __device__ __forceinline__ void stg4(float *p, const float4 &r) { *reinterpret_cast<F4u *>(p) = F4u{r.x, r.y, r.z, r.w}; }
 
+// The residual is written once and never read again inside the launch, yet a plain store leaves its line in the XCD's L2:
+// 8 KB per workgroup and plane step next to the 30 KB of input rows of which the neighbouring tiles want the outermost
+// two again.  MARCH_ST_SC1 (experiment): one 16-byte buffer store with the sc1 (write-through) policy, which does not keep
+// the line - through a wave-uniform descriptor of the output plane and the thread's 32-bit byte offset in it, as the loads
+// go; an output view too large for that offset keeps the plain store (Geom::obuf).  Measured +0.7 % on the x-slabs of NS
+// momentum and +-0.5 % elsewhere, and nothing on top of the halo lead (profiles/r07/README.md): not taken.
+#ifndef MARCH_ST_SC1
+#define MARCH_ST_SC1 0          // 0: plain stores through a 64-bit pointer
+#endif
+__device__ __forceinline__ void stb4_sc1(float *plane, unsigned int off, const float4 &r)
+{
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 v = {__float_as_uint(r.x), __float_as_uint(r.y), __float_as_uint(r.z), __float_as_uint(r.w)};
+    __builtin_amdgcn_raw_buffer_store_b128(v, __builtin_amdgcn_make_buffer_rsrc(plane, 0, -1, 0x00020000), (int)off, 0, 16);
+}
+
 // y-neighbours from the adjacent lane: the value of lane - 1 / lane + 1 of the 64-wide wave (a wave's first / last lane
 // gets something unspecified: the callers give those lanes their edge scalar).  MARCH_DPP: one `v_mov_b32_dpp wave_shr:1 /
 // wave_shl:1` each (gfx9 DPP wave shifts: tools/exp/dpp_probe.hip) instead of `__shfl_up / __shfl_down`, which compile to
@@ -407,10 +426,26 @@ struct NoBC {};
 #ifndef MARCH_COOP_MAXF
 #define MARCH_COOP_MAXF 4
 #endif
+#ifndef MARCH_HALO_AHEAD
+#define MARCH_HALO_AHEAD 1      // a plane's halo rows and edge scalars requested with its own cells, two planes ahead, into a third halo
+                                // set: 0 by no functor, 1 by those that ask (Fn::HALO_LEAD: NS momentum in the reference's tap structure,
+                                // -1.5 ... -1.8 % on the x-slabs), 2 by every functor of up to four fields (MHD induction +3.6 ... +4.2 %,
+                                // wave +-0, Burgers -1.4 %: profiles/r07/README.md)
+#endif
+#ifndef MARCH_NS16
+#define MARCH_NS16 0            // 1 (experiment): NS momentum in the reference's tap structure on tiles of 16 rows, 1024 threads, where the
+                                // grid has 16 rows: +1.9 ... +2.5 % on the x-slabs (profiles/r07/README.md)
+#endif
 
 // Fn::MIN_WAVES (optional): waves per SIMD the register allocator must leave room for
 template <class Fn, class = void> struct MinWaves { static constexpr int value = Fn::F >= 5 ? MARCH6_MINW : 1; };
 template <class Fn> struct MinWaves<Fn, std::void_t<decltype(Fn::MIN_WAVES)>> { static constexpr int value = Fn::MIN_WAVES; };
+
+// Fn::HALO_LEAD (optional): the functor's tiled march requests the halo with the own cells' lead (MARCH_HALO_AHEAD)
+template <class Fn, class = void> struct HaloLead { static constexpr bool value = MARCH_HALO_AHEAD == 2; };
+template <class Fn> struct HaloLead<Fn, std::void_t<decltype(Fn::HALO_LEAD)>> {
+    static constexpr bool value = MARCH_HALO_AHEAD == 2 || (MARCH_HALO_AHEAD == 1 && Fn::HALO_LEAD);
+};
 
 // Fn::XMASK (optional): the fields staged through LDS for their x-neighbours (default: all)
 template <class Fn, class = void> struct XMask { static constexpr unsigned value = (1u << Fn::F) - 1u; };
@@ -430,6 +465,9 @@ march_kernel(const Geom g, const typename Fn::Params prm, const typename std::co
     constexpr int F = Fn::F;
     using SX = Staged<Fn>;
     constexpr int AHEAD = (F >= 5 && MARCH6_AHEAD == 3) ? 3 : 2;       // planes between a plane's request and its use as t + 1
+    // three halo sets, requested AHEAD planes ahead (the boundary-condition instantiations hold a second edge scalar per field
+    // and set: they keep two sets)
+    constexpr bool HAL3 = HaloLead<Fn>::value && !BC && F <= MARCH_COOP_MAXF && AHEAD == 2;
     static_assert(NR >= 2, "tile needs at least two rows (top and bottom halo owners differ)");
     __shared__ float4 lds[2][SX::FX][NR + 2][TYQ];
 
@@ -511,7 +549,12 @@ march_kernel(const Geom g, const typename Fn::Params prm, const typename std::co
         voff[i] = (unsigned int)(((long long)(xl + 1) * g.sX[i] + y) * 4);
         hoff[i] = (unsigned int)(((long long)(hx + 1) * g.sX[i] + hy) * 4);
     }
-    float *outp = g.out + (long long)b * g.oB + (long long)x * g.oX + y;
+    // the output: this sample's planes (wave-uniform) and the thread's place in one - a 32-bit byte offset where the host
+    // found that every thread's fits (Geom::obuf), or else, and with plain stores always, elements added to a 64-bit pointer
+    constexpr bool SC1 = MARCH_ST_SC1 != 0;
+    const long long oel = (long long)x * g.oX + y;
+    const unsigned int ooff = (unsigned int)(oel * 4);
+    float *outp = g.out + (long long)b * g.oB + (SC1 ? 0 : oel);
     const long long oT = g.oT;
     // the planes this workgroup may touch: all of them - or, when no operator has a tap along the marched axis (1-D residuals
     // on [1,B,T,X], spatial operators, D_x / Laplacians on 3-D fields), its own segment only: a segment then costs no window
@@ -561,7 +604,7 @@ march_kernel(const Geom g, const typename Fn::Params prm, const typename std::co
     };
 
     // One plane.  P,C,N hold planes t-1,t,t+1 of the own cells; D receives plane t+2;
-    // hc is the halo of plane t, hn receives the halo of plane t+1.  The caller rotates the
+    // hc is the halo of plane t, hn receives the halo of plane t+1 (HAL3: of plane t+2).  The caller rotates the
     // roles instead of moving registers, so D/hn stay in flight until they are first read.
     auto step = [&](int t, float4(&P)[F], float4(&C)[F], float4(&N)[F], float4(&D)[F],
                     Halo<F, BC, COOP> &hc, Halo<F, BC, COOP> &hn) __attribute__((always_inline)) {
@@ -581,7 +624,9 @@ march_kernel(const Geom g, const typename Fn::Params prm, const typename std::co
         // issue order, so the own-cell loads of plane t+2 stay in flight behind it
         // (measured +7 % on NS momentum vs the other order; non-temporal stores: -25 %; round 3: the own-cell loads with
         // the slc / nt bit -5 ... -12 % on every functor, with glc +-0)
-        load_halo(t + 1, hn);
+        // (with the halo lead, HAL3, the halo is requested with the own cells of its plane and still before them: the other
+        // order measured 0.2 ... 1.3 % slower, a lead of three planes into four sets no faster than none - profiles/r07)
+        load_halo(t + (HAL3 ? AHEAD : 1), hn);
         load_own(t + AHEAD, D);
         if constexpr (SX::count > 0) lds_barrier();
 
@@ -607,7 +652,12 @@ march_kernel(const Geom g, const typename Fn::Params prm, const typename std::co
         float4 r = Fn::eval(n, prm);
         if (g.flags & PRE_FLAG_ABS) r = fabs4(r);
         if (inb) {
-            stg4(outp + (long long)t * oT, r);
+            if constexpr (SC1) {
+                if (g.obuf) stb4_sc1(outp + (long long)t * oT, ooff, r);
+                else stg4(outp + (long long)t * oT + ((long long)x * g.oX + y), r);
+            } else {
+                stg4(outp + (long long)t * oT, r);
+            }
         }
     };
 
@@ -633,6 +683,40 @@ march_kernel(const Geom g, const typename Fn::Params prm, const typename std::co
             if (t + 4 >= t1) break;
             step(t + 4, w4, w0, w1, w3, h0, h1);
             h0 = h1;
+        }
+    } else if constexpr (HAL3) {
+        // three halo sets against a four-plane ring: the roles repeat every twelve planes
+        float4 w0[F], w1[F], w2[F], w3[F];
+        Halo<F, BC, COOP> h2;
+        load_own(t0 - 1, w0);
+        load_own(t0, w1);
+        load_own(t0 + 1, w2);
+        load_halo(t0, h0);
+        load_halo(t0 + 1, h1);
+        for (int t = t0; t < t1; t += 12) {
+            step(t, w0, w1, w2, w3, h0, h2);
+            if (t + 1 >= t1) break;
+            step(t + 1, w1, w2, w3, w0, h1, h0);
+            if (t + 2 >= t1) break;
+            step(t + 2, w2, w3, w0, w1, h2, h1);
+            if (t + 3 >= t1) break;
+            step(t + 3, w3, w0, w1, w2, h0, h2);
+            if (t + 4 >= t1) break;
+            step(t + 4, w0, w1, w2, w3, h1, h0);
+            if (t + 5 >= t1) break;
+            step(t + 5, w1, w2, w3, w0, h2, h1);
+            if (t + 6 >= t1) break;
+            step(t + 6, w2, w3, w0, w1, h0, h2);
+            if (t + 7 >= t1) break;
+            step(t + 7, w3, w0, w1, w2, h1, h0);
+            if (t + 8 >= t1) break;
+            step(t + 8, w0, w1, w2, w3, h2, h1);
+            if (t + 9 >= t1) break;
+            step(t + 9, w1, w2, w3, w0, h0, h2);
+            if (t + 10 >= t1) break;
+            step(t + 10, w2, w3, w0, w1, h1, h0);
+            if (t + 11 >= t1) break;
+            step(t + 11, w3, w0, w1, w2, h2, h1);
         }
     } else {
         float4 w0[F], w1[F], w2[F], w3[F];
@@ -752,7 +836,9 @@ int launch_tiled(Geom &g, const typename Fn::Params &prm, hipStream_t st, const 
     g.nXT = (g.X + NR - 1) / NR;
     g.nYT = (g.Yc + 4 * TYQ - 1) / (4 * TYQ);
     for (int i = 0; i < Fn::F; ++i)            // a thread's place in a plane is a 32-bit byte offset (from one row before row 0)
-        if (g.sX[i] < 0 || ((long long)(g.X + 2 + NR) * g.sX[i] + g.Y + 8) * 4 >= (1LL << 32)) return PRE_E_UNSUPPORTED;
+        if (!plane_offsets_fit_u32(g.sX[i], (int64_t)g.X + 2 + NR, g.Y)) return PRE_E_UNSUPPORTED;
+    // the output's likewise, from row 0: a view that fails it is no error, it keeps the 64-bit pointer and the plain store
+    g.obuf = MARCH_ST_SC1 != 0 && plane_offsets_fit_u32(g.oX, (int64_t)g.X + NR, g.Y);
     // split long T axes so that the grid fills the chip and its last round of workgroups is nearly full, without paying
     // the 2-plane window prologue too often (pick_tseg)
     long long tiles = (long long)g.B * g.nXT * g.nYT;
@@ -880,7 +966,9 @@ flat_march_kernel(const Geom g, const typename Fn::Params prm)
     // pointers they cost 4 registers per field (JOREK temperature in its native layout: 139 registers, one workgroup per CU)
     const unsigned int voff = (unsigned int)m * 4u, hoff = (unsigned int)hm * 4u;       // (hm < 0: never loaded)
     const unsigned int eoff = ledge ? voff - 4u : voff + 16u;                           // (never loaded where it would be outside)
-    float *outp = g.out + (long long)b * g.oB + m;
+    // (the output shares the fields' in-plane layout: with MARCH_ST_SC1 its plane is a descriptor too and voff the place in it)
+    constexpr bool SC1 = MARCH_ST_SC1 != 0;
+    float *outp = g.out + (long long)b * g.oB + (SC1 ? 0 : m);
     const long long oT = g.oT;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     auto rsrc = [&](int i, int t) __attribute__((always_inline)) {
@@ -971,7 +1059,10 @@ flat_march_kernel(const Geom g, const typename Fn::Params prm)
         }
         float4 r = Fn::eval(n, prm);
         if (g.flags & PRE_FLAG_ABS) r = fabs4(r);
-        if (inb) stg4(outp + (long long)t * oT, r);
+        if (inb) {
+            if constexpr (SC1) stb4_sc1(outp + (long long)t * oT, voff, r);
+            else stg4(outp + (long long)t * oT, r);
+        }
     };
 
     float4 w0[F], w1[F], w2[F], w3[F];
@@ -1017,6 +1108,7 @@ int launch_flat(Geom &g, const typename Fn::Params &prm, hipStream_t st)
     static_assert(2 * FlatStaged<Fn>::FX * (FLAT_NT + 2 * FLAT_H) * 16 <= 160 * 1024, "chunk does not fit the 160 KiB LDS");
     g.nXT = 1;
     if ((long long)g.X * g.Y >= (1LL << 30)) return PRE_E_UNSUPPORTED;      // a thread's place in a plane is a 32-bit byte offset
+    g.obuf = MARCH_ST_SC1 != 0;                // (the output plane has the fields' layout, prepare(): its offsets are theirs)
     const long long quads = (long long)g.X * g.Y / 4;
     const int nt = flat_chunk(quads, g.Y, FlatStaged<Fn>::count > 0);
     g.nYT = (int)((quads + nt - 1) / nt);
@@ -1050,6 +1142,8 @@ int launch(Geom &g, const typename Fn::Params &prm, hipStream_t st, const BCInfo
     // 16x64 (1024 threads) 50.5 ms, 16x32 48.5, 32x16 50.7 against 47.4 for 8x64 (gpurun_out/r3b/nr_*.log)
     if constexpr (Fn::F >= 5)
         if (g.Y >= 192) return launch_tiled<Fn, MARCH6_NR, MARCH6_TYQ, BC>(g, prm, st, bc);
+    if constexpr (MARCH_NS16 != 0 && !BC && std::is_same<Fn, NSMomentum<0>>::value)
+        if (g.Y >= 192 && g.X >= 16) return launch_tiled<Fn, 16, 64, BC>(g, prm, st, bc);
     if (g.Y >= 192) return launch_tiled<Fn, 8, 64, BC>(g, prm, st, bc);
     if (g.Y >= 96) return launch_tiled<Fn, 16, 32, BC>(g, prm, st, bc);
     return launch_tiled<Fn, 32, 16, BC>(g, prm, st, bc);

@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Turn the rocprofv3 CSVs that `tools/profile_round.sh` left under gpurun_out/prof/ into the small,
-committed summaries under profiles/<round>/ (usage: python tools/distill_profiles.py r01)."""
+committed summaries under profiles/<round>/ (usage: python tools/distill_profiles.py r01).  A second argument is the
+bench.py command line of the C3 counter passes when they were collected without tracing on a plain run
+(python tools/distill_profiles.py r07 "--steps 2 --warmup 1": one rocprofv3 --pmc FETCH_SIZE run with -d <prof>/fetch and
+one --pmc WRITE_SIZE run with -d <prof>/write, <prof> being the directory named above, the FETCH_SIZE run's output in
+<prof>/bench_fetch.log)."""
 import collections, csv, glob, json, os, re, shutil, sys
 
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
+C3_PLAIN_CMD = sys.argv[2] if len(sys.argv) > 2 else None
 out = f"profiles/{rnd}"
 os.makedirs(out, exist_ok=True)
 MK = "march_kernel<NSMomentum<0>,8,64>"
@@ -81,13 +86,17 @@ except Exception:
 SRC_NOTE = "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes; FETCH_SIZE x2 gfx950 correction"
 
 
-def hbm_report(tag, fetch_src, write_src, kernel, cmd, workload, alg_bytes, halo_bytes=None, note=""):
+def hbm_report(tag, fetch_src, write_src, kernel, cmd, workload, alg_bytes, halo_bytes=None, note="", plain=False):
     pm = {**counters(fetch_src), **counters(write_src)}
     if ("FETCH_SIZE", kernel) not in pm or ("WRITE_SIZE", kernel) not in pm:
         return
     with open(f"{out}/pmc_hbm_{tag}.txt", "w") as o:
-        o.write("rocprofv3 --pmc FETCH_SIZE --kernel-trace / --pmc WRITE_SIZE --kernel-trace (separate passes)\n"
-                f"   -- python3 bench.py --full {cmd}   (MI355X)\n")
+        if plain:
+            o.write("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, counters alone: no tracing)\n"
+                    f"   -- python3 bench.py {cmd}   (MI355X)\n")
+        else:
+            o.write("rocprofv3 --pmc FETCH_SIZE --kernel-trace / --pmc WRITE_SIZE --kernel-trace (separate passes)\n"
+                    f"   -- python3 bench.py --full {cmd}   (MI355X)\n")
         o.write("counter unit KiB.  gfx950 corrections (MI355X_MICROARCH.md, HBM): FETCH_SIZE reports 1/2 of the bytes of a 16 B/lane\n"
                 "coalesced streaming read -> x2; WRITE_SIZE is exact for 16 B/lane streaming stores.\n\n")
         for (name, k), (n, avg) in sorted(pm.items(), key=lambda x: (x[0][1], x[0][0])):
@@ -123,12 +132,12 @@ except Exception:
     pass
 slabs = bench.split_slabs(c3[2] - 2 if axis == "x" else c3[1], slab)      # x-slabs: the reference's interior rows 1 .. Nx-2
 cells_xy = c3[0] * (c3[1] * c3[3] if axis == "x" else c3[2] * c3[3])        # batch x cells per row (x-slabs) / plane (t-slabs)
-hbm_report("c3", "fetch", "write", MK, "--steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-parity",
+hbm_report("c3", "fetch", "write", MK, C3_PLAIN_CMD or "--steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-parity",
            {"batch": c3[0], "nt": c3[1], "nx": c3[2], "ny": c3[3], "slab": slab, "slab_axis": axis, "rows": "interior"},
            sum(16 * sl * cells_xy for sl in slabs) / len(slabs),
            sum((12 * (sl + 2) + 4 * sl) * cells_xy for sl in slabs) / len(slabs),
            note=(f" [4096,64,S+2,512] x3 -> [4096,64,S,512], S in {slabs}" if axis == "x" else
-                 f" [4096,S+2,512,512] x3 -> [4096,S,512,512], S in {slabs}"))
+                 f" [4096,S+2,512,512] x3 -> [4096,S,512,512], S in {slabs}"), plain=bool(C3_PLAIN_CMD))
 for e in EQS:
     cfg = bench.mhd_config(e)
     shp = cfg["shape"]
