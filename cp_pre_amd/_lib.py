@@ -299,6 +299,17 @@ VJPMHD_SIGNATURES = {
     "pre_vjpmhd_energy_f32": _mhdvjp + [c_double] + _mhdtail,
 }
 
+# libcp_pre_screenjorek.so (include/cp_pre_screenjorek.h): the two 2-D screens for the reduced-MHD (JOREK) residuals; the set
+# descriptors are PreScreen (Ny-fastest fields) and PreScreenFlat (Nt-fastest fields)
+SCREENJOREK_SO_PATH = os.path.join(_HERE, "libcp_pre_screenjorek.so")
+PRE_SCREENJOREK_ABI_VERSION = 1
+_jrk = [c_int, POINTER(PreField), _fld] + [POINTER(c_float)] * 5 + [POINTER(c_float)]     # eq, fields, Rb, K_t .. K_ZZ, coef
+SCREENJOREK_SIGNATURES = {
+    "pre_screenjorek_abi_version": [],
+    "pre_screenjorek_f32": _jrk + _scr,
+    "pre_screenjorek_flat_f32": _jrk + _scrf,
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -326,8 +337,9 @@ _LIBS_MORE = {
     "cns": ("_cns", "CNS_", "pre_cns_abi_version", "PRE_CNS_ABI_VERSION", ()),
     "cnsvjp": ("_cnsvjp", "CNSVJP_", "pre_cnsvjp_abi_version", "PRE_CNSVJP_ABI_VERSION", ()),
     "vjpmhd": ("_vjpmhd", "VJPMHD_", "pre_vjpmhd_abi_version", "PRE_VJPMHD_ABI_VERSION", ()),
+    "screenjorek": ("_screenjorek", "SCREENJOREK_", "pre_screenjorek_abi_version", "PRE_SCREENJOREK_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -424,6 +436,10 @@ def load_cnsvjp():
 
 def load_vjpmhd():
     return _vjpmhd or _load("vjpmhd")
+
+
+def load_screenjorek():
+    return _screenjorek or _load("screenjorek")
 
 
 def require_gpu():

@@ -484,6 +484,31 @@ class JOREK:
     def _t32(self, x, like):
         return torch.as_tensor(x, dtype=torch.float32).to(like.device)
 
+    def _R_view(self, f0):
+        """R as one more field view that repeats its row, for the device field view ``f0`` [BS,Nt,Nx,Ny]: unit stride on the
+        axis the fields are contiguous on.  None: no layout of R goes with the fields'.  Shared by the residual pass and the
+        fused screen (``screen._Spec``); raises before any launch if ``len(R)`` is not Ny."""
+        if self.R.numel() != f0.shape[3]:
+            raise RuntimeError(f"R has {self.R.numel()} points, the fields' last axis {f0.shape[3]} (the reference "
+                               "broadcasts its 1-D R along the last axis)")
+        Rd = self.R.to(f0.device)
+        if f0.stride(3) == 1:
+            return Rd.view(1, 1, 1, -1).expand(f0.shape)
+        if f0.stride(1) == 1:                                             # Nt fastest (the surrogate's memory order)
+            return Rd.view(-1, 1).expand(-1, f0.shape[1]).contiguous().as_strided(tuple(f0.shape), (0, 1, 0, f0.shape[1]))
+        return None
+
+    def _coef(self, eq, norms=False):
+        """The four scalars a0..a3 ``pre_residual_jorek_f32`` takes for equation ``eq`` (0 continuity, 1 temperature): the
+        script's scalars, folded in fp32 in its own order of operations."""
+        t = lambda v: torch.tensor(v, dtype=torch.float32)
+        if eq == 1:
+            return [float(2 * t(self.gamma)), 0.0, 0.0, float(t(self.K))]
+        if norms:
+            dx, dy, dt, D = t(self.dx), t(self.dy), t(self.dt), t(self.D)
+            return [float(2*dx*dy), float(dt), float((2*dt*dy)*2), float((4*dt)*D)]
+        return [1.0, 1.0, 2.0, float(t(self.D))]
+
     def _fused(self, eq, fields, coef, absolute):
         """One streaming pass (``pre_residual_jorek_f32``); None -> compose.  No ``out`` / ``halo_x`` here."""
         if not self.fused or any(f.numel() == 0 for f in fields) or \
@@ -495,16 +520,8 @@ class JOREK:
 
         def call(d, out, flags):
             devs, f0 = d[0], d[0][0]
-            if self.R.numel() != f0.shape[3]:
-                raise RuntimeError(f"R has {self.R.numel()} points, the fields' last axis {f0.shape[3]} (the reference "
-                                   "broadcasts its 1-D R along the last axis)")
-            # R as one more field view that repeats the row: unit stride on the axis the fields are contiguous on
-            Rd = self.R.to(f0.device)
-            if f0.stride(3) == 1:
-                Rb = Rd.view(1, 1, 1, -1).expand(f0.shape)
-            elif f0.stride(1) == 1:                                       # Nt fastest (the surrogate's memory order)
-                Rb = Rd.view(-1, 1).expand(-1, f0.shape[1]).contiguous().as_strided(tuple(f0.shape), (0, 1, 0, f0.shape[1]))
-            else:
+            Rb = self._R_view(f0)
+            if Rb is None:
                 return _lib.PRE_E_UNSUPPORTED                             # (no layout of R to go with the fields': compose)
             return _lib.load().pre_residual_jorek_f32(
                 eq, _arr([devs[i] if i < len(devs) else devs[0] for i in range(3)]), ctypes.byref(_lib.field(Rb)),
@@ -536,13 +553,8 @@ class JOREK:
                     - (4*dt)*D*(D_RR(rho) + (1/R)*D_R(rho) + D_ZZ(rho))
             return D_t(rho) - R*(D_R(rho)*D_Z(phi) - D_R(phi)*D_Z(rho)) - 2*rho*D_Z(phi) \
                 - D*(D_RR(rho) + (1/R)*D_R(rho) + D_ZZ(rho))
-        if norms:      # the script's scalars, folded in fp32 in its own order of operations
-            t = lambda v: torch.tensor(v, dtype=torch.float32)
-            dx, dy, dt, D = t(self.dx), t(self.dy), t(self.dt), t(self.D)
-            coef = [float(2*dx*dy), float(dt), float((2*dt*dy)*2), float((4*dt)*D)]
-        else:
-            coef = [1.0, 1.0, 2.0, float(torch.tensor(self.D, dtype=torch.float32))]
-        return self._residual(0, (rho, phi), composed, coef, lambda x, b: self.residual_continuity(x, b, norms),
+        return self._residual(0, (rho, phi), composed, self._coef(0, norms),
+                              lambda x, b: self.residual_continuity(x, b, norms),
                               vars, minus, boundary, absolute)
 
     def residual_temperature(self, vars, boundary=False, norms=False, absolute=False, minus=None):
@@ -558,9 +570,7 @@ class JOREK:
                 T*R*(D_R(rho)*D_Z(phi) - D_R(phi)*D_Z(rho)) + \
                 2*gamma*rho*T*D_Z(phi) + \
                 K * (D_RR(T) + (1/R)*D_R(T) + D_ZZ(T))
-        t = lambda v: torch.tensor(v, dtype=torch.float32)
-        coef = [float(2 * t(self.gamma)), 0.0, 0.0, float(t(self.K))]
-        return self._residual(1, (rho, phi, T), composed, coef, self.residual_temperature, vars, minus, boundary, absolute)
+        return self._residual(1, (rho, phi, T), composed, self._coef(1), self.residual_temperature, vars, minus, boundary, absolute)
 
 
 class PRE_MHD(MHD):

@@ -17,11 +17,11 @@ Fused route (``libcp_pre_screen.so``, ``include/cp_pre_screen.h``): the march of
 in registers and reduces it per sample - a maximum and nk integer counts - so the three launches and the residual buffer of
 the route a user writes today (residual, ``ncf_metric_joint``, ``CoverageLevels``) become one launch that stores nothing.
 Fused kinds: ``stencil3d`` (a ``ConvOperator`` of ``convops_2d``, ``PRE_Wave``), ``linear2`` (NS continuity, MHD gauss),
-``ns_momentum``, ``mhd_continuity`` / ``mhd_momentum`` / ``mhd_energy`` / ``mhd_induction``.  Everything else takes that
-three-pass route (residual, ``ncf_metric_joint``, then ``CoverageLevels`` once per sample) and returns the same ``Screened``:
-JOREK, views without unit stride on their last axis, row widths that are no multiple of 4, inputs on the CPU (staged as
-elsewhere), ``minus=``, operator kernels off the 7-point star or requiring grad, ``fused=False``, float64 levels or
-modulation.  ``last_route()`` says which route the last call took.
+``ns_momentum``, ``mhd_continuity`` / ``mhd_momentum`` / ``mhd_energy`` / ``mhd_induction`` and, opt-in, ``jorek_continuity``
+/ ``jorek_temperature`` (below).  Everything else takes that three-pass route (residual, ``ncf_metric_joint``, then
+``CoverageLevels`` once per sample) and returns the same ``Screened``: views without unit stride on their last axis, row
+widths that are no multiple of 4, inputs on the CPU (staged as elsewhere), ``minus=``, operator kernels off the 7-point
+star or requiring grad, ``fused=False``, float64 levels or modulation.  ``last_route()`` says which route the last call took.
 
 The 1-D family on ``[BS,Nt,Nx]`` (a ``ConvOperator`` of ``convops_1d``, ``Advection.residual``, ``Burgers.residual``) has a
 fused route of its own (``libcp_pre_screen1d.so``, ``include/cp_pre_screen1d.h``): the march above would run over the
@@ -35,6 +35,16 @@ Nt-fastest views of the 2-D residuals - ``pred.permute(0,1,4,2,3)`` of the surro
 (``libcp_pre_screenflat.so``, ``include/cp_pre_screenflat.h``): the merged-row march of the residual pass's flat form with
 the same end of a plane.  Routes ``fused:flat_<kind>``; taken when the rows are dense (``stride(Ny) == Nt``), ``Ny*Nt`` is a
 multiple of 4 and ``Nt < FLAT_MAX_NT``, else the three-pass route says why.  ``halo_x`` on such a view behaves as before.
+
+The reduced-MHD residuals (``JOREK.residual_continuity`` / ``residual_temperature``, ``Joint/JOREK_residuals_CP.py:210-243,
+297-308``) are screened in one launch only where the caller asks for it: ``screen(..., jorek=True)`` /
+``Screen.add_slab(..., jorek=True)`` (``libcp_pre_screenjorek.so``, ``include/cp_pre_screenjorek.h``: both marches above with
+the functors of ``pre_residual_jorek_f32``).  ``vars`` is the script's ``[BS,F,Nx,Ny,Nt]``; every layout decision is taken on
+its ``unstack_fields`` views ``[BS,Nt,Nx,Ny]``: the dense tensor the script holds is Nt-fastest (route
+``fused:flat_jorek_<eq>``), a view of memory ``[BS,F,Nt,Nx,Ny]`` is Ny-fastest (``fused:jorek_<eq>``).  The equations are
+evaluated with ``norms=False`` (``norms=True`` of the continuity equation cannot be reached through a bound method);
+``halo_x`` raises, as for every method whose residual pass reads no halo.  Without the keyword JOREK keeps the three-pass
+route (``fallback:no fused screen for JOREK``) and the library is never loaded.
 
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
@@ -120,25 +130,50 @@ _FORMS = {"": ("load_screen", "pre_screen_", ""), "flat": ("load_screenflat", "p
           "rows": ("load_screen1d", "pre_screen1d_", "rows_")}
 # the four MHD kinds share ONE entry point, pre_screen[flat]_mhd_f32: kind -> the ``eq`` it takes first
 _MHD_EQ = {"mhd_" + e: i for i, e in enumerate(MHD_EQ)}
+# the two JOREK kinds (opt-in) share the two entry points of a library of their own: kind -> ``eq``; form -> entry point
+_JOREK_EQ = {"jorek_continuity": 0, "jorek_temperature": 1}
+_JOREK_ENTRY = {"": "pre_screenjorek_f32", "flat": "pre_screenjorek_flat_f32"}
 
 
 class _Spec(Method):
     """One residual method, resolved (``_method.Method``) for the fused screens: ``kind`` (None: no fused screen of the
     2-D family), ``chan`` - the channels of a stacked ``[BS,F,...]`` input the residual reads (None: the input is the field
     itself), ``rows_kind`` - the fused screen of the 1-D family ('stencil2d', 'burgers'; None: none), which ``kind`` and
-    ``why`` do not speak of; ``eq`` (the MHD equations) and ``ratio`` (``linear2``) as the launches take them."""
+    ``why`` do not speak of; ``eq`` (the MHD and JOREK equations) and ``ratio`` (``linear2``) as the launches take them.
+    ``jorek=True`` on a bound ``JOREK.residual_continuity`` / ``residual_temperature`` resolves the opt-in kinds
+    ``jorek_continuity`` / ``jorek_temperature`` (``norms=False``): ``ops`` are the object's five operators, ``fields`` its
+    ``unstack_fields`` views; on anything else it is a ``TypeError``.  Without it JOREK has no fused kind, as before."""
     KIND = {"op3d": "stencil3d", "wave": "stencil3d", "ns_momentum": "ns_momentum", "ns_continuity": "linear2",
             "mhd_gauss": "linear2", **{k: k for k in _MHD_EQ}}
     ROWS_KIND = {"op2d": "stencil2d", "advection": "stencil2d", "burgers": "burgers"}
     WHY = {"spectral": "spectral operator", "jorek": "no fused screen for JOREK",
            **dict.fromkeys(ROWS_KIND, "1-D family: the marched axis is the batch")}
 
-    def __init__(self, method):
+    def __init__(self, method, jorek=False):
         super().__init__(method)
+        if jorek:
+            kind = "jorek_" + getattr(method, "__name__", "")[len("residual_"):]
+            if self.row != "jorek" or kind not in _JOREK_EQ:
+                raise TypeError("jorek=True takes a bound JOREK.residual_continuity or JOREK.residual_temperature")
+            self.kind, self.why, self.eq, self.ops = kind, None, _JOREK_EQ[kind], tuple(self.obj._ops())
         if self.kind == "linear2":
             self.ratio, = self.scalars()
         elif self.kind in _MHD_EQ:
             self.eq = _MHD_EQ[self.kind]
+
+    def fields(self, x):
+        if self.kind in _JOREK_EQ:
+            return R.JOREK.unstack_fields(x)[:2 + self.eq]
+        return super().fields(x)
+
+    def scalars(self):
+        if self.kind in _JOREK_EQ:
+            return (_lib.farr(self.obj._coef(self.eq)),)          # (norms=False: what a bound method evaluates)
+        return super().scalars()
+
+    def view(self, x):
+        """What the layout of input ``x`` is decided on: ``x`` itself, or for JOREK's ``[BS,F,Nx,Ny,Nt]`` a field view."""
+        return x[:, 0].permute(0, 3, 1, 2) if self.kind in _JOREK_EQ else x
 
     def reads_halo(self):
         """Does the method's own residual pass take ``halo_x``?  (A ``ConvOperator`` call, NS continuity and MHD gauss do
@@ -162,9 +197,11 @@ class _Spec(Method):
 
     # -------- can a fused screen run?  input, then layout, then what declines whatever the layout, then the kernels
     def _prepare(self, layout, kind, points, x, minus, qhats, modulation):
-        why = _input_declined(x, minus, qhats, modulation) or layout(x) or self.declined(x)
+        why = _input_declined(x, minus, qhats, modulation) or layout(self.view(x)) or self.declined(x)
         if why is None and kind in _MHD_EQ and x.shape[1] < 6:
             why = "fewer than six MHD channels"                  # (pre_screen_mhd_f32 takes the six views)
+        if why is None and kind in _JOREK_EQ and x.shape[1] != 3:
+            why = "not three JOREK channels"                     # (the residual methods unstack exactly rho, phi, T)
         return (why, ()) if why is not None else self.star_kernels(kind, points)
 
     def prepare(self, x, minus, qhats, modulation):
@@ -192,6 +229,7 @@ class _Spec(Method):
 
     def nt_fastest(self, x):
         """Is ``x`` an Nt-fastest view of a 2-D residual's input (unit stride on Nt, not on Ny)?"""
+        x = self.view(x)
         return self.kind is not None and x.dim() >= 4 and x.stride(-3) == 1 and x.stride(-1) != 1
 
     @staticmethod
@@ -218,6 +256,8 @@ class _Spec(Method):
     # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
     def entry(self, form):
         """The entry point of this method's fused screen in the library of ``form``."""
+        if self.kind in _JOREK_EQ and form != "rows":
+            return _JOREK_ENTRY[form]
         kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
         return _FORMS[form][1] + kind + "_f32"
 
@@ -227,8 +267,8 @@ class _Spec(Method):
     def launch(self, kernels, x, st, flags, form=""):
         """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
-        lib = getattr(_lib, _FORMS[form][0])()
         kind = self.rows_kind if form == "rows" else self.kind
+        lib = getattr(_lib, "load_screenjorek" if kind in _JOREK_EQ else _FORMS[form][0])()
         if form == "rows":
             views, shape = (_lib.ptr(x), _lib.iarr64(x.stride())), x.shape
         else:
@@ -236,6 +276,11 @@ class _Spec(Method):
             shape = fs[0].shape
             if kind in _MHD_EQ:
                 views = (self.eq, R._arr([x[:, i] for i in range(6)]))
+            elif kind in _JOREK_EQ:
+                Rb = self.obj._R_view(fs[0])                     # (raises before any launch if len(R) is not Ny)
+                if Rb is None:
+                    return _lib.PRE_E_UNSUPPORTED
+                views = (self.eq, R._arr([fs[i] if i < len(fs) else fs[0] for i in range(3)]), ctypes.byref(_lib.field(Rb)))
             else:
                 views = [ctypes.byref(_lib.field(f)) for f in fs]
         if kind.startswith("stencil"):
@@ -316,18 +361,21 @@ class Screen:
             self.acc = torch.zeros(self.nk + 1, self.n_local, dtype=torch.int32, device=device)
         return self.acc
 
-    def add_slab(self, method, vars_slab, qhats, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None):
+    def add_slab(self, method, vars_slab, qhats, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None, jorek=False):
         """``vars_slab``: the method's input on a slab of the grid (all local samples); ``modulation_slab`` [T,X,Y] of the
         slab's uncropped residual extents, or None (m == 1); ``crop`` cells per side of each residual axis are left out
-        (``JointCalibration.add_slab``'s meaning); ``halo_x``: the slab's rows -1 and X lie in the same memory."""
+        (``JointCalibration.add_slab``'s meaning); ``halo_x``: the slab's rows -1 and X lie in the same memory; ``jorek``: the
+        opt-in fused screen of the JOREK residuals (``_Spec``; a method given as a ``_Spec`` has decided already)."""
         global _last_route
-        spec = method if isinstance(method, _Spec) else _Spec(method)
+        spec = method if isinstance(method, _Spec) else _Spec(method, jorek)
         shape, crop, cells = _check_inputs(spec, vars_slab, qhats, modulation_slab, minus, crop, self.nk)
         if shape[0] != self.n_local:
             raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
         if _dev_key(vars_slab.device) != _dev_key(self.device):
             raise ValueError(f"slab on {vars_slab.device}, this Screen was made for {self.device}")
         why, kernels = spec.prepare(vars_slab, minus, qhats, modulation_slab)
+        if halo_x and spec.kind in _JOREK_EQ:
+            why = why or "halo_x"                                 # (no pass of the JOREK residuals reads halo rows: raises below)
         if halo_x and not vars_slab.is_cuda:
             raise ValueError("halo_x needs a device-resident view of a larger grid (a staged copy has no halo rows)")
         if halo_x and why is not None and not spec.reads_halo():
@@ -425,11 +473,13 @@ class Screen:
         return Screened(self.acc[0].view(torch.float32).clone(), self.acc[1:].to(torch.int64) & 0xffffffff, self.cells)
 
 
-def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=None):
+def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=None, jorek=False):
     """Screen the predictions ``vars`` against the sets ``|r| <= qhats[k] * modulation``.  ``boundary=False``: the counted
     cells are the interior ``[1:-1]`` of every residual axis, as the reference crops its residuals (``modulation`` keeps
-    the uncropped extents: its rim is never used); ``boundary=True``: every cell.  Returns a :class:`Screened`."""
-    spec = _Spec(residual_method)
+    the uncropped extents: its rim is never used); ``boundary=True``: every cell.  ``jorek=True``: the opt-in fused screen
+    of ``JOREK.residual_continuity`` / ``residual_temperature`` (``vars`` [BS,F,Nx,Ny,Nt], ``modulation`` [Nt,Nx,Ny]; the
+    equations with ``norms=False``).  Returns a :class:`Screened`."""
+    spec = _Spec(residual_method, jorek)
     crop = (0,) * spec.nd if boundary else (1,) * spec.nd
     shape, _, _ = _check_inputs(spec, vars, qhats, modulation, minus, crop)
     s = Screen(shape[0], qhats.shape[0], vars.device)

@@ -22,6 +22,11 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                through ``permute(0,1,4,2,3)`` as the reference's 2-D scripts pass them (``libcp_pre_screenflat.so``: the
                merged-row march).  (B) scores with ``ncf_metric_joint(..., crop=1)`` as the package's fallback does in
                this layout; (R) is the flat residual launch into a buffer laid out like the fields
+    jorek_temperature_ntfast / jorek_continuity_ntfast
+               the JOREK residuals on the script's dense vars [96,3,256,256,40] (Nt = 40 = its T_out; 3.0 GB of fields), Nt-fastest
+               field views, ``jorek=True`` (``libcp_pre_screenjorek.so``: the merged-row march with the functors of
+               ``pre_residual_jorek_f32``).  The JOREK residual pass takes no ``out=``: (B) and (R) allocate their residual from
+               torch's caching allocator on every call, as for Burgers; (R) is ``pre_residual_jorek_f32`` on the same views
 
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
@@ -69,7 +74,8 @@ def blocks_of(fns, reps, blocks, warmup):
 
 
 def case(name, div, dev):
-    """(method, vars view, crop, halo_x, residual call into out=, bytes of fields per cell)"""
+    """(method, vars view, crop, halo_x, residual call into out=, bytes of fields per cell)  A JOREK method's vars are the
+    script's [BS,F,Nx,Ny,Nt]."""
     g = torch.Generator(device=dev).manual_seed(0)
 
     def rnd(*s):
@@ -106,6 +112,11 @@ def case(name, div, dev):
         mhd = R.MHD(device=dev)
         v = rnd(max(1024 // div, 1), 6, 256, 256, 64).permute(0, 1, 4, 2, 3)
         return mhd.residual_induction, v, (1, 1, 1), False, lambda out: mhd.residual_induction(v, boundary=True, out=out), 16
+    if name in ("jorek_temperature_ntfast", "jorek_continuity_ntfast"):
+        jo = R.JOREK(torch.linspace(1.0, 2.0, 256), device=dev)
+        v = rnd(max(96 // div, 1), 3, 256, 256, 40)
+        method = jo.residual_temperature if "temperature" in name else jo.residual_continuity
+        return method, v, (1, 1, 1), False, lambda out: method(v, boundary=True), 12 if "temperature" in name else 8
     raise KeyError(name)
 
 
@@ -125,28 +136,35 @@ def main():
         method, v, crop, halo_x, residual_into, fbytes = case(name, args.div, dev)
         n = v.shape[0]
         one_d = len(crop) == 2
-        nt_fast = not one_d and v.stride(-1) != 1
-        shape = (n,) + tuple(v.shape[-len(crop):])
+        jorek = isinstance(method.__self__, R.JOREK) if hasattr(method, "__self__") else False
+        nt_fast = not one_d and (jorek or v.stride(-1) != 1)
+        shape = (n, v.shape[4], v.shape[2], v.shape[3]) if jorek else (n,) + tuple(v.shape[-len(crop):])
         mod = torch.rand(shape[1:], device=dev) + 0.5
         if one_d and v.stride(-1) != 1:
             mod = mod.t().contiguous().t()
         q = torch.linspace(0.5, 50.0, NK, device=dev)
         if nt_fast:
             mod = mod.permute(1, 2, 0).contiguous().permute(2, 0, 1)
-        out = None if one_d else torch.empty(shape, dtype=torch.float32, device=dev)
-        if nt_fast:
+        out = None if one_d or jorek else torch.empty(shape, dtype=torch.float32, device=dev)
+        if nt_fast and not jorek:
             out = torch.empty((n,) + shape[2:] + shape[1:2], dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
         reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
 
         def fused():
             s = screen.Screen(n, NK, dev)
-            s.add_slab(method, v, q, mod, crop=crop, halo_x=halo_x)
+            s.add_slab(method, v, q, mod, crop=crop, halo_x=halo_x, jorek=jorek)
             return s
 
         def three():
             if one_d:
                 res = residual_into(None)
                 scores = icp.ncf_metric_joint(res[reg].contiguous(), None, mod[reg[1:]].contiguous())
+                cov = pipeline.CoverageLevels(n, NK, dev, joint=True)
+                cov.add_slab(res[reg], q, modulation=mod[reg[1:]])
+                return scores, cov
+            if jorek:                                        # (no out=: the residual comes back laid out like the fields)
+                res = residual_into(None)
+                scores = icp.ncf_metric_joint(res, None, mod, crop=1)
                 cov = pipeline.CoverageLevels(n, NK, dev, joint=True)
                 cov.add_slab(res[reg], q, modulation=mod[reg[1:]])
                 return scores, cov
@@ -182,6 +200,8 @@ def main():
             line[k + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
         if "fused" in pick:
             line["fused_TBps_of_fields"] = round(cells * fbytes / (line["fused_ms"] * 1e-3) / 1e12, 3)
+        if "fused" in pick and "three" in pick:
+            line["fused_over_three"] = round(line["fused_ms"] / line["three_ms"], 4)
         txt = json.dumps(line)
         print(txt, flush=True)
         with open(args.out, "a") as f:
