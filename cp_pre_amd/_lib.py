@@ -310,6 +310,12 @@ SCREENJOREK_SIGNATURES = {
     "pre_screenjorek_flat_f32": _jrk + _scrf,
 }
 
+# libcp_pre_vjpflatmhd.so (include/cp_pre_vjpflatmhd.h): the entries of libcp_pre_vjpmhd.so for Nt-fastest views (the march of
+# libcp_pre_vjpflat.so), argument for argument
+VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
+PRE_VJPFLATMHD_ABI_VERSION = 1
+VJPFLATMHD_SIGNATURES = {name.replace("pre_vjpmhd_", "pre_vjpflatmhd_"): sig for name, sig in VJPMHD_SIGNATURES.items()}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -338,8 +344,9 @@ _LIBS_MORE = {
     "cnsvjp": ("_cnsvjp", "CNSVJP_", "pre_cnsvjp_abi_version", "PRE_CNSVJP_ABI_VERSION", ()),
     "vjpmhd": ("_vjpmhd", "VJPMHD_", "pre_vjpmhd_abi_version", "PRE_VJPMHD_ABI_VERSION", ()),
     "screenjorek": ("_screenjorek", "SCREENJOREK_", "pre_screenjorek_abi_version", "PRE_SCREENJOREK_ABI_VERSION", ()),
+    "vjpflatmhd": ("_vjpflatmhd", "VJPFLATMHD_", "pre_vjpflatmhd_abi_version", "PRE_VJPFLATMHD_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -440,6 +447,10 @@ def load_vjpmhd():
 
 def load_screenjorek():
     return _screenjorek or _load("screenjorek")
+
+
+def load_vjpflatmhd():
+    return _vjpflatmhd or _load("vjpflatmhd")
 
 
 def require_gpu():

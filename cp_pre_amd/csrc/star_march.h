@@ -53,7 +53,7 @@ struct Nbr { float4 c, tm, tp, xm, xp, ym, yp; };
 __device__ __forceinline__ float4 f4(float s) { return make_float4(s, s, s, s); }
 __device__ __forceinline__ float4 fabs4(const float4 &a) { return make_float4(fabsf(a.x), fabsf(a.y), fabsf(a.z), fabsf(a.w)); }
 
-enum Kind { K_T3, K_X3, K_Y3, K_XY5, K_TX5, K_STAR7 };
+enum Kind { K_T3, K_X3, K_Y3, K_XY5, K_TX5, K_STAR7, K_TY5 };
 
 template <int KIND>
 __device__ __forceinline__ float4 apply(const Star &w, const Nbr &n)
@@ -63,6 +63,7 @@ __device__ __forceinline__ float4 apply(const Star &w, const Nbr &n)
     if (KIND == K_Y3) return w.ym * n.ym + w.c * n.c + w.yp * n.yp;
     if (KIND == K_XY5) return w.xm * n.xm + w.ym * n.ym + w.c * n.c + w.yp * n.yp + w.xp * n.xp;
     if (KIND == K_TX5) return w.tm * n.tm + w.xm * n.xm + w.c * n.c + w.xp * n.xp + w.tp * n.tp;
+    if (KIND == K_TY5) return w.tm * n.tm + w.ym * n.ym + w.c * n.c + w.yp * n.yp + w.tp * n.tp;
     // the general star: a zero weight along the marched axis is not multiplied.  When no operator has such a tap
     // (Geom::tfree) the neighbouring planes are other samples of a [1,B,T,X] field, or real planes inside a segment and
     // zeros at its cuts: 0 * inf from there would put NaN outside the operator's extent box (cp_pre_hip.h, non-finite

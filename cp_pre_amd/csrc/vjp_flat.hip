@@ -16,7 +16,7 @@
 // the crop reaches nothing; scale = host_scale * *dev_scale, the device scalar never read on the host.  Every stream is
 // staged: the functors are general 7-point stars (mirrored and folded on the host in double, as residual_vjp.hip folds
 // them, then relabelled to the kernel's axes), and the products gg*u, gg*v need the x-neighbours of u and v too.  Padding is
-// zero (the adjoint of a zero-padded correlation).  Up to three output streams in the same merged order; marched planes
+// zero (the adjoint of a zero-padded correlation).  Up to VF_MAXOUT (here three) output streams in the same merged order; marched planes
 // are not cut by the crop: a rim plane's gradient is generally non-zero.  No atomics.
 //
 // The split (tests/vjpflat_helpers.py states it again and names the test seams from it):
@@ -32,9 +32,15 @@
 #define PRE_VJPFLAT_NS 1
 #endif
 
-namespace {
+// the streams a launch can take; a unit that includes this one with more of them (vjp_flat_mhd.hip) sets its own
+#ifndef VF_MAXIN
+#define VF_MAXIN 3
+#endif
+#ifndef VF_MAXOUT
+#define VF_MAXOUT 3
+#endif
 
-constexpr int VF_MAXIN = 3, VF_MAXOUT = 3;
+namespace {
 
 // Kernel axes: T = the marched axis (logical Nx), X = logical Ny, Y = logical Nt; a plane is one row of X * Y cells.
 struct FVGeom {
@@ -206,7 +212,7 @@ Star relabelled(const Star &o) { return Star{o.c, o.xm, o.xp, o.ym, o.yp, o.tm, 
 template <class Fn>
 int launch_vjp_flat(FVGeom &g, const typename Fn::Params &prm, hipStream_t st)
 {
-    static_assert(2 * Fn::FIN * (FLAT_NT + 2 * FLAT_H) * 16 <= 64 * 1024, "static LDS of a workgroup");
+    static_assert(2 * Fn::FIN * (FLAT_NT + 2 * FLAT_H) * 16 <= 160 * 1024, "chunk does not fit the 160 KiB LDS");
     static_assert(FLAT_MAX_Y <= 4 * FLAT_H, "an x-neighbour must lie inside the staged halo");
     const long long quads = (long long)g.X * g.Y / 4;
     const int nt = flat_chunk(quads, g.Y, true);                   // (every stream is staged)
@@ -220,11 +226,11 @@ int launch_vjp_flat(FVGeom &g, const typename Fn::Params &prm, hipStream_t st)
     return PRE_OK;
 }
 
-// Null / empty / layout / overlap checks of everything the entry points hand to the kernel (residual_vjp.hip's
-// prepare_vjp with the flat form's layout), and the geometry on the kernel's axes.  Shapes come in on the caller's
-// logical [B,T,X,Y].
-int prepare_vjp_flat(FVGeom &g, const pre_field_t *const *fs, int nf, const pre_out_t *const *os, int no, int64_t B, int64_t T,
-                     int64_t X, int64_t Y, int flags, float host_scale, const float *dev_scale)
+// Null / empty / layout / overlap checks of everything an entry point hands to the kernel (residual_vjp.hip's prepare_vjp
+// with the flat form's layout), every view against every other: an entry of several launches checks the views of all of
+// them here before the first.  Shapes come in on the caller's logical [B,T,X,Y].
+int check_vjp_flat(const pre_field_t *const *fs, int nf, const pre_out_t *const *os, int no, int64_t B, int64_t T, int64_t X,
+                   int64_t Y, int flags)
 {
     if (!vjp_views_given(fs, nf, os, no, B, T, X, Y)) return PRE_E_NULL;
     if (B > 0x7fffffff || T > 0x7fffffff || X > 0x7fffffff || Y > 0x7fffffff) return PRE_E_SHAPE;
@@ -237,6 +243,15 @@ int prepare_vjp_flat(FVGeom &g, const pre_field_t *const *fs, int nf, const pre_
         if (os[k]->sT != 1 || os[k]->sY != T || os[k]->sX != Y * T) return PRE_E_UNSUPPORTED;
     if (Y * T >= (1LL << 30)) return PRE_E_SHAPE;                  // a thread's place in a plane is a 32-bit byte offset
     if (!vjp_views_disjoint(fs, nf, os, no, B, T, X, Y)) return PRE_E_SHAPE;
+    return PRE_OK;
+}
+
+// The checks above for the views of ONE launch, and its geometry on the kernel's axes.
+int prepare_vjp_flat(FVGeom &g, const pre_field_t *const *fs, int nf, const pre_out_t *const *os, int no, int64_t B, int64_t T,
+                     int64_t X, int64_t Y, int flags, float host_scale, const float *dev_scale)
+{
+    const int rc = check_vjp_flat(fs, nf, os, no, B, T, X, Y, flags);
+    if (rc) return rc;
     for (int i = 0; i < VF_MAXIN; ++i) {
         const bool on = i < nf;
         g.f[i] = on ? fs[i]->ptr : nullptr;
@@ -256,6 +271,7 @@ int prepare_vjp_flat(FVGeom &g, const pre_field_t *const *fs, int nf, const pre_
 
 }  // namespace
 
+#ifndef PRE_VJPFLAT_NO_ENTRIES      // (vjp_flat_mhd.hip includes this unit for the march and its host side, not for the entries)
 extern "C" {
 
 int pre_vjpflat_abi_version(void) { return PRE_VJPFLAT_ABI_VERSION; }
@@ -325,3 +341,4 @@ int pre_vjpflat_ns_momentum_f32(const pre_field_t *g, const pre_field_t uv[2], c
 }
 
 }  // extern "C"
+#endif

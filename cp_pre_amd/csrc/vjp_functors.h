@@ -1,6 +1,6 @@
 // vjp_functors.h - what the backward passes of the residual losses share: the functors of the tiled march (vjp_march.h:
 // residual_vjp.hip, libcp_pre_vjp.so; vjp_mhd.hip, libcp_pre_vjpmhd.so) and of the merged-row march (vjp_flat.hip,
-// libcp_pre_vjpflat.so), the crop bits and the host-side folding of their stars.  With D(f)(x) = sum_k w_k f(x+k) (zero padding), D^T(g)(x) = sum_k w_k g(x-k): the same star with mirrored
+// libcp_pre_vjpflat.so; vjp_flat_mhd.hip, libcp_pre_vjpflatmhd.so), the crop bits and the host-side folding of their stars.  With D(f)(x) = sum_k w_k f(x+k) (zero padding), D^T(g)(x) = sum_k w_k g(x-k): the same star with mirrored
 // taps.  Every functor gets its stars already mirrored and folded with their scalar factors (host, in double, rounded once)
 // and, in the merged-row march, relabelled to the kernel's axes.
 #pragma once
@@ -56,11 +56,12 @@ struct VjpNSMomentum {
 // ------------------------------------------------------------------ ideal MHD (vjp_mhd.hip, include/cp_pre_vjpmhd.h)
 // The functors are templated on the MODE of the forward march (star_march.h: OpKinds, pick_mode), so that an operator
 // multiplies only the taps its tap structure has; a mirrored star keeps its kind.  M = D_x - D_y and P = D_x + D_y are
-// folded on the host and live on the union of the two structures: (Nt, Nx) in MODE 0, (Nx, Ny) in MODE 1.  With general
+// folded on the host and live on the union of the two structures: (Nt, Nx) in MODE 0, (Nx, Ny) in MODE 1; on the kernel
+// axes of an Nt-fastest view (vjp_flat_mhd.hip) the marched axis and y in MODE 3, the marched axis and x in MODE 4.  With general
 // stars everywhere (MODE 2) the one-pass forms need scratch; momentum and energy are split by output group into two
 // launches whatever the MODE (the resource table: DESIGN 4.19).
 template <int MODE> struct VjpKinds : OpKinds<MODE> {
-    static constexpr int MP = MODE == 0 ? K_TX5 : MODE == 1 ? K_XY5 : K_STAR7;
+    static constexpr int MP = MODE == 0 ? K_TX5 : MODE == 1 ? K_XY5 : MODE == 3 ? K_TY5 : MODE == 4 ? K_TX5 : K_STAR7;
 };
 
 template <class F> __device__ __forceinline__ Nbr nbr_of(const Nbr &a, const Nbr &b, F f)

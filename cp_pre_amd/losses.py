@@ -58,6 +58,17 @@ with operators that are general stars only momentum is built, the others take ``
 Together with ``flat=True`` an Nt-fastest input takes ``fallback:no flat VJP for MHD``.  The channels an equation does not
 read get a zero gradient.
 
+``mhd="flat"`` (a further opt-in value: ``mhd=True`` is unchanged) does everything ``mhd=True`` does and additionally offers
+an Nt-fastest MHD input - ``pred.permute(0,1,4,2,3)`` of a surrogate's ``[BS,F,Nx,Ny,Nt]`` output, the view
+``Joint/MHD_Residuals_CP.py`` and ``Marginal/MHD_Residuals_CP.py`` pass - to ``libcp_pre_vjpflatmhd.so``
+(``include/cp_pre_vjpflatmhd.h``: the merged-row march of ``libcp_pre_vjpflat.so`` with the MHD functors), whatever ``flat``
+says; the library loads only when that route is taken.  Routes ``fused:flat_mhd_continuity``, ``fused:flat_mhd_induction``
+(one launch), ``fused:flat_mhd_momentum``, ``fused:flat_mhd_energy`` (two); ``residual_gauss`` takes
+``fused:flat_linear2`` through ``pre_vjpflat_linear2_f32``.  The host checks are those of ``flat=True`` with their reasons,
+``rows of the fields not dense`` for the channels a non-linear equation reads, and ``declined by the library`` where the
+library has no instantiation for the operators' tap structure (general stars: momentum and energy).  The gradient is dense
+in the input's memory order; a unit-stride input takes ``fused:mhd_*`` as with ``mhd=True``.
+
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
 ``_method.Method`` (shared with ``screen``); ``_Spec`` adds the kinds that have a fused VJP, the order of the reasons of
 ``prepare`` / ``prepare_flat`` and ONE launcher (``vjp``; ``flat=True``: the merged-row library).  ``_LossFn`` is the one
@@ -78,7 +89,9 @@ _last_route = None
 
 def last_route():
     """'fused:<kind>' (kind: stencil3d, stencil2d, linear2, burgers, ns_momentum; with ``flat=True`` also flat_stencil3d,
-    flat_linear2, flat_ns_momentum; with ``mhd=True`` also mhd_continuity, mhd_induction, mhd_momentum, mhd_energy) or 'fallback:<why>' of the last ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
+    flat_linear2, flat_ns_momentum; with ``mhd=True`` also mhd_continuity, mhd_induction, mhd_momentum, mhd_energy; with
+    ``mhd="flat"`` also flat_mhd_continuity, flat_mhd_induction, flat_mhd_momentum, flat_mhd_energy, and flat_linear2 for
+    ``residual_gauss``) or 'fallback:<why>' of the last ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
     return _last_route
 
 
@@ -96,6 +109,7 @@ class _Spec(Method):
     def __init__(self, method, mhd=False):
         super().__init__(method)
         self.mhd = bool(mhd) and self.row in self.MHD_KIND
+        self.mhd_flat = self.mhd and isinstance(mhd, str) and mhd == "flat"     # Nt-fastest inputs too: libcp_pre_vjpflatmhd.so
         if self.mhd:
             self.kind, self.why = self.MHD_KIND[self.row], None
         if self.kind is None and not self.is_op:
@@ -154,15 +168,17 @@ class _Spec(Method):
 
     # -------- flat=True: an input without unit stride on its last axis (host checks + one download)
     def wants_flat(self, x):
-        """Is ``x`` an input ``flat=True`` offers to the merged-row VJP at all?  (Everything else: ``prepare``.)"""
+        """Is ``x`` an input ``flat=True`` (``mhd="flat"``: an MHD residual) offers to the merged-row VJP at all?
+        (Everything else: ``prepare``.)"""
         return x.is_cuda and x.numel() > 0 and x.dim() > 0 and x.stride(-1) != 1
 
     def prepare_flat(self, x, minus=None, wgrad=False):
-        """``prepare`` for the merged-row VJP of ``libcp_pre_vjpflat.so``: (why, kernels).  The layout conditions are the
-        library's own (include/cp_pre_vjpflat.h), stated here so that the reason has a name."""
+        """``prepare`` for the merged-row VJP of ``libcp_pre_vjpflat.so`` (``mhd="flat"``: ``libcp_pre_vjpflatmhd.so``):
+        (why, kernels).  The layout conditions are the library's own (include/cp_pre_vjpflat.h), stated here so that the
+        reason has a name."""
         if self.kind is None:
             return self.why, ()
-        if self.mhd:
+        if self.mhd and not self.mhd_flat:
             return "no flat VJP for MHD", ()
         if self.nd != 3:
             return "no flat VJP for the 1-D family", ()
@@ -179,7 +195,15 @@ class _Spec(Method):
             return "merged row Ny*Nt not a multiple of 4", ()
         if self.kind == "ns_momentum" and any(v.stride(1) != 1 or v.stride(3) != Nt or v.stride(2) != Ny * Nt for v in f[:2]):
             return "rows of u, v not dense", ()
-        return self.star_kernels(self.kind)
+        mhd = self.kind.startswith("mhd_")               # (gauss is linear: its launch reads no field)
+        if mhd and any(v.stride(1) != 1 or v.stride(3) != Nt or v.stride(2) != Ny * Nt for v in f):
+            return "rows of the fields not dense", ()
+        why, kernels = self.star_kernels(self.kind)
+        if why is None and mhd:                          # a tap structure the library has no instantiation for
+            eq = MHD_EQ.index(self.kind[4:])
+            if _lib.load_vjpflatmhd().pre_vjpflatmhd_supported(eq, *kernels) == _lib.PRE_E_UNSUPPORTED:
+                return "declined by the library", ()
+        return why, kernels
 
     # -------- the VJP launch: gfull [BS,*field] -> gradient of x's shape
     def vjp(self, kernels, gfull, x, crop, host_scale, dev_scale, flat=False):
@@ -187,10 +211,16 @@ class _Spec(Method):
         ``flat``: the merged-row launch - ``kernels``: what ``prepare_flat`` returned; ``gfull`` [BS,Nt,Nx,Ny], dense in
         memory order [BS,Nx,Ny,Nt]; the gradient is dense in ``x``'s memory order.  None if the library declines."""
         mhd = self.kind.startswith("mhd_")
-        lib = _lib.load_vjpflat() if flat else _lib.load_vjpmhd() if mhd else _lib.load_vjp()
-        name = ("pre_vjpmhd_" + self.kind[4:] if mhd else ("pre_vjpflat_" if flat else "pre_vjp_") + self.kind) + "_f32"
+        if mhd:
+            lib = _lib.load_vjpflatmhd() if flat else _lib.load_vjpmhd()
+        else:
+            lib = _lib.load_vjpflat() if flat else _lib.load_vjp()
+        name = (("pre_vjpflatmhd_" if flat else "pre_vjpmhd_") + self.kind[4:] if mhd else
+                ("pre_vjpflat_" if flat else "pre_vjp_") + self.kind) + "_f32"
         scalars = self.scalars() if not mhd or self.kind == "mhd_energy" else ()
         grad = _lib.empty_like_layout(x) if flat else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        if flat and self.mhd_flat:                       # (what this module allocates: an extent of 1 may carry any stride)
+            grad, gfull = _nt_fastest_strides(grad), _nt_fastest_strides(gfull)
         if not flat and gfull.stride(-1) != 1:
             gfull = gfull.contiguous()
         if self.kind == "ns_momentum":
@@ -247,6 +277,17 @@ class _Spec(Method):
             return None
         _lib.check(rc, "pre_wgrad_stencil3d_f32")
         return dk
+
+
+def _nt_fastest_strides(v):
+    """``v`` [...,Nt,Nx,Ny], dense in memory order [...,Nx,Ny,Nt], with the strides of that order written out on its last
+    three axes: torch is free to give an axis of extent 1 any stride, the merged-row libraries read them all.  The same
+    memory; ``v`` itself where an axis longer than 1 has another stride."""
+    Nt, Nx, Ny = v.shape[-3:]
+    want = tuple(v.stride()[:-3]) + (1, Ny * Nt, Nt)
+    if v.stride() == want or any(s != w and n != 1 for s, w, n in zip(v.stride(), want, v.shape)):
+        return v
+    return v.as_strided(tuple(v.shape), want, v.storage_offset())
 
 
 def _nt_fastest_dense(r):
@@ -367,7 +408,7 @@ def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False, mhd=Fals
     if yy is not None:
         _check_like(yy, pred, "yy")
     data = None if yy is None else yy.detach()
-    flat, r = bool(flat and spec.wants_flat(pred)), None
+    flat, r = bool((flat or spec.mhd_flat) and spec.wants_flat(pred)), None
     if flat:
         why, kernels = spec.prepare_flat(pred, yy, wgrad)
         if why is None:
@@ -395,7 +436,8 @@ def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False, mhd=
     keeps the fused route and gets ``kernel.grad`` from one launch of ``pre_wgrad_stencil3d_f32`` (route ``...+wgrad``);
     NS momentum, NS continuity, Burgers and any residual where several operator kernels require grad keep
     ``fallback:operator kernel requires grad``.  ``mhd=True``: the ideal-MHD residuals take the fused backward passes of
-    ``libcp_pre_vjpmhd.so`` (module docstring)."""
+    ``libcp_pre_vjpmhd.so``; ``mhd="flat"``: the same, and an Nt-fastest ``pred`` takes those of
+    ``libcp_pre_vjpflatmhd.so`` whatever ``flat`` says (module docstring)."""
     return _loss(residual_method, pred, None, boundary, flat, wgrad, mhd)
 
 
@@ -415,14 +457,14 @@ def residual_vjp(residual_method, vars, g, boundary=False, flat=False, mhd=False
     spec = _Spec(residual_method, mhd)
     _check_tensor(vars, "vars")
     _check_like(g, vars, "g", spec.out_shape(vars, boundary))
-    if flat and spec.wants_flat(vars):
+    if (flat or spec.mhd_flat) and spec.wants_flat(vars):
         why, kernels = spec.prepare_flat(vars)
         if why is not None:
             _last_route = "fallback:" + why
             return _recompute_grad(spec, vars, None, boundary, g)
         _last_route = "fused:flat_" + spec.kind
         if g.numel() == 0:                               # (an empty interior: nothing reaches vars)
-            return torch.zeros(vars.shape, dtype=torch.float32, device=vars.device)
+            return _lib.empty_like_layout(vars).zero_()
         with torch.no_grad():
             gfull = _lib.empty_like_layout(spec.fields(vars)[0])         # g in vars' memory order, the rim zero
             if boundary:

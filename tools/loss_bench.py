@@ -27,10 +27,19 @@ autograd) on a C4-shard-like [16,6,64,256,256], alternating in one process, with
 launches alone (``residual_vjp`` with a full-grid g) against a device copy of the six fields timed in the same run and against
 the algorithmic bytes of the equation (28, 36, 56 and 60 B per cell).  They run only when named in --cases.
 
+Cases ``mhd_continuity_ntfast``, ``mhd_induction_ntfast``, ``mhd_momentum_ntfast`` and ``mhd_energy_ntfast`` are the view the
+reference's MHD callers pass, ``pred.permute(0,1,4,2,3)`` of memory [16,6,256,256,32]: ``pi_loss(..., mhd="flat")`` +
+``backward()`` (the merged-row launches of ``libcp_pre_vjpflatmhd.so``) against the same call with ``mhd=True`` (what that
+keyword does on this view: ``fallback:no unit stride on the last axis``, the composed expression under autograd), alternating
+call by call in one process: medians of --reps measurements with [min, max], and the peak memory of both in fields.  They run
+only when named in --cases.
+
     python tools/loss_bench.py [--reps 7] [--warmup 2] [--out profiles/loss/loss_bench.txt] [--max-batch 16]
     python tools/loss_bench.py --cases wave_ntfast,ns_momentum_ntfast --out profiles/losses/loss_bench_ntfast.txt
     python tools/loss_bench.py --cases wave_kgrad,wave_ntfast_kgrad --out profiles/losses/loss_bench_kgrad.txt
     python tools/loss_bench.py --cases mhd_continuity,mhd_induction,mhd_momentum,mhd_energy --out profiles/losses/loss_bench_mhd.txt
+    python tools/loss_bench.py --cases mhd_continuity_ntfast,mhd_induction_ntfast,mhd_momentum_ntfast,mhd_energy_ntfast \
+        --out profiles/losses/loss_bench_mhd_ntfast.txt
     rocprofv3 --kernel-trace --stats -- python tools/loss_bench.py --vjp-only      # the VJP kernel under the profiler
 """
 import argparse
@@ -206,6 +215,36 @@ def mhd_case(name, bs, rand, reps, warmup, emit):
          f"{48 * cells / (mc * 1e-3) / 1e12:.2f} TB/s: the launches move their bytes at {nb / mv / (48 * cells / mc):.2f} of the copy's rate")
 
 
+def mhd_ntfast_case(name, bs, rand, reps, warmup, emit):
+    """``mhd="flat"`` against ``mhd=True`` (the fallback on this view) on ``pred.permute(0,1,4,2,3)`` of [bs,6,256,256,32],
+    interleaved"""
+    eq = name[4:-7]
+    method = getattr(R.MHD(), "residual_" + eq)
+    pred = rand(bs, 6, 256, 256, 32).requires_grad_(True)
+    routes = {}
+
+    def step(mhd):
+        def f():
+            pred.grad = None
+            losses.pi_loss(method, pred.permute(0, 1, 4, 2, 3), mhd=mhd).backward()
+            routes[mhd] = losses.last_route()
+        return f
+    a, b = step("flat"), step(True)
+    a()
+    ga = pred.grad.clone()
+    b()
+    err = float((ga - pred.grad).abs().max() / pred.grad.abs().max())
+    del ga
+    pa, pb = peak_of(a), peak_of(b)
+    (ma, la, ha), (mb, lb, hb) = alternate_spread([a, b], reps, warmup)
+    field = pred.numel() // 6 * 4
+    apart = "apart" if ha < lb else "OVERLAPPING"
+    emit(f"{name}: memory {list(pred.shape)}; mhd=\"flat\" route {routes['flat']} {ma:.3f} ms [{la:.3f}, {ha:.3f}], mhd=True route "
+         f"{routes[True]} {mb:.3f} ms [{lb:.3f}, {hb:.3f}], True/flat = {mb / ma:.2f}x, [min, max] {apart}; peak memory mhd=\"flat\" "
+         f"{pa / field:.2f} fields ({pa / 2**30:.2f} GiB), mhd=True {pb / field:.2f} fields ({pb / 2**30:.2f} GiB); "
+         f"max |grad flat - grad True| / max |grad True| = {err:.2e}")
+
+
 def steps(method, v):
     def a():
         v.grad = None
@@ -226,7 +265,8 @@ def main():
     ap.add_argument("--vjp-only", action="store_true", help="only a few NS momentum VJP launches (for a profiler)")
     ap.add_argument("--cases", default="ns_momentum,burgers,wave",
                     help="comma-separated: ns_momentum, burgers, wave, wave_ntfast, ns_momentum_ntfast, wave_kgrad, "
-                         "wave_ntfast_kgrad, mhd_continuity, mhd_induction, mhd_momentum, mhd_energy")
+                         "wave_ntfast_kgrad, mhd_continuity, mhd_induction, mhd_momentum, mhd_energy, mhd_continuity_ntfast, "
+                         "mhd_induction_ntfast, mhd_momentum_ntfast, mhd_energy_ntfast")
     args = ap.parse_args()
     wanted = [c for c in args.cases.split(",") if c]
     assert torch.cuda.is_available(), "loss_bench needs the MI355X"
@@ -260,13 +300,16 @@ def main():
         ("wave", lambda bs: rand(bs, 64, 512, 512), R.PRE_Wave(0.01, 1 / 512).residual, args.max_batch, 5),
     ]
     for name in wanted:
-        if name.startswith("mhd_"):
+        if name.startswith("mhd_") and name.endswith("_ntfast"):
+            mhd_ntfast_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
+            torch.cuda.empty_cache()
+        elif name.startswith("mhd_"):
             mhd_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
             torch.cuda.empty_cache()
-        if name.endswith("_kgrad"):
+        elif name.endswith("_kgrad"):
             kgrad_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
             torch.cuda.empty_cache()
-        if name.endswith("_ntfast"):
+        elif name.endswith("_ntfast"):
             ntfast_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
             torch.cuda.empty_cache()
     for name, mk, method, cap, streams_a in cases:
