@@ -316,6 +316,17 @@ VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
 PRE_VJPFLATMHD_ABI_VERSION = 1
 VJPFLATMHD_SIGNATURES = {name.replace("pre_vjpmhd_", "pre_vjpflatmhd_"): sig for name, sig in VJPMHD_SIGNATURES.items()}
 
+# libcp_pre_vjpjorek.so (include/cp_pre_vjpjorek.h): the vector-Jacobian products of the reduced-MHD (JOREK) residuals for
+# Nt-fastest views: the merged-row geometry of libcp_pre_vjpflat.so with three planes in LDS
+VJPJOREK_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpjorek.so")
+PRE_VJPJOREK_ABI_VERSION = 1
+VJPJOREK_SIGNATURES = {
+    "pre_vjpjorek_abi_version": [],
+    "pre_vjpjorek_supported": [c_int] + [POINTER(c_float)] * 5,
+    # eq, g, fields, Rb, out, K_t .. K_ZZ, coef, then the tail of the MHD entries
+    "pre_vjpjorek_flat_f32": [c_int, _fld, POINTER(PreField), _fld, POINTER(PreField)] + [POINTER(c_float)] * 6 + _mhdtail,
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -345,8 +356,9 @@ _LIBS_MORE = {
     "vjpmhd": ("_vjpmhd", "VJPMHD_", "pre_vjpmhd_abi_version", "PRE_VJPMHD_ABI_VERSION", ()),
     "screenjorek": ("_screenjorek", "SCREENJOREK_", "pre_screenjorek_abi_version", "PRE_SCREENJOREK_ABI_VERSION", ()),
     "vjpflatmhd": ("_vjpflatmhd", "VJPFLATMHD_", "pre_vjpflatmhd_abi_version", "PRE_VJPFLATMHD_ABI_VERSION", ()),
+    "vjpjorek": ("_vjpjorek", "VJPJOREK_", "pre_vjpjorek_abi_version", "PRE_VJPJOREK_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -451,6 +463,10 @@ def load_screenjorek():
 
 def load_vjpflatmhd():
     return _vjpflatmhd or _load("vjpflatmhd")
+
+
+def load_vjpjorek():
+    return _vjpjorek or _load("vjpjorek")
 
 
 def require_gpu():

@@ -69,6 +69,19 @@ says; the library loads only when that route is taken.  Routes ``fused:flat_mhd_
 library has no instantiation for the operators' tap structure (general stars: momentum and energy).  The gradient is dense
 in the input's memory order; a unit-stride input takes ``fused:mhd_*`` as with ``mhd=True``.
 
+``jorek=True`` (off by default: nothing above changes, ``libcp_pre_vjpjorek.so`` is never loaded and the reduced-MHD residuals
+keep ``fallback:no fused VJP for JOREK``) gives ``JOREK.residual_continuity`` / ``residual_temperature`` a fused backward pass
+on the layout ``Joint/JOREK_residuals_CP.py`` holds: a CUDA ``vars`` ``[BS,F>=3,Nx,Ny,Nt]`` whose field views
+(``JOREK.unstack_fields``) are Nt-fastest with dense rows, whatever ``flat`` says (``include/cp_pre_vjpjorek.h``: the merged-row
+march with three planes of rho, phi (and T) in LDS, because the gradient at a cell reads phi at the four corners of the
+(R, Z) plane).  Routes ``fused:flat_jorek_continuity`` (one launch) and ``fused:flat_jorek_temperature`` (two, split by output
+group).  ``norms=True`` of the continuity equation: hand over ``functools.partial(jorek.residual_continuity, norms=True)``.
+The library is built for the tap structure the reference constructs; ``y_axis_fix`` operators and general stars take
+``fallback:declined by the library``, Ny-fastest field views ``fallback:fields not Nt-fastest``, and the host checks of
+``flat=True`` keep their reasons (``Nt >= 96``, ``merged row Ny*Nt not a multiple of 4``, ``rows of the fields not dense``,
+``operator kernel requires grad``).  The gradient is dense in ``vars``' memory order; T (continuity) and every channel
+from 3 on get a zero gradient.
+
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
 ``_method.Method`` (shared with ``screen``); ``_Spec`` adds the kinds that have a fused VJP, the order of the reasons of
 ``prepare`` / ``prepare_flat`` and ONE launcher (``vjp``; ``flat=True``: the merged-row library).  ``_LossFn`` is the one
@@ -77,6 +90,7 @@ Host side: what a method is, what it reads and what declines a fused launch what
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
 
@@ -91,7 +105,7 @@ def last_route():
     """'fused:<kind>' (kind: stencil3d, stencil2d, linear2, burgers, ns_momentum; with ``flat=True`` also flat_stencil3d,
     flat_linear2, flat_ns_momentum; with ``mhd=True`` also mhd_continuity, mhd_induction, mhd_momentum, mhd_energy; with
     ``mhd="flat"`` also flat_mhd_continuity, flat_mhd_induction, flat_mhd_momentum, flat_mhd_energy, and flat_linear2 for
-    ``residual_gauss``) or 'fallback:<why>' of the last ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
+    ``residual_gauss``; with ``jorek=True`` also flat_jorek_continuity, flat_jorek_temperature) or 'fallback:<why>' of the last ``pi_loss`` / ``pisl_loss`` / ``residual_vjp`` call."""
     return _last_route
 
 
@@ -106,8 +120,20 @@ class _Spec(Method):
     # ``mhd=True``: the kinds of libcp_pre_vjpmhd.so (gauss is two linear operators: ``pre_vjp_linear2_f32``)
     MHD_KIND = {**{"mhd_" + e: "mhd_" + e for e in MHD_EQ}, "mhd_gauss": "linear2"}
 
-    def __init__(self, method, mhd=False):
-        super().__init__(method)
+    JOREK_EQ = {"residual_continuity": 0, "residual_temperature": 1}
+
+    def __init__(self, method, mhd=False, jorek=False):
+        bound, self.norms = method, False
+        if jorek and isinstance(method, functools.partial) and not method.args and set(method.keywords) <= {"norms"} and \
+                isinstance(getattr(method.func, "__self__", None), R.JOREK):
+            bound, self.norms = method.func, bool(method.keywords.get("norms", False))      # (the one keyword of the equations)
+        super().__init__(bound)
+        self.method = method
+        name = getattr(bound, "__name__", "")
+        self.jorek = bool(jorek) and self.row == "jorek" and name in self.JOREK_EQ
+        if self.jorek:                                           # the kinds of libcp_pre_vjpjorek.so
+            self.eq = self.JOREK_EQ[name]
+            self.kind, self.why, self.ops = "jorek_" + name[len("residual_"):], None, tuple(self.obj._ops())
         self.mhd = bool(mhd) and self.row in self.MHD_KIND
         self.mhd_flat = self.mhd and isinstance(mhd, str) and mhd == "flat"     # Nt-fastest inputs too: libcp_pre_vjpflatmhd.so
         if self.mhd:
@@ -205,11 +231,63 @@ class _Spec(Method):
                 return "declined by the library", ()
         return why, kernels
 
+    # -------- jorek=True: vars [BS,F,Nx,Ny,Nt] as the script holds it (host checks + one download)
+    def prepare_jorek(self, x, minus=None):
+        """``prepare_flat`` for ``libcp_pre_vjpjorek.so``: (why, kernels).  The layout is decided on the field views of
+        ``JOREK.unstack_fields``; the conditions are the library's own (include/cp_pre_vjpjorek.h)."""
+        if not x.is_cuda or (minus is not None and not minus.is_cuda):
+            return "input on the CPU", ()
+        if x.numel() == 0:
+            return "empty input", ()
+        why = self.declined(x, minus)
+        if why is not None:
+            return why, ()
+        if x.shape[1] < 3:
+            return "fewer than three JOREK channels", ()
+        f = R.JOREK.unstack_fields(x)[:2 + self.eq]
+        Nt, Nx, Ny = f[0].shape[1:]
+        if Nt > 1 and any(v.stride(1) != 1 for v in f):
+            return "fields not Nt-fastest", ()
+        if Nt >= FLAT_MAX_NT:
+            return "Nt >= %d" % FLAT_MAX_NT, ()
+        if (Ny * Nt) % 4 != 0:
+            return "merged row Ny*Nt not a multiple of 4", ()
+        if any(n != 1 and st != w for v in f for n, st, w in zip((Nx, Ny), v.stride()[2:], (Ny * Nt, Nt))):
+            return "rows of the fields not dense", ()
+        if self.obj.R.numel() != Ny:                             # (``JOREK._R_view`` raises: so does every route)
+            return "len(R) is not Ny", ()
+        why, kernels = self.star_kernels(self.kind)
+        if why is None and _lib.load_vjpjorek().pre_vjpjorek_supported(self.eq, *kernels) == _lib.PRE_E_UNSUPPORTED:
+            return "declined by the library", ()                 # (y_axis_fix, general stars: not the reference's tap structure)
+        return why, kernels
+
+    def vjp_jorek(self, kernels, gfull, x, crop, host_scale, dev_scale):
+        """``gfull`` [BS,Nt,Nx,Ny], dense in memory order [BS,Nx,Ny,Nt]; ``x`` the ``vars`` ``prepare_jorek`` accepted.  The
+        gradient is dense in ``x``'s memory order.  None if the library declines."""
+        nf = 2 + self.eq
+        grad = _lib.empty_like_layout(x)
+        gfull = _nt_fastest_strides(gfull)
+        fs = [_nt_fastest_strides(v) for v in R.JOREK.unstack_fields(x)[:3]]
+        os_ = [_nt_fastest_strides(v) for v in R.JOREK.unstack_fields(grad)[:3]]
+        Rb = self.obj._R_view(fs[0])
+        with torch.cuda.device(x.device):
+            rc = _lib.load_vjpjorek().pre_vjpjorek_flat_f32(
+                self.eq, ctypes.byref(_lib.field(gfull)), R._arr(fs), ctypes.byref(_lib.field(Rb)), R._arr(os_), *kernels,
+                _lib.farr(self.obj._coef(self.eq, self.norms)), float(host_scale), _lib.ptr(dev_scale), *gfull.shape,
+                _lib.PRE_VJP_CROP if crop else 0, _lib.stream())
+        if rc == _lib.PRE_E_UNSUPPORTED:
+            return None
+        _lib.check(rc, "pre_vjpjorek_flat_f32")
+        grad[:, nf:].zero_()                                     # (T under continuity, every channel from 3 on: not read)
+        return grad
+
     # -------- the VJP launch: gfull [BS,*field] -> gradient of x's shape
     def vjp(self, kernels, gfull, x, crop, host_scale, dev_scale, flat=False):
         """``kernels``: what ``prepare`` returned; ``gfull`` [BS,*field] (copied unless its last axis has unit stride).
         ``flat``: the merged-row launch - ``kernels``: what ``prepare_flat`` returned; ``gfull`` [BS,Nt,Nx,Ny], dense in
         memory order [BS,Nx,Ny,Nt]; the gradient is dense in ``x``'s memory order.  None if the library declines."""
+        if self.jorek:
+            return self.vjp_jorek(kernels, gfull, x, crop, host_scale, dev_scale)
         mhd = self.kind.startswith("mhd_")
         if mhd:
             lib = _lib.load_vjpflatmhd() if flat else _lib.load_vjpmhd()
@@ -400,17 +478,17 @@ class _LossFn(torch.autograd.Function):
         return grad, gk, None, None, None, None, None, None
 
 
-def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False, mhd=False):
+def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False, mhd=False, jorek=False):
     global _last_route
-    spec = _Spec(residual_method, mhd)
+    spec = _Spec(residual_method, mhd, jorek)
     _check_tensor(pred, "pred")
     spec.field_shape(pred)                               # (called for its raise: a rank the method does not take)
     if yy is not None:
         _check_like(yy, pred, "yy")
     data = None if yy is None else yy.detach()
-    flat, r = bool((flat or spec.mhd_flat) and spec.wants_flat(pred)), None
+    flat, r = bool(spec.jorek or ((flat or spec.mhd_flat) and spec.wants_flat(pred))), None
     if flat:
-        why, kernels = spec.prepare_flat(pred, yy, wgrad)
+        why, kernels = spec.prepare_jorek(pred, yy) if spec.jorek else spec.prepare_flat(pred, yy, wgrad)
         if why is None:
             r = spec.full(pred, data)
             if not _nt_fastest_dense(r):
@@ -425,7 +503,7 @@ def _loss(residual_method, pred, yy, boundary, flat=False, wgrad=False, mhd=Fals
     return _LossFn.apply(pred, spec.ops[0].kernel if trains else None, spec, kernels, data, bool(boundary), flat, r)
 
 
-def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False, mhd=False):
+def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False, mhd=False, jorek=False):
     """``residual_method(pred, boundary).pow(2).mean()`` (``PI_loss``, Physics_Informed/Wave_FNO_PISL.py:213-214) as a
     0-d fp32 tensor on ``pred``'s device, differentiable with respect to ``pred``.  ``residual_method``: a bound
     ``residual*`` method of a class of ``cp_pre_amd.residuals``, or a ``ConvOperator`` (2-D: [BS,Nt,Nx,Ny], 1-D:
@@ -437,28 +515,30 @@ def pi_loss(residual_method, pred, boundary=False, flat=False, wgrad=False, mhd=
     NS momentum, NS continuity, Burgers and any residual where several operator kernels require grad keep
     ``fallback:operator kernel requires grad``.  ``mhd=True``: the ideal-MHD residuals take the fused backward passes of
     ``libcp_pre_vjpmhd.so``; ``mhd="flat"``: the same, and an Nt-fastest ``pred`` takes those of
-    ``libcp_pre_vjpflatmhd.so`` whatever ``flat`` says (module docstring)."""
-    return _loss(residual_method, pred, None, boundary, flat, wgrad, mhd)
+    ``libcp_pre_vjpflatmhd.so`` whatever ``flat`` says (module docstring).  ``jorek=True``: the reduced-MHD (JOREK) residuals
+    take the fused backward passes of ``libcp_pre_vjpjorek.so`` on ``pred`` [BS,F>=3,Nx,Ny,Nt] (module docstring)."""
+    return _loss(residual_method, pred, None, boundary, flat, wgrad, mhd, jorek)
 
 
-def pisl_loss(residual_method, pred, yy, boundary=False, flat=False, wgrad=False, mhd=False):
+def pisl_loss(residual_method, pred, yy, boundary=False, flat=False, wgrad=False, mhd=False, jorek=False):
     """``(residual(pred) - residual(yy)).pow(2).mean()`` (``PISL``, Physics_Informed/Wave_FNO_PISL.py:216-217).  ``yy``
     (``pred``'s shape, dtype and device) is data: the fused route does not differentiate it (one that requires grad takes
-    the fallback, which does).  ``flat``, ``wgrad`` and ``mhd`` as on ``pi_loss`` (the kernel gradient reads ``pred - yy``)."""
-    return _loss(residual_method, pred, yy, boundary, flat, wgrad, mhd)
+    the fallback, which does).  ``flat``, ``wgrad``, ``mhd`` and ``jorek`` as on ``pi_loss`` (the kernel gradient reads
+    ``pred - yy``)."""
+    return _loss(residual_method, pred, yy, boundary, flat, wgrad, mhd, jorek)
 
 
-def residual_vjp(residual_method, vars, g, boundary=False, flat=False, mhd=False):
+def residual_vjp(residual_method, vars, g, boundary=False, flat=False, mhd=False, jorek=False):
     """The vector-Jacobian product ``d <g, residual_method(vars, boundary)> / d vars`` for a general upstream gradient
     ``g`` (the shape of the method's result), by the kernels the losses use.  Returns a tensor of ``vars``' shape.
-    ``flat`` and ``mhd`` as on ``pi_loss`` (``flat``: the gradient is then dense in ``vars``' memory order).  Operator
+    ``flat``, ``mhd`` and ``jorek`` as on ``pi_loss`` (``flat``, ``jorek``: the gradient is then dense in ``vars``' memory order).  Operator
     kernels that require grad take ``fallback:operator kernel requires grad`` here (their own gradient: ``kernel_vjp``)."""
     global _last_route
-    spec = _Spec(residual_method, mhd)
+    spec = _Spec(residual_method, mhd, jorek)
     _check_tensor(vars, "vars")
     _check_like(g, vars, "g", spec.out_shape(vars, boundary))
-    if (flat or spec.mhd_flat) and spec.wants_flat(vars):
-        why, kernels = spec.prepare_flat(vars)
+    if spec.jorek or ((flat or spec.mhd_flat) and spec.wants_flat(vars)):
+        why, kernels = spec.prepare_jorek(vars) if spec.jorek else spec.prepare_flat(vars)
         if why is not None:
             _last_route = "fallback:" + why
             return _recompute_grad(spec, vars, None, boundary, g)
@@ -466,7 +546,8 @@ def residual_vjp(residual_method, vars, g, boundary=False, flat=False, mhd=False
         if g.numel() == 0:                               # (an empty interior: nothing reaches vars)
             return _lib.empty_like_layout(vars).zero_()
         with torch.no_grad():
-            gfull = _lib.empty_like_layout(spec.fields(vars)[0])         # g in vars' memory order, the rim zero
+            f0 = R.JOREK.unstack_fields(vars)[0] if spec.jorek else spec.fields(vars)[0]
+            gfull = _lib.empty_like_layout(f0)                           # g in vars' memory order, the rim zero
             if boundary:
                 gfull.copy_(g)
             else:

@@ -34,12 +34,21 @@ keyword does on this view: ``fallback:no unit stride on the last axis``, the com
 call by call in one process: medians of --reps measurements with [min, max], and the peak memory of both in fields.  They run
 only when named in --cases.
 
+Cases ``jorek_continuity_ntfast`` and ``jorek_temperature_ntfast`` are the reduced-MHD residuals on the script's dense
+``vars`` [96,3,256,256,40] (the shape of tools/screen_bench.py's cases of the same names; Nt-fastest field views):
+``pi_loss(..., jorek=True)`` + ``backward()`` against the same call without the keyword (``fallback:no fused VJP for JOREK``: the
+composed expression under autograd), alternating call by call in one process, with the peak memory of both; then
+``loss.backward()`` alone on both routes (the forward outside the timed region), and the VJP launches alone (``residual_vjp``
+with a full-grid g) against a device copy of the three fields timed in the same run and against the algorithmic bytes of the
+equation (20 and 28 B per cell).  They run only when named in --cases.
+
     python tools/loss_bench.py [--reps 7] [--warmup 2] [--out profiles/loss/loss_bench.txt] [--max-batch 16]
     python tools/loss_bench.py --cases wave_ntfast,ns_momentum_ntfast --out profiles/losses/loss_bench_ntfast.txt
     python tools/loss_bench.py --cases wave_kgrad,wave_ntfast_kgrad --out profiles/losses/loss_bench_kgrad.txt
     python tools/loss_bench.py --cases mhd_continuity,mhd_induction,mhd_momentum,mhd_energy --out profiles/losses/loss_bench_mhd.txt
     python tools/loss_bench.py --cases mhd_continuity_ntfast,mhd_induction_ntfast,mhd_momentum_ntfast,mhd_energy_ntfast \
         --out profiles/losses/loss_bench_mhd_ntfast.txt
+    python tools/loss_bench.py --cases jorek_continuity_ntfast,jorek_temperature_ntfast --out profiles/losses/loss_bench_jorek_ntfast.txt
     rocprofv3 --kernel-trace --stats -- python tools/loss_bench.py --vjp-only      # the VJP kernel under the profiler
 """
 import argparse
@@ -245,6 +254,67 @@ def mhd_ntfast_case(name, bs, rand, reps, warmup, emit):
          f"max |grad flat - grad True| / max |grad True| = {err:.2e}")
 
 
+JOREK_BYTES = {"continuity": 20, "temperature": 28}      # algorithmic bytes per cell: gg and the fields read, the gradients written
+
+
+def jorek_ntfast_case(name, bs, rand, reps, warmup, emit):
+    """``jorek=True`` against the same call without it (the parent's route) on the script's vars [bs,3,256,256,40],
+    interleaved; ``backward()`` alone; the VJP launches alone against a device copy"""
+    eq = name[len("jorek_"):-len("_ntfast")]
+    method = getattr(R.JOREK(torch.linspace(1, 2, 256)), "residual_" + eq)
+    pred = rand(bs, 3, 256, 256, 40).requires_grad_(True)
+    routes = {}
+
+    def step(jorek):
+        def f():
+            pred.grad = None
+            losses.pi_loss(method, pred, jorek=jorek).backward()
+            routes[jorek] = losses.last_route()
+        return f
+    a, b = step(True), step(False)
+    a()
+    ga = pred.grad.clone()
+    b()
+    err = float((ga - pred.grad).abs().max() / pred.grad.abs().max())
+    del ga
+    pa, pb = peak_of(a), peak_of(b)
+    (ma, la, ha), (mb, lb, hb) = alternate_spread([a, b], reps, warmup)
+    cells = pred.numel() // 3
+    field = cells * 4
+    apart = "apart" if ha < lb else "OVERLAPPING"
+    emit(f"{name}: memory {list(pred.shape)}; jorek=True route {routes[True]} {ma:.3f} ms [{la:.3f}, {ha:.3f}], jorek=False route "
+         f"{routes[False]} {mb:.3f} ms [{lb:.3f}, {hb:.3f}], False/True = {mb / ma:.2f}x, [min, max] {apart}; peak memory jorek=True "
+         f"{pa / field:.2f} fields ({pa / 2**30:.2f} GiB), jorek=False {pb / field:.2f} fields ({pb / 2**30:.2f} GiB); "
+         f"max |grad True - grad False| / max |grad False| = {err:.2e}")
+    # backward() alone: the forward (the same fused residual pass on both routes, and the graph of the fallback) is not timed
+    back = {True: [], False: []}
+    for i in range(warmup + reps):
+        for jorek in (True, False):
+            pred.grad = None
+            loss = losses.pi_loss(method, pred, jorek=jorek)
+            t0, t1 = _ev(), _ev()
+            t0.record()
+            loss.backward()
+            t1.record()
+            t1.synchronize()
+            if i >= warmup:
+                back[jorek].append(t0.elapsed_time(t1))
+            del loss
+    med = {k: (sorted(t)[len(t) // 2], min(t), max(t)) for k, t in back.items()}
+    emit(f"{name} backward() alone: jorek=True {med[True][0]:.3f} ms [{med[True][1]:.3f}, {med[True][2]:.3f}], jorek=False "
+         f"{med[False][0]:.3f} ms [{med[False][1]:.3f}, {med[False][2]:.3f}], False/True = {med[False][0] / med[True][0]:.2f}x")
+    pred.grad = None
+    vd, gg, dst = pred.detach(), rand(bs, 256, 256, 40).permute(0, 3, 1, 2), torch.empty_like(pred)
+    (mv, lv, hv), (mc, lc, hc) = alternate_spread([lambda: losses.residual_vjp(method, vd, gg, boundary=True, jorek=True),
+                                                   lambda: dst.copy_(vd)], reps, warmup)
+    nb = JOREK_BYTES[eq] * cells
+    emit(f"{name} VJP launches alone (route {routes[True]}, device events around the call, the copy of g and "
+         f"the zeroing of unread channels included): {mv:.3f} ms [{lv:.3f}, {hv:.3f}], {JOREK_BYTES[eq]} B x {cells} cells / time = "
+         f"{nb / (mv * 1e-3) / 1e12:.2f} TB/s = {nb / (mv * 1e-3) / HBM:.3f} of 8 TB/s; device copy of the three fields (24 B per cell) "
+         f"{mc:.3f} ms [{lc:.3f}, {hc:.3f}] = {24 * cells / (mc * 1e-3) / 1e12:.2f} TB/s: the launches move their bytes at "
+         f"{nb / mv / (24 * cells / mc):.2f} of the copy's rate")
+
+
 def steps(method, v):
     def a():
         v.grad = None
@@ -266,7 +336,8 @@ def main():
     ap.add_argument("--cases", default="ns_momentum,burgers,wave",
                     help="comma-separated: ns_momentum, burgers, wave, wave_ntfast, ns_momentum_ntfast, wave_kgrad, "
                          "wave_ntfast_kgrad, mhd_continuity, mhd_induction, mhd_momentum, mhd_energy, mhd_continuity_ntfast, "
-                         "mhd_induction_ntfast, mhd_momentum_ntfast, mhd_energy_ntfast")
+                         "mhd_induction_ntfast, mhd_momentum_ntfast, mhd_energy_ntfast, jorek_continuity_ntfast, "
+                         "jorek_temperature_ntfast")
     args = ap.parse_args()
     wanted = [c for c in args.cases.split(",") if c]
     assert torch.cuda.is_available(), "loss_bench needs the MI355X"
@@ -300,7 +371,10 @@ def main():
         ("wave", lambda bs: rand(bs, 64, 512, 512), R.PRE_Wave(0.01, 1 / 512).residual, args.max_batch, 5),
     ]
     for name in wanted:
-        if name.startswith("mhd_") and name.endswith("_ntfast"):
+        if name.startswith("jorek_") and name.endswith("_ntfast"):
+            jorek_ntfast_case(name, min(6 * args.max_batch, 96), rand, args.reps, args.warmup, emit)
+            torch.cuda.empty_cache()
+        elif name.startswith("mhd_") and name.endswith("_ntfast"):
             mhd_ntfast_case(name, min(args.max_batch, 16), rand, args.reps, args.warmup, emit)
             torch.cuda.empty_cache()
         elif name.startswith("mhd_"):
