@@ -7,6 +7,7 @@
 // sample row (coalesced), and a lane walks the batch axis for its own cell, so per-cell
 // state (running sums, radix prefixes) lives in registers and never crosses lanes.
 #include "common.h"
+#include "guarded_divide.h"
 
 // The reductions below reproduce numpy's operation order: a*b+c must stay two roundings.
 // This file is compiled with -ffp-contract=off (csrc/Makefile); the pragma covers other builds.
@@ -513,27 +514,21 @@ __device__ __forceinline__ float wave_max(float v)
 // grid (row-chunks, n); one block reduces JS_RB rows (t,x) of sample blockIdx.y.
 // max_i |v_i|/s_i with IEEE division on every element would make the pass VALU-bound (a
 // correctly rounded fp32 divide is ~10 instructions).  Each lane keeps its exact running
-// maximum m and first tests |v| > m(1-2^-20)*s (one multiply, one compare): a quotient that
-// rounds above m always passes (|v|/s >= q(1-2^-24) > m(1-2^-24)), so only the few candidates
-// that can raise the maximum pay for the exact divide, and the result is bit-identical to
-// dividing everything.
+// maximum m and skips a cell only when p = fl(fl(m(1-2^-20)) * s) is a normal number and
+// |v| <= p (one multiply, three compares against p): guarded_divide.h shows that
+// fl(|v|/s) <= m then, for every fp32 input, so only the few candidates that can raise the
+// maximum pay for the exact divide, and the result is bit-identical to dividing everything.
 constexpr int JS_RB = 32;
 #ifndef JS_TARGET_CELLS
 #define JS_TARGET_CELLS 65536    // cells a block of the full score pass takes at least (spans of JS_RB rows; round 6: 8192 ->
                                  // 65536, -5 ... -11 % on every shape of profiles/r06/score_pass_block_ab.txt: 32 KB blocks were too short-lived)
 #endif
-// NaN: np.max propagates it.  A NaN residual or modulation fails `av <= thr*sv` and reaches the divide; 0/0 (a
-// constant cell: modulation 0 and residual 0) reaches it through `sv == 0`; a NaN quotient sets the sticky flag and
-// the sample's score becomes NaN.
+// NaN: np.max propagates it.  A NaN residual or modulation fails `av <= p` and reaches the divide; 0/0 (a constant
+// cell: modulation 0 and residual 0) reaches it because p = thr * 0 is not a normal number; a NaN quotient sets the
+// sticky flag and the sample's score becomes NaN.
 __device__ __forceinline__ void js_update(float av, float sv, float &m, float &thr, bool &nan)
 {
-    // (sv below the smallest normal number: thr * sv is then rounded with an ABSOLUTE error, and "a quotient that rounds
-    // above m always passes" no longer follows - such cells, and sv == 0, always take the divide)
-    if (!(av <= thr * sv) || sv < 1.17549435e-38f) {
-        const float q = av / sv;
-        if (q != q) nan = true;
-        else if (q > m) { m = q; thr = m * 0.99999905f; }
-    }
+    guarded_max_update(av, sv, m, thr, nan);
 }
 
 __global__ void __launch_bounds__(256) joint_score_kernel(const float *__restrict__ a, const float *__restrict__ b,

@@ -4,6 +4,7 @@
 // is one fp32 multiply with contraction off by pragma, the counts go compare -> wave mask -> population count -> scalar add.
 #pragma once
 #include "star_march.h"
+#include "guarded_divide.h"
 #include "../../include/cp_pre_screen.h"
 
 namespace {
@@ -11,17 +12,14 @@ namespace {
 static_assert(PRE_SCREEN_MAX_LEVELS == 16, "the level loop of screen_plane is unrolled 16 times");
 constexpr int NKMAX = PRE_SCREEN_MAX_LEVELS;
 
-// The guarded divide of calib.hip's js_update (a translation unit of libcp_pre_hip.so): the running maximum m of av / sv,
-// bitwise what dividing every element gives.  Only a candidate that can raise the maximum pays for the IEEE division: a
-// quotient that rounds above m always fails `av <= thr * sv` with thr = m(1 - 2^-20).  A NaN av or sv fails it too and
-// reaches the divide, 0/0 reaches it through the subnormal test; a NaN quotient sets the sticky flag.
+// The guarded divide of calib.hip's js_update (a translation unit of libcp_pre_hip.so), stated once in guarded_divide.h:
+// the running maximum m of av / sv, bitwise what dividing every element gives.  Only a candidate that can raise the
+// maximum pays for the IEEE division: a cell is skipped only if p = thr * sv is a normal number and av <= p, which that
+// header shows to imply fl(av / sv) <= m for every fp32 input.  A NaN av or sv fails the compare and reaches the divide,
+// 0/0 reaches it because p is then no normal number; a NaN quotient sets the sticky flag.
 __device__ __forceinline__ void score_update(float av, float sv, float &m, float &thr, bool &nan)
 {
-    if (!(av <= thr * sv) || sv < 1.17549435e-38f) {
-        const float qt = av / sv;
-        if (qt != qt) nan = true;
-        else if (qt > m) { m = qt; thr = m * 0.99999905f; }
-    }
+    guarded_max_update(av, sv, m, thr, nan);
 }
 
 // The end of one plane.  r: the residual quad, mm: its modulation, keep[j]: cell j is counted.  qk / cnt: the levels and
