@@ -310,6 +310,20 @@ SCREENJOREK_SIGNATURES = {
     "pre_screenjorek_flat_f32": _jrk + _scrf,
 }
 
+# libcp_pre_screenpair.so (include/cp_pre_screenpair.h): the two 2-D screens for the data-driven scores r(a) - r(b): each entry
+# takes its single-set twin's arguments with the two field sets in place of the twin's views (PreScreen / PreScreenFlat reused)
+SCREENPAIR_SO_PATH = os.path.join(_HERE, "libcp_pre_screenpair.so")
+PRE_SCREENPAIR_ABI_VERSION = 1
+_arr2 = [POINTER(PreField)] * 2                                         # the two sets: pre_field_t[F] each
+SCREENPAIR_SIGNATURES = {"pre_screenpair_abi_version": []}
+for _form, _tail in (("", _scr), ("flat_", _scrf)):
+    SCREENPAIR_SIGNATURES.update({
+        "pre_screenpair_%sstencil3d_f32" % _form: [_fld, _fld, POINTER(c_float), POINTER(c_int32), c_int] + _tail,
+        "pre_screenpair_%slinear2_f32" % _form: _arr2 + [POINTER(c_float), POINTER(c_float), c_float] + _tail,
+        "pre_screenpair_%sns_momentum_f32" % _form: _arr2 + [POINTER(c_float)] * 4 + [c_float] * 4 + _tail,
+        "pre_screenpair_%smhd_continuity_f32" % _form: _arr2 + [POINTER(c_float)] * 3 + [c_double] + _tail,
+    })
+
 # libcp_pre_vjpflatmhd.so (include/cp_pre_vjpflatmhd.h): the entries of libcp_pre_vjpmhd.so for Nt-fastest views (the march of
 # libcp_pre_vjpflat.so), argument for argument
 VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
@@ -357,8 +371,9 @@ _LIBS_MORE = {
     "screenjorek": ("_screenjorek", "SCREENJOREK_", "pre_screenjorek_abi_version", "PRE_SCREENJOREK_ABI_VERSION", ()),
     "vjpflatmhd": ("_vjpflatmhd", "VJPFLATMHD_", "pre_vjpflatmhd_abi_version", "PRE_VJPFLATMHD_ABI_VERSION", ()),
     "vjpjorek": ("_vjpjorek", "VJPJOREK_", "pre_vjpjorek_abi_version", "PRE_VJPJOREK_ABI_VERSION", ()),
+    "screenpair": ("_screenpair", "SCREENPAIR_", "pre_screenpair_abi_version", "PRE_SCREENPAIR_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -467,6 +482,10 @@ def load_vjpflatmhd():
 
 def load_vjpjorek():
     return _vjpjorek or _load("vjpjorek")
+
+
+def load_screenpair():
+    return _screenpair or _load("screenpair")
 
 
 def require_gpu():

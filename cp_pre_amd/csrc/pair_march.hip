@@ -1,7 +1,8 @@
 // pair_march.hip - data-driven residual scores d = r(a) - r(b) in one streaming pass (libcp_pre_pair.so,
 // include/cp_pre_pair.h).
 //
-// The march of star_march.h evaluates a functor of up to MAXF = 6 field views.  Paired<Fn> is a functor of 2*Fn::F views:
+// The march of star_march.h evaluates a functor of up to MAXF = 6 field views.  Paired<Fn> (paired_functor.h, shared with
+// screen_pair.hip) is a functor of 2*Fn::F views:
 // views [0, F) are the truth set, [F, 2F) the prediction set, and eval = Fn::eval(first half) - Fn::eval(second half).
 // Every layout mode of the march (contiguous, vars[:, i] views, the Nt-fastest relabelling, the flat form, the general
 // star) and every flag (ABS after the subtraction, INTERIOR_T, OUT_INTERIOR_T, HALO_X) comes with it unchanged.
@@ -14,27 +15,10 @@
 #error "PRE_PAIR_PART: 1 or 2 (see the Makefile)"
 #endif
 #include "star_march.h"
+#include "paired_functor.h"
 #include "../../include/cp_pre_pair.h"
 
 namespace {
-
-template <class Fn>
-struct Paired {
-    static constexpr int F = 2 * Fn::F;
-    static_assert(F <= MAXF, "a paired functor must fit the march's field views");
-    // (no cap: the paired NS momentum in the Nt-fastest relabelling, the heaviest, needs more than the 128 VGPRs its
-    // single-set twin is capped at, and spilling in the plane loop cost 30 % once - NSMomentum)
-    static constexpr int MIN_WAVES = 1;
-    static constexpr unsigned XMASK = XMask<Fn>::value | (XMask<Fn>::value << Fn::F);
-    using Params = typename Fn::Params;
-    static __device__ __forceinline__ float4 eval(const Nbr (&n)[F], const Params &p)
-    {
-        // each half rounded to fp32 before the difference, as numpy subtracts the two residual arrays
-        const float4 a = Fn::eval(*reinterpret_cast<const Nbr(*)[Fn::F]>(&n[0]), p);
-        const float4 b = Fn::eval(*reinterpret_cast<const Nbr(*)[Fn::F]>(&n[Fn::F]), p);
-        return a - b;
-    }
-};
 
 // launch_mode without the general-star instantiation where the paired functor does not fit the registers: the general-star
 // Paired<NSMomentum<2>> and Paired<MHDContinuity<2>> need more than the 256 VGPRs a 512-thread workgroup leaves a wave and
@@ -51,8 +35,6 @@ int launch_pair_mode(int mode, Geom &g, const P &prm, hipStream_t st)
     return PRE_E_UNSUPPORTED;
 }
 
-template <int M> using PairedNS = Paired<NSMomentum<M>>;
-template <int M> using PairedMHDContinuity = Paired<MHDContinuity<M>>;
 template <int M> using PairedBurgers = Paired<Burgers<M>>;
 
 // ---- the <= 3 columns of an odd-width contiguous axis the march leaves (the twin's generic tail) -----------------------

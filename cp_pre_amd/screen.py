@@ -20,8 +20,9 @@ Fused kinds: ``stencil3d`` (a ``ConvOperator`` of ``convops_2d``, ``PRE_Wave``),
 ``ns_momentum``, ``mhd_continuity`` / ``mhd_momentum`` / ``mhd_energy`` / ``mhd_induction`` and, opt-in, ``jorek_continuity``
 / ``jorek_temperature`` (below).  Everything else takes that three-pass route (residual, ``ncf_metric_joint``, then
 ``CoverageLevels`` once per sample) and returns the same ``Screened``: views without unit stride on their last axis, row
-widths that are no multiple of 4, inputs on the CPU (staged as elsewhere), ``minus=``, operator kernels off the 7-point
-star or requiring grad, ``fused=False``, float64 levels or modulation.  ``last_route()`` says which route the last call took.
+widths that are no multiple of 4, inputs on the CPU (staged as elsewhere), ``minus=`` (unless ``pair=True``, below),
+operator kernels off the 7-point star or requiring grad, ``fused=False``, float64 levels or modulation.  ``last_route()``
+says which route the last call took.
 
 The 1-D family on ``[BS,Nt,Nx]`` (a ``ConvOperator`` of ``convops_1d``, ``Advection.residual``, ``Burgers.residual``) has a
 fused route of its own (``libcp_pre_screen1d.so``, ``include/cp_pre_screen1d.h``): the march above would run over the
@@ -45,6 +46,28 @@ its ``unstack_fields`` views ``[BS,Nt,Nx,Ny]``: the dense tensor the script hold
 evaluated with ``norms=False`` (``norms=True`` of the continuity equation cannot be reached through a bound method);
 ``halo_x`` raises, as for every method whose residual pass reads no halo.  Without the keyword JOREK keeps the three-pass
 route (``fallback:no fused screen for JOREK``) and the library is never loaded.
+
+The data-driven score ``d = r(vars) - r(minus)`` - what every ``Joint/`` script calibrates on first and then validates on
+held-out pairs (``Joint/NS_Residuals_CP.py:289-290, 307-313``, the same lines of ``Joint/MHD_Residuals_CP.py``,
+``Joint/Burgers_Residuals_CP.py:217-220``; ``Other_UQ/Evaluation/Eval.py:278-281``) - is screened in one launch only where
+the caller asks for it: ``screen(..., minus=pred, pair=True)`` / ``Screen.add_slab(..., minus=, pair=True)``
+(``libcp_pre_screenpair.so``, ``include/cp_pre_screenpair.h``: both marches above with the paired functor of
+``libcp_pre_pair.so``).  Routes ``fused:pair_<kind>`` (Ny-fastest sets) and ``fused:flat_pair_<kind>`` (Nt-fastest sets) for
+the kinds ``stencil3d``, ``linear2``, ``ns_momentum`` and ``mhd_continuity``; both sets must be on the device and in the same
+layout, and each must meet the layout conditions above (a reason of the second set is reported as ``minus: <reason>``).
+Everything else keeps the three-pass route and says why: ``no paired screen for <kind>`` (the other three MHD equations,
+JOREK), ``no paired screen for the 1-D family``, ``field sets in different layouts``, and the reasons above.  Under
+``halo_x`` both sets must be Ny-contiguous device views with rows -1 and X in memory.  Without ``pair=True`` a ``minus=``
+call takes ``fallback:minus=`` as before and the library is never loaded; ``pair=True`` without ``minus`` has no effect.
+What is computed is the three-pass route's answer: ``d = fl(fl(r(vars)) - fl(r(minus)))``, ``score = max |d| / m``,
+``inside = #{|d| <= fl(q_k * m)}`` - the one-sided test on the difference, NOT the reference's two-sided form
+``c - hw <= y <= c + hw`` on the two residual arrays; the two can differ in a cell that sits within rounding of the band.
+``minus`` may be ``vars`` itself: every score is then exactly 0 and every counted cell inside wherever ``q_k * m >= 0``.
+
+Per-cell (marginal) sets at ONE level - ``Other_UQ/Evaluation/Eval.py:286-288`` and the ``Marginal/`` validation at a fixed
+alpha, where the calibration left a quantile per cell - need no entry of their own: pass the per-cell quantiles as the
+modulation and one level of 1, ``screen(method, vars, torch.ones(1), modulation=qhat_cells, [minus=pred, pair=True])``.
+``1.0f * m == m`` exactly, so ``inside[0]`` counts ``|d| <= qhat_cells`` exactly (``emp_cov_levels``'s count per sample).
 
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
@@ -114,11 +137,12 @@ class Screened:
 
 
 # ------------------------------------------------------------------------------------------- what a method is
-def _input_declined(x, minus, qhats, modulation):
-    """What keeps a call from every fused screen, whatever the method and the layout, or None."""
-    if minus is not None:
+def _input_declined(x, minus, qhats, modulation, pair=False):
+    """What keeps a call from every fused screen, whatever the method and the layout, or None.  ``pair``: the caller asked
+    for the paired screens, which take ``minus``."""
+    if minus is not None and not pair:
         return "minus="
-    if not x.is_cuda:
+    if not x.is_cuda or (minus is not None and not minus.is_cuda):
         return "input on the CPU"
     if qhats.dtype != torch.float32 or (modulation is not None and modulation.dtype != torch.float32):
         return "float64 levels or modulation"
@@ -133,6 +157,9 @@ _MHD_EQ = {"mhd_" + e: i for i, e in enumerate(MHD_EQ)}
 # the two JOREK kinds (opt-in) share the two entry points of a library of their own: kind -> ``eq``; form -> entry point
 _JOREK_EQ = {"jorek_continuity": 0, "jorek_temperature": 1}
 _JOREK_ENTRY = {"": "pre_screenjorek_f32", "flat": "pre_screenjorek_flat_f32"}
+# the kinds with a paired screen (opt-in, ``pair=True`` with ``minus=``), a library of their own: form -> prefix of its entries
+_PAIR_KINDS = ("stencil3d", "linear2", "ns_momentum", "mhd_continuity")
+_PAIR_ENTRY = {"": "pre_screenpair_", "flat": "pre_screenpair_flat_"}
 
 
 class _Spec(Method):
@@ -196,28 +223,46 @@ class _Spec(Method):
             return self.method(x, boundary=True, **kw)
 
     # -------- can a fused screen run?  input, then layout, then what declines whatever the layout, then the kernels
-    def _prepare(self, layout, kind, points, x, minus, qhats, modulation):
-        why = _input_declined(x, minus, qhats, modulation) or layout(self.view(x)) or self.declined(x)
-        if why is None and kind in _MHD_EQ and x.shape[1] < 6:
+    def pair_declined(self):
+        """What keeps this method from the paired screens (``pair=True`` with ``minus=``) whatever the input, or None."""
+        if self.rows_kind is not None:
+            return "no paired screen for the 1-D family"
+        if self.kind is None:
+            return self.why
+        return None if self.kind in _PAIR_KINDS else "no paired screen for " + self.kind
+
+    def _prepare(self, layout, kind, points, x, minus, qhats, modulation, pair=False):
+        pair = pair and minus is not None
+        why = (self.pair_declined() if pair else None) or _input_declined(x, minus, qhats, modulation, pair) or layout(self.view(x))
+        if why is None and pair:
+            # the second set: in the other layout no march takes the two together; in the same one, its own reasons
+            if self.nt_fastest(minus) != self.nt_fastest(x):
+                why = "field sets in different layouts"
+            else:
+                why = layout(self.view(minus))
+                why = why and "minus: " + why
+        why = why or self.declined(x)
+        if why is None and not pair and kind in _MHD_EQ and x.shape[1] < 6:
             why = "fewer than six MHD channels"                  # (pre_screen_mhd_f32 takes the six views)
         if why is None and kind in _JOREK_EQ and x.shape[1] != 3:
             why = "not three JOREK channels"                     # (the residual methods unstack exactly rho, phi, T)
         return (why, ()) if why is not None else self.star_kernels(kind, points)
 
-    def prepare(self, x, minus, qhats, modulation):
+    def prepare(self, x, minus, qhats, modulation, pair=False):
         """(why, kernels): ``why`` is None if the fused screen can run; host checks and one download of the operator
-        kernels (``_dispatch.host_kernel`` on every call: a screen applies the kernels its operators hold now)."""
+        kernels (``_dispatch.host_kernel`` on every call: a screen applies the kernels its operators hold now).  ``pair``
+        with a ``minus``: the same question of the paired screen, of both sets."""
         if self.kind is None:
-            return self.why, ()
-        return self._prepare(self._layout, self.kind, 7, x, minus, qhats, modulation)
+            return (pair and minus is not None and self.pair_declined()) or self.why, ()
+        return self._prepare(self._layout, self.kind, 7, x, minus, qhats, modulation, pair)
 
-    def prepare_flat(self, x, minus, qhats, modulation):
+    def prepare_flat(self, x, minus, qhats, modulation, pair=False):
         """``prepare`` for the fused screen of Nt-fastest views (``nt_fastest(x)``): (why, kernels)."""
-        return self._prepare(self._layout_flat, self.kind, 7, x, minus, qhats, modulation)
+        return self._prepare(self._layout_flat, self.kind, 7, x, minus, qhats, modulation, pair)
 
-    def prepare_rows(self, x, minus, qhats, modulation):
+    def prepare_rows(self, x, minus, qhats, modulation, pair=False):
         """``prepare`` for the fused screen of the 1-D family (``rows_kind``): (why, kernels)."""
-        return self._prepare(self._layout_rows, self.rows_kind, 5, x, minus, qhats, modulation)
+        return self._prepare(self._layout_rows, self.rows_kind, 5, x, minus, qhats, modulation, pair)
 
     @staticmethod
     def _layout(x):
@@ -254,19 +299,30 @@ class _Spec(Method):
         return None
 
     # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
-    def entry(self, form):
-        """The entry point of this method's fused screen in the library of ``form``."""
+    def entry(self, form, pair=False):
+        """The entry point of this method's fused screen in the library of ``form`` (``pair``: of its paired screen)."""
+        if pair:
+            return _PAIR_ENTRY[form] + self.kind + "_f32"
         if self.kind in _JOREK_EQ and form != "rows":
             return _JOREK_ENTRY[form]
         kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
         return _FORMS[form][1] + kind + "_f32"
 
-    def route(self, form):
-        return "fused:" + _FORMS[form][2] + (self.rows_kind if form == "rows" else self.kind)
+    def route(self, form, pair=False):
+        return "fused:" + _FORMS[form][2] + ("pair_" if pair else "") + (self.rows_kind if form == "rows" else self.kind)
 
-    def launch(self, kernels, x, st, flags, form=""):
-        """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code."""
+    def launch(self, kernels, x, st, flags, form="", minus=None):
+        """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code.
+        ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so``; forms '' and 'flat')."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
+        if minus is not None:
+            fa, fb = self.fields(x), self.fields(minus)
+            one = self.kind.startswith("stencil")                # (one view per set; else a pre_field_t[F] per set)
+            views = [ctypes.byref(_lib.field(f[0])) if one else R._arr(f) for f in (fa, fb)]
+            if one:
+                kernels = _dispatch.tap_args(*kernels)
+            fn = getattr(_lib.load_screenpair(), self.entry(form, True))
+            return fn(*views, *kernels, *self.scalars(), ctypes.byref(st), *fa[0].shape, flags, _lib.stream())
         kind = self.rows_kind if form == "rows" else self.kind
         lib = getattr(_lib, "load_screenjorek" if kind in _JOREK_EQ else _FORMS[form][0])()
         if form == "rows":
@@ -361,19 +417,25 @@ class Screen:
             self.acc = torch.zeros(self.nk + 1, self.n_local, dtype=torch.int32, device=device)
         return self.acc
 
-    def add_slab(self, method, vars_slab, qhats, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None, jorek=False):
+    def add_slab(self, method, vars_slab, qhats, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None, jorek=False,
+                 pair=False):
         """``vars_slab``: the method's input on a slab of the grid (all local samples); ``modulation_slab`` [T,X,Y] of the
         slab's uncropped residual extents, or None (m == 1); ``crop`` cells per side of each residual axis are left out
         (``JointCalibration.add_slab``'s meaning); ``halo_x``: the slab's rows -1 and X lie in the same memory; ``jorek``: the
-        opt-in fused screen of the JOREK residuals (``_Spec``; a method given as a ``_Spec`` has decided already)."""
+        opt-in fused screen of the JOREK residuals (``_Spec``; a method given as a ``_Spec`` has decided already); ``pair``:
+        the opt-in paired screen of ``vars_slab`` and ``minus`` (no effect without ``minus``; under ``halo_x`` both sets
+        must be Ny-contiguous device views with rows -1 and X in memory)."""
         global _last_route
         spec = method if isinstance(method, _Spec) else _Spec(method, jorek)
+        pair = bool(pair) and minus is not None
         shape, crop, cells = _check_inputs(spec, vars_slab, qhats, modulation_slab, minus, crop, self.nk)
         if shape[0] != self.n_local:
             raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
         if _dev_key(vars_slab.device) != _dev_key(self.device):
             raise ValueError(f"slab on {vars_slab.device}, this Screen was made for {self.device}")
-        why, kernels = spec.prepare(vars_slab, minus, qhats, modulation_slab)
+        if halo_x and pair and vars_slab.is_cuda:
+            R._check_minus(vars_slab, minus, device_view=True)
+        why, kernels = spec.prepare(vars_slab, minus, qhats, modulation_slab, pair)
         if halo_x and spec.kind in _JOREK_EQ:
             why = why or "halo_x"                                 # (no pass of the JOREK residuals reads halo rows: raises below)
         if halo_x and not vars_slab.is_cuda:
@@ -383,11 +445,11 @@ class Screen:
             raise RuntimeError(f"halo_x: the fused screen cannot run ({why}) and no other pass of this method reads the halo rows")
         rows = spec.rows_kind is not None                     # (the 1-D family: halo_x has raised above)
         if rows:
-            why, kernels = spec.prepare_rows(vars_slab, minus, qhats, modulation_slab)
+            why, kernels = spec.prepare_rows(vars_slab, minus, qhats, modulation_slab, pair)
         # Nt-fastest views of the 2-D residuals: the flat route (halo_x keeps the behaviour it had: the flat form pads x)
         flat = not rows and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
         if flat:
-            why, kernels = spec.prepare_flat(vars_slab, minus, qhats, modulation_slab)
+            why, kernels = spec.prepare_flat(vars_slab, minus, qhats, modulation_slab, pair)
         if why is None:
             acc = self._buffers(vars_slab.device)
             mod = modulation_slab
@@ -411,14 +473,15 @@ class Screen:
                                     ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
             form = "rows" if rows else "flat" if flat else ""
             with torch.no_grad(), torch.cuda.device(vars_slab.device):
-                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x and form == "" else 0, form)
+                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x and form == "" else 0, form,
+                                 minus if pair else None)
             if rc == _lib.PRE_E_UNSUPPORTED:
                 why = "declined by the library"
                 if halo_x and not spec.reads_halo():
                     raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
             else:
-                _lib.check(rc, spec.entry(form))
-                _last_route = spec.route(form)
+                _lib.check(rc, spec.entry(form, pair))
+                _last_route = spec.route(form, pair)
                 self.cells += cells
                 return
         _last_route = "fallback:" + why
@@ -473,17 +536,19 @@ class Screen:
         return Screened(self.acc[0].view(torch.float32).clone(), self.acc[1:].to(torch.int64) & 0xffffffff, self.cells)
 
 
-def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=None, jorek=False):
+def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=None, jorek=False, pair=False):
     """Screen the predictions ``vars`` against the sets ``|r| <= qhats[k] * modulation``.  ``boundary=False``: the counted
     cells are the interior ``[1:-1]`` of every residual axis, as the reference crops its residuals (``modulation`` keeps
     the uncropped extents: its rim is never used); ``boundary=True``: every cell.  ``jorek=True``: the opt-in fused screen
     of ``JOREK.residual_continuity`` / ``residual_temperature`` (``vars`` [BS,F,Nx,Ny,Nt], ``modulation`` [Nt,Nx,Ny]; the
-    equations with ``norms=False``).  Returns a :class:`Screened`."""
+    equations with ``norms=False``).  ``minus``: the data-driven score, ``d = r(vars) - r(minus)`` in place of the residual;
+    ``pair=True`` with it: the opt-in paired screen (one launch over both sets; module docstring); without ``minus`` the
+    keyword has no effect.  Returns a :class:`Screened`."""
     spec = _Spec(residual_method, jorek)
     crop = (0,) * spec.nd if boundary else (1,) * spec.nd
     shape, _, _ = _check_inputs(spec, vars, qhats, modulation, minus, crop)
     s = Screen(shape[0], qhats.shape[0], vars.device)
-    s.add_slab(spec, vars, qhats, modulation, crop=crop, minus=minus)
+    s.add_slab(spec, vars, qhats, modulation, crop=crop, minus=minus, pair=pair)
     out = s.finish()
     if not vars.is_cuda:                                     # (staged inputs: the verdicts come home, as elsewhere)
         out.score, out.inside = out.score.to(vars.device), out.inside.to(vars.device)

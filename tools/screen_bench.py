@@ -28,6 +28,18 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                ``pre_residual_jorek_f32``).  The JOREK residual pass takes no ``out=``: (B) and (R) allocate their residual from
                torch's caching allocator on every call, as for Burgers; (R) is ``pre_residual_jorek_f32`` on the same views
 
+    c3_pair_xslab / c3_pair_ntfast / c4_continuity_pair / c2_wave_pair
+               the paired screen of the data-driven score r(a) - r(b) (``minus=``, ``pair=True``: ``libcp_pre_screenpair.so``) on
+               two field sets: NS momentum on the x-slab geometry of tools/paired_bench.py, [2048,3,64,32(+2 halo rows),512]
+               twice with halo_x (half its batch: both sets, the residual buffer of the replaced routes and their scores fit
+               with room to spare); NS momentum on memory [256,3,512,512,64] twice, Nt-fastest; MHD continuity on
+               [512,3,64,256,256] twice (the three channels it reads); the wave residual on [512,32,256,256] twice.  Four
+               routes, alternated call by call: (A) the fused launch; (P) the route it replaces as the package runs it without
+               ``pair=True`` - paired residual pass, ``ncf_metric_joint``, ``CoverageLevels`` once PER SAMPLE; (B) the best a
+               user composes for score and accept only - paired pass into a buffer, the joint score pass, ONE joint
+               ``CoverageLevels`` pass (``filter_sims_joint_levels``); (R) the paired residual pass alone, which moves 4 B/cell
+               more than (A).  Lines go to profiles/screenpair/screen_bench_pair.jsonl unless --out says otherwise
+
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
@@ -120,6 +132,113 @@ def case(name, div, dev):
     raise KeyError(name)
 
 
+PAIR_CASES = ("c3_pair_xslab", "c3_pair_ntfast", "c4_continuity_pair", "c2_wave_pair")
+HBM_TBPS = 8.0               # the MI355X's nominal HBM bandwidth: what the fractions below are fractions of
+
+
+def pair_case(name, div, dev):
+    """(method, truth view, prediction view, crop, halo_x, paired residual call into out=, fields per set)"""
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def rnd(*s):
+        return torch.rand(*s, device=dev, generator=g) + 0.5
+    if name == "c3_pair_xslab":
+        ns = R.NavierStokes(0.01, 1 / 512, 1 / 512, device=dev)
+        a, b = (rnd(max(2048 // div, 1), 3, 64, 34, 512)[:, :, :, 1:-1] for _ in range(2))
+        return (ns.residual_momentum, a, b, (1, 0, 1), True,
+                lambda out: ns.residual_momentum(a, boundary=True, out=out, halo_x=True, minus=b), 3)
+    if name == "c3_pair_ntfast":
+        ns = R.NavierStokes(0.01, 1 / 512, 1 / 512, device=dev)
+        a, b = (rnd(max(256 // div, 1), 3, 512, 512, 64).permute(0, 1, 4, 2, 3) for _ in range(2))
+        return ns.residual_momentum, a, b, (1, 1, 1), False, lambda out: ns.residual_momentum(a, boundary=True, out=out, minus=b), 3
+    if name == "c4_continuity_pair":
+        mhd = R.MHD(device=dev)
+        a, b = (rnd(max(512 // div, 1), 3, 64, 256, 256) for _ in range(2))
+        return mhd.residual_continuity, a, b, (1, 1, 1), False, lambda out: mhd.residual_continuity(a, boundary=True, out=out, minus=b), 3
+    if name == "c2_wave_pair":
+        w = R.PRE_Wave(0.01, 0.02, device=dev)
+        a, b = (rnd(max(512 // div, 1), 32, 256, 256) for _ in range(2))
+        return w.residual, a, b, (1, 1, 1), False, lambda out: w.residual(a, boundary=True, out=out, minus=b), 1
+    raise KeyError(name)
+
+
+def run_pair(name, args, dev):
+    """One paired case: the four routes alternated, one JSON line."""
+    method, a, b, crop, halo_x, paired_into, F = pair_case(name, args.div, dev)
+    n = a.shape[0]
+    nt_fast = a.stride(-1) != 1
+    shape = (n,) + tuple(a.shape[-3:])
+    mod = torch.rand(shape[1:], device=dev) + 0.5
+    q = torch.ones(NK, device=dev)                       # (replaced below by levels that split the samples)
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    if nt_fast:
+        mod = mod.permute(1, 2, 0).contiguous().permute(2, 0, 1)
+        out = torch.empty((n,) + shape[2:] + shape[1:2], dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+    reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
+
+    def fused():
+        s = screen.Screen(n, NK, dev)
+        s.add_slab(method, a, q, mod, crop=crop, halo_x=halo_x, minus=b, pair=True)
+        return s
+
+    def parent():
+        s = screen.Screen(n, NK, dev)
+        s.add_slab(method, a, q, mod, crop=crop, halo_x=halo_x, minus=b)
+        return s
+
+    def composed():
+        paired_into(out)
+        if nt_fast:
+            scores = icp.ncf_metric_joint(out, None, mod, crop=1)
+        else:
+            scores = torch.zeros(n, dtype=torch.float32, device=dev)
+            pipeline.HipOps.max_scores(out, mod, crop, scores)
+        cov = pipeline.CoverageLevels(n, NK, dev, joint=True)
+        cov.add_slab(out[reg], q, modulation=mod[reg[1:]])
+        return scores, cov
+
+    def residual():
+        paired_into(out)
+
+    # the levels: quantiles of the samples' own scores, so that every level accepts some samples and rejects others and
+    # the equalities recorded below compare verdicts that differ from sample to sample
+    sc0 = fused().finish().score
+    q = torch.quantile(sc0, torch.linspace(0.05, 0.95, NK, device=dev)).contiguous()
+    s = fused()
+    route = screen.last_route()
+    p = parent()
+    proute = screen.last_route()
+    sc, cov = composed()
+    torch.cuda.synchronize()
+    got, old = s.finish(), p.finish()
+    line = {"case": name, "shape": list(a.shape), "sets": 2, "nk": NK, "route": route, "replaced_route": proute,
+            "bit_identical_to_replaced_route": bool(torch.equal(got.inside, old.inside)) and
+            bool(torch.equal(got.score.view(torch.int32), old.score.view(torch.int32))),
+            "accept_equal_to_composed": bool(torch.equal(got.accept(), cov.inside)),
+            "accepted_per_level": [int(v) for v in got.accept().sum(dim=1).cpu()]}
+    fns = {"fused": fused, "parent": parent, "composed": composed, "residual": residual}
+    if args.only is not None and args.only not in fns:
+        raise SystemExit(f"--only {args.only}: the paired cases have the routes {', '.join(fns)}")
+    pick = [args.only] if args.only else list(fns)
+    res = blocks_of([fns[k] for k in pick], args.reps, args.blocks, args.warmup)
+    cells = 1
+    for d in shape:
+        cells *= d
+    # bytes per cell each route must move: the fields of both sets; + the stored difference; + its two further reads
+    bpc = {"fused": 8 * F, "residual": 8 * F + 4, "composed": 8 * F + 12, "parent": 8 * F + 12}
+    line["cells"] = cells
+    for k, (med, lo, hi) in zip(pick, res):
+        line[k + "_ms"] = round(med, 4)
+        line[k + "_ms_min_max"] = [round(lo, 4), round(hi, 4)]
+        line[k + "_B_per_cell"] = bpc[k]
+        line[k + "_fraction_of_8TBps"] = round(cells * bpc[k] / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+    if "fused" in pick:
+        for k in ("parent", "composed", "residual"):
+            if k in pick:
+                line["fused_over_" + k] = round(line["fused_ms"] / line[k + "_ms"], 4)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
@@ -127,12 +246,23 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--only", choices=["fused", "three", "residual"], default=None, help="run one route alone (for a profiler)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "screen", "screen_bench.jsonl"))
+    ap.add_argument("--only", choices=["fused", "three", "residual", "parent", "composed"], default=None,
+                    help="run one route alone (for a profiler)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
     for name in args.cases.split(","):
+        pair = name in PAIR_CASES
+        path = args.out or os.path.join(ROOT, "profiles", "screenpair" if pair else "screen",
+                                        "screen_bench_pair.jsonl" if pair else "screen_bench.jsonl")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        if pair:
+            txt = json.dumps(run_pair(name, args, dev))
+            print(txt, flush=True)
+            with open(path, "a") as f:
+                f.write(txt + "\n")
+            torch.cuda.empty_cache()
+            continue
         method, v, crop, halo_x, residual_into, fbytes = case(name, args.div, dev)
         n = v.shape[0]
         one_d = len(crop) == 2
@@ -204,7 +334,7 @@ def main():
             line["fused_over_three"] = round(line["fused_ms"] / line["three_ms"], 4)
         txt = json.dumps(line)
         print(txt, flush=True)
-        with open(args.out, "a") as f:
+        with open(path, "a") as f:
             f.write(txt + "\n")
         del v, out, mod
         torch.cuda.empty_cache()
