@@ -324,6 +324,17 @@ for _form, _tail in (("", _scr), ("flat_", _scrf)):
         "pre_screenpair_%smhd_continuity_f32" % _form: _arr2 + [POINTER(c_float)] * 3 + [c_double] + _tail,
     })
 
+# libcp_pre_screen1dpair.so (include/cp_pre_screen1dpair.h): the 1-D screen for the data-driven scores r(a) - r(b): each entry
+# takes its single-set twin's arguments with the two field sets (pointer, strides each) in place of the twin's field
+SCREEN1DPAIR_SO_PATH = os.path.join(_HERE, "libcp_pre_screen1dpair.so")
+PRE_SCREEN1DPAIR_ABI_VERSION = 1
+_sets1 = [_fp, _i64p, _fp, _i64p]                                       # a, strides_a, b, strides_b
+SCREEN1DPAIR_SIGNATURES = {
+    "pre_screen1dpair_abi_version": [],
+    "pre_screen1dpair_stencil2d_f32": _sets1 + SCREEN1D_SIGNATURES["pre_screen1d_stencil2d_f32"][2:],
+    "pre_screen1dpair_burgers_f32": _sets1 + SCREEN1D_SIGNATURES["pre_screen1d_burgers_f32"][2:],
+}
+
 # libcp_pre_vjpflatmhd.so (include/cp_pre_vjpflatmhd.h): the entries of libcp_pre_vjpmhd.so for Nt-fastest views (the march of
 # libcp_pre_vjpflat.so), argument for argument
 VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
@@ -372,8 +383,9 @@ _LIBS_MORE = {
     "vjpflatmhd": ("_vjpflatmhd", "VJPFLATMHD_", "pre_vjpflatmhd_abi_version", "PRE_VJPFLATMHD_ABI_VERSION", ()),
     "vjpjorek": ("_vjpjorek", "VJPJOREK_", "pre_vjpjorek_abi_version", "PRE_VJPJOREK_ABI_VERSION", ()),
     "screenpair": ("_screenpair", "SCREENPAIR_", "pre_screenpair_abi_version", "PRE_SCREENPAIR_ABI_VERSION", ()),
+    "screen1dpair": ("_screen1dpair", "SCREEN1DPAIR_", "pre_screen1dpair_abi_version", "PRE_SCREEN1DPAIR_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -486,6 +498,10 @@ def load_vjpjorek():
 
 def load_screenpair():
     return _screenpair or _load("screenpair")
+
+
+def load_screen1dpair():
+    return _screen1dpair or _load("screen1dpair")
 
 
 def require_gpu():

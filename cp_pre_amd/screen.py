@@ -56,13 +56,24 @@ the caller asks for it: ``screen(..., minus=pred, pair=True)`` / ``Screen.add_sl
 the kinds ``stencil3d``, ``linear2``, ``ns_momentum`` and ``mhd_continuity``; both sets must be on the device and in the same
 layout, and each must meet the layout conditions above (a reason of the second set is reported as ``minus: <reason>``).
 Everything else keeps the three-pass route and says why: ``no paired screen for <kind>`` (the other three MHD equations,
-JOREK), ``no paired screen for the 1-D family``, ``field sets in different layouts``, and the reasons above.  Under
+JOREK), ``no paired screen for the 1-D family`` (under ``pair=True``; below), ``field sets in different layouts``, and the reasons above.  Under
 ``halo_x`` both sets must be Ny-contiguous device views with rows -1 and X in memory.  Without ``pair=True`` a ``minus=``
 call takes ``fallback:minus=`` as before and the library is never loaded; ``pair=True`` without ``minus`` has no effect.
 What is computed is the three-pass route's answer: ``d = fl(fl(r(vars)) - fl(r(minus)))``, ``score = max |d| / m``,
 ``inside = #{|d| <= fl(q_k * m)}`` - the one-sided test on the difference, NOT the reference's two-sided form
 ``c - hw <= y <= c + hw`` on the two residual arrays; the two can differ in a cell that sits within rounding of the band.
 ``minus`` may be ``vars`` itself: every score is then exactly 0 and every counted cell inside wherever ``q_k * m >= 0``.
+
+The 1-D family has a paired screen as well, asked for by ``pair="rows"`` (``Joint/Burgers_Residuals_CP.py:217-220, 250-259``,
+``Joint/Advection_Residuals_CP.py`` and the ``Active_Learning/*_AL_Joint.py`` loops; ``libcp_pre_screen1dpair.so``,
+``include/cp_pre_screen1dpair.h``: the row march of the rows route on two field sets, with the same paired functor).
+``pair="rows"`` does everything ``pair=True`` does and, for ``rows_kind`` ``stencil2d`` and ``burgers``, takes routes
+``fused:rows_pair_stencil2d`` / ``fused:rows_pair_burgers`` - as ``mhd="flat"`` stands next to ``mhd=True`` in ``losses``.
+Both sets must be on the device with their unit stride on the same axis (Nx-fastest, or the Nt-fastest
+``u.permute(0,1,3,2)[:,0]``; else ``field sets in different layouts``), each with its own sample and row pitch; the reasons of
+the rows route above apply to both (``minus: <reason>`` for the second), the modulation is relabelled or copied as there, and
+``halo_x`` raises.  The semantics are those of the paragraph above.  ``pair=True`` keeps ``no paired screen for the 1-D
+family``, any other value of ``pair`` keeps its truthiness, and without ``pair="rows"`` the library is never loaded.
 
 Per-cell (marginal) sets at ONE level - ``Other_UQ/Evaluation/Eval.py:286-288`` and the ``Marginal/`` validation at a fixed
 alpha, where the calibration left a quantile per cell - need no entry of their own: pass the per-cell quantiles as the
@@ -160,6 +171,16 @@ _JOREK_ENTRY = {"": "pre_screenjorek_f32", "flat": "pre_screenjorek_flat_f32"}
 # the kinds with a paired screen (opt-in, ``pair=True`` with ``minus=``), a library of their own: form -> prefix of its entries
 _PAIR_KINDS = ("stencil3d", "linear2", "ns_momentum", "mhd_continuity")
 _PAIR_ENTRY = {"": "pre_screenpair_", "flat": "pre_screenpair_flat_"}
+# the paired screen of the 1-D family (opt-in, ``pair="rows"`` with ``minus=``), one more library: the prefix of its entries
+_PAIR_ROWS_ENTRY = "pre_screen1dpair_"
+
+
+def _pair_mode(pair, minus):
+    """``pair`` as the host side carries it: False without ``minus``, "rows" for ``pair="rows"`` (the paired screens and,
+    for the 1-D family, the paired rows screen), else its truthiness."""
+    if minus is None:
+        return False
+    return "rows" if isinstance(pair, str) and pair == "rows" else bool(pair)
 
 
 class _Spec(Method):
@@ -223,20 +244,22 @@ class _Spec(Method):
             return self.method(x, boundary=True, **kw)
 
     # -------- can a fused screen run?  input, then layout, then what declines whatever the layout, then the kernels
-    def pair_declined(self):
-        """What keeps this method from the paired screens (``pair=True`` with ``minus=``) whatever the input, or None."""
+    def pair_declined(self, rows=False):
+        """What keeps this method from the paired screens (``pair=True`` with ``minus=``) whatever the input, or None.
+        ``rows``: the caller asked with ``pair="rows"``, which the 1-D family takes."""
         if self.rows_kind is not None:
-            return "no paired screen for the 1-D family"
+            return None if rows else "no paired screen for the 1-D family"
         if self.kind is None:
             return self.why
         return None if self.kind in _PAIR_KINDS else "no paired screen for " + self.kind
 
     def _prepare(self, layout, kind, points, x, minus, qhats, modulation, pair=False):
-        pair = pair and minus is not None
-        why = (self.pair_declined() if pair else None) or _input_declined(x, minus, qhats, modulation, pair) or layout(self.view(x))
+        pair = _pair_mode(pair, minus)
+        why = (self.pair_declined(pair == "rows") if pair else None) or _input_declined(x, minus, qhats, modulation, pair) or \
+            layout(self.view(x))
         if why is None and pair:
             # the second set: in the other layout no march takes the two together; in the same one, its own reasons
-            if self.nt_fastest(minus) != self.nt_fastest(x):
+            if self._other_layout(x, minus) if layout is self._layout_rows else self.nt_fastest(minus) != self.nt_fastest(x):
                 why = "field sets in different layouts"
             else:
                 why = layout(self.view(minus))
@@ -253,7 +276,8 @@ class _Spec(Method):
         kernels (``_dispatch.host_kernel`` on every call: a screen applies the kernels its operators hold now).  ``pair``
         with a ``minus``: the same question of the paired screen, of both sets."""
         if self.kind is None:
-            return (pair and minus is not None and self.pair_declined()) or self.why, ()
+            pair = _pair_mode(pair, minus)
+            return (pair and self.pair_declined(pair == "rows")) or self.why, ()
         return self._prepare(self._layout, self.kind, 7, x, minus, qhats, modulation, pair)
 
     def prepare_flat(self, x, minus, qhats, modulation, pair=False):
@@ -298,11 +322,18 @@ class _Spec(Method):
             return "contiguous-axis length not a multiple of 4"
         return None
 
+    @staticmethod
+    def _other_layout(x, minus):
+        """Of two [BS,Nt,Nx] sets of the 1-D family, ``x`` past ``_layout_rows``: does ``minus`` have its unit stride on the
+        other axis only?  (No unit-stride axis at all is a reason of its own, ``_layout_rows``'s.)"""
+        ax = 2 if x.stride(2) == 1 else 1
+        return minus.dim() == 3 and minus.stride(ax) != 1 and minus.stride(3 - ax) == 1
+
     # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
     def entry(self, form, pair=False):
         """The entry point of this method's fused screen in the library of ``form`` (``pair``: of its paired screen)."""
         if pair:
-            return _PAIR_ENTRY[form] + self.kind + "_f32"
+            return _PAIR_ROWS_ENTRY + self.rows_kind + "_f32" if form == "rows" else _PAIR_ENTRY[form] + self.kind + "_f32"
         if self.kind in _JOREK_EQ and form != "rows":
             return _JOREK_ENTRY[form]
         kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
@@ -313,8 +344,15 @@ class _Spec(Method):
 
     def launch(self, kernels, x, st, flags, form="", minus=None):
         """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code.
-        ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so``; forms '' and 'flat')."""
+        ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so`` for forms '' and 'flat',
+        ``libcp_pre_screen1dpair.so`` for 'rows')."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
+        if minus is not None and form == "rows":
+            sets = (_lib.ptr(x), _lib.iarr64(x.stride()), _lib.ptr(minus), _lib.iarr64(minus.stride()))
+            if self.rows_kind.startswith("stencil"):
+                kernels = _dispatch.tap_args(*kernels)
+            fn = getattr(_lib.load_screen1dpair(), self.entry(form, True))
+            return fn(*sets, *kernels, *self.scalars(), ctypes.byref(st), *x.shape, flags, _lib.stream())
         if minus is not None:
             fa, fb = self.fields(x), self.fields(minus)
             one = self.kind.startswith("stencil")                # (one view per set; else a pre_field_t[F] per set)
@@ -424,10 +462,11 @@ class Screen:
         (``JointCalibration.add_slab``'s meaning); ``halo_x``: the slab's rows -1 and X lie in the same memory; ``jorek``: the
         opt-in fused screen of the JOREK residuals (``_Spec``; a method given as a ``_Spec`` has decided already); ``pair``:
         the opt-in paired screen of ``vars_slab`` and ``minus`` (no effect without ``minus``; under ``halo_x`` both sets
-        must be Ny-contiguous device views with rows -1 and X in memory)."""
+        must be Ny-contiguous device views with rows -1 and X in memory); ``pair="rows"``: the same, and the paired rows
+        screen for the 1-D family (module docstring)."""
         global _last_route
         spec = method if isinstance(method, _Spec) else _Spec(method, jorek)
-        pair = bool(pair) and minus is not None
+        pair = _pair_mode(pair, minus)
         shape, crop, cells = _check_inputs(spec, vars_slab, qhats, modulation_slab, minus, crop, self.nk)
         if shape[0] != self.n_local:
             raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
@@ -480,8 +519,8 @@ class Screen:
                 if halo_x and not spec.reads_halo():
                     raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
             else:
-                _lib.check(rc, spec.entry(form, pair))
-                _last_route = spec.route(form, pair)
+                _lib.check(rc, spec.entry(form, bool(pair)))
+                _last_route = spec.route(form, bool(pair))
                 self.cells += cells
                 return
         _last_route = "fallback:" + why
@@ -542,8 +581,9 @@ def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=
     the uncropped extents: its rim is never used); ``boundary=True``: every cell.  ``jorek=True``: the opt-in fused screen
     of ``JOREK.residual_continuity`` / ``residual_temperature`` (``vars`` [BS,F,Nx,Ny,Nt], ``modulation`` [Nt,Nx,Ny]; the
     equations with ``norms=False``).  ``minus``: the data-driven score, ``d = r(vars) - r(minus)`` in place of the residual;
-    ``pair=True`` with it: the opt-in paired screen (one launch over both sets; module docstring); without ``minus`` the
-    keyword has no effect.  Returns a :class:`Screened`."""
+    ``pair=True`` with it: the opt-in paired screen (one launch over both sets; module docstring), ``pair="rows"``: the
+    same, and for the 1-D family its paired rows screen; without ``minus`` the keyword has no effect.  Returns a
+    :class:`Screened`."""
     spec = _Spec(residual_method, jorek)
     crop = (0,) * spec.nd if boundary else (1,) * spec.nd
     shape, _, _ = _check_inputs(spec, vars, qhats, modulation, minus, crop)

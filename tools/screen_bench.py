@@ -39,6 +39,14 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                user composes for score and accept only - paired pass into a buffer, the joint score pass, ONE joint
                ``CoverageLevels`` pass (``filter_sims_joint_levels``); (R) the paired residual pass alone, which moves 4 B/cell
                more than (A).  Lines go to profiles/screenpair/screen_bench_pair.jsonl unless --out says otherwise
+    c5_burgers_pair_nx / c5_burgers_pair_nt
+               the paired screen of the 1-D family (``minus=``, ``pair="rows"``: ``libcp_pre_screen1dpair.so``): Burgers on two
+               [4096,200,512] sets, Nx-fastest and in the Nt-fastest layout of the active-learning scripts.  Three routes,
+               alternated call by call: (A) the fused launch; (P) the route the package runs for the same call without
+               ``pair="rows"`` - the paired residual pass on the [1,B,T,X] view into a batch-sized buffer,
+               ``ncf_metric_joint``, ``CoverageLevels`` once PER SAMPLE; (R) the paired residual pass alone (the 1-D pass
+               takes no ``out=``: it allocates its result on every call).  There is no (B): a user composes nothing
+               shorter for per-sample verdicts of this family.  Lines go to profiles/screen1dpair/screen_bench_pair.jsonl
 
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
@@ -132,7 +140,8 @@ def case(name, div, dev):
     raise KeyError(name)
 
 
-PAIR_CASES = ("c3_pair_xslab", "c3_pair_ntfast", "c4_continuity_pair", "c2_wave_pair")
+PAIR1D_CASES = ("c5_burgers_pair_nx", "c5_burgers_pair_nt")
+PAIR_CASES = ("c3_pair_xslab", "c3_pair_ntfast", "c4_continuity_pair", "c2_wave_pair") + PAIR1D_CASES
 HBM_TBPS = 8.0               # the MI355X's nominal HBM bandwidth: what the fractions below are fractions of
 
 
@@ -159,6 +168,12 @@ def pair_case(name, div, dev):
         w = R.PRE_Wave(0.01, 0.02, device=dev)
         a, b = (rnd(max(512 // div, 1), 32, 256, 256) for _ in range(2))
         return w.residual, a, b, (1, 1, 1), False, lambda out: w.residual(a, boundary=True, out=out, minus=b), 1
+    if name in PAIR1D_CASES:
+        bg = R.Burgers(1 / 512, 0.005, 0.002, device=dev)
+        a, b = (rnd(max(4096 // div, 1), 200, 512) for _ in range(2))
+        if name.endswith("nt"):
+            a, b = (v.transpose(1, 2).contiguous().transpose(1, 2) for v in (a, b))
+        return bg.residual, a, b, (1, 1), False, lambda out: bg.residual(a, boundary=True, minus=b), 1
     raise KeyError(name)
 
 
@@ -166,19 +181,22 @@ def run_pair(name, args, dev):
     """One paired case: the four routes alternated, one JSON line."""
     method, a, b, crop, halo_x, paired_into, F = pair_case(name, args.div, dev)
     n = a.shape[0]
+    one_d = name in PAIR1D_CASES
     nt_fast = a.stride(-1) != 1
-    shape = (n,) + tuple(a.shape[-3:])
+    shape = (n,) + tuple(a.shape[-len(crop):])
     mod = torch.rand(shape[1:], device=dev) + 0.5
     q = torch.ones(NK, device=dev)                       # (replaced below by levels that split the samples)
-    out = torch.empty(shape, dtype=torch.float32, device=dev)
-    if nt_fast:
+    out = None if one_d else torch.empty(shape, dtype=torch.float32, device=dev)
+    if one_d and nt_fast:
+        mod = mod.t().contiguous().t()
+    elif nt_fast:
         mod = mod.permute(1, 2, 0).contiguous().permute(2, 0, 1)
         out = torch.empty((n,) + shape[2:] + shape[1:2], dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
     reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
 
     def fused():
         s = screen.Screen(n, NK, dev)
-        s.add_slab(method, a, q, mod, crop=crop, halo_x=halo_x, minus=b, pair=True)
+        s.add_slab(method, a, q, mod, crop=crop, halo_x=halo_x, minus=b, pair="rows" if one_d else True)
         return s
 
     def parent():
@@ -208,15 +226,19 @@ def run_pair(name, args, dev):
     route = screen.last_route()
     p = parent()
     proute = screen.last_route()
-    sc, cov = composed()
+    if not one_d:
+        sc, cov = composed()
     torch.cuda.synchronize()
     got, old = s.finish(), p.finish()
     line = {"case": name, "shape": list(a.shape), "sets": 2, "nk": NK, "route": route, "replaced_route": proute,
             "bit_identical_to_replaced_route": bool(torch.equal(got.inside, old.inside)) and
             bool(torch.equal(got.score.view(torch.int32), old.score.view(torch.int32))),
-            "accept_equal_to_composed": bool(torch.equal(got.accept(), cov.inside)),
+            "accept_equal_to_replaced_route": bool(torch.equal(got.accept(), old.accept())),
             "accepted_per_level": [int(v) for v in got.accept().sum(dim=1).cpu()]}
-    fns = {"fused": fused, "parent": parent, "composed": composed, "residual": residual}
+    fns = {"fused": fused, "parent": parent, "residual": residual}
+    if not one_d:
+        line["accept_equal_to_composed"] = bool(torch.equal(got.accept(), cov.inside))
+        fns = {"fused": fused, "parent": parent, "composed": composed, "residual": residual}
     if args.only is not None and args.only not in fns:
         raise SystemExit(f"--only {args.only}: the paired cases have the routes {', '.join(fns)}")
     pick = [args.only] if args.only else list(fns)
@@ -253,7 +275,8 @@ def main():
     dev = torch.device("cuda:0")
     for name in args.cases.split(","):
         pair = name in PAIR_CASES
-        path = args.out or os.path.join(ROOT, "profiles", "screenpair" if pair else "screen",
+        folder = "screen1dpair" if name in PAIR1D_CASES else "screenpair" if pair else "screen"
+        path = args.out or os.path.join(ROOT, "profiles", folder,
                                         "screen_bench_pair.jsonl" if pair else "screen_bench.jsonl")
         os.makedirs(os.path.dirname(path), exist_ok=True)
         if pair:
