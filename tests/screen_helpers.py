@@ -42,9 +42,24 @@ def oracle_fp64():
         ocv.xcorr_torch = orig
 
 
-def oracle_residual(kind, x):
-    """The uncropped residual of ``x`` (float64 CPU) by the oracle."""
+def ns_coef(coef=None):
+    """dt, dx, dy, nu of the NS kinds: the module's, with ``coef`` (a dict, optional) on top"""
+    c = dict(dt=NS_DT, dx=NS_DX, dy=NS_DY, nu=NS_NU)
+    c.update(coef or {})
+    return c
+
+
+def oracle_residual(kind, x, coef=None):
+    """The uncropped residual of ``x`` (float64 CPU) by the oracle.  ``coef``: a dict of coefficients off the module's
+    (``dt, dx, dy, nu`` for the NS kinds, ``gamma`` for the MHD kinds); None: as before."""
     with oracle_fp64():
+        if coef is not None and kind.startswith("ns_"):
+            c = ns_coef(coef)
+            if kind == "ns_continuity":
+                return orr.ns_continuity(x, c["dx"], c["dy"], boundary=True)
+            return orr.ns_momentum(x, c["dt"], c["dx"], c["dy"], c["nu"], boundary=True)
+        if coef is not None and kind == "mhd_energy":
+            return orr.mhd_energy(x, boundary=True, **coef)
         if kind == "wave":
             return orr.wave_residual(x, 1.0, WAVE_DT, WAVE_DX, boundary=True)
         if kind == "lap":
@@ -56,8 +71,8 @@ def oracle_residual(kind, x):
         return getattr(orr, kind)(x, boundary=True)
 
 
-def method_of(kind, device="cpu"):
-    """The ``cp_pre_amd`` method the screen takes for ``kind``."""
+def method_of(kind, device="cpu", coef=None):
+    """The ``cp_pre_amd`` method the screen takes for ``kind``.  ``coef``: as ``oracle_residual`` takes it."""
     from cp_pre_amd import residuals as R
     from cp_pre_amd.convops_2d import ConvOperator
     if kind == "wave":
@@ -65,8 +80,9 @@ def method_of(kind, device="cpu"):
     if kind == "lap":
         return ConvOperator(("x", "y"), 2, device=device)
     if kind.startswith("ns_"):
-        return getattr(R.NavierStokes(NS_DT, NS_DX, NS_DY, nu=NS_NU, device=device), "residual_" + kind[3:])
-    return getattr(R.MHD(device=device), "residual_" + kind[4:])
+        c = ns_coef(coef)
+        return getattr(R.NavierStokes(c["dt"], c["dx"], c["dy"], nu=c["nu"], device=device), "residual_" + kind[3:])
+    return getattr(R.MHD(device=device, **(coef or {})), "residual_" + kind[4:])
 
 
 def fields(kind, shape, seed=0, n=None):
@@ -90,10 +106,11 @@ def fields(kind, shape, seed=0, n=None):
     return out[:, 0] if NCHAN[kind] is None else out
 
 
-def modulation(kind, shape, seed=0):
+def modulation(kind, shape, seed=0, coef=None):
     """float32 [T,X,Y]: [0.5, 2] times the per-cell std of the residuals of a synthetic calibration set of N_CAL
     samples."""
-    cal = oracle_residual(kind, fields(kind, shape, seed + 100, n=N_CAL).double())
+    kw = {} if coef is None else {"coef": coef}
+    cal = oracle_residual(kind, fields(kind, shape, seed + 100, n=N_CAL).double(), **kw)
     gen = torch.Generator().manual_seed(31 * seed + sum(shape))
     u = 0.5 + 1.5 * torch.rand(cal.shape[1:], generator=gen, dtype=torch.float64)
     return (u * cal.std(dim=0, unbiased=False)).float()
@@ -106,12 +123,13 @@ def region(shape, crop):
 class Case:
     """One screening case: inputs, levels and the float64 reference with its tolerances."""
 
-    def __init__(self, kind, shape, boundary, with_mod, nk, seed=0, crop=None):
-        self.kind, self.shape, self.boundary, self.nk = kind, tuple(shape), boundary, nk
+    def __init__(self, kind, shape, boundary, with_mod, nk, seed=0, crop=None, coef=None):
+        self.kind, self.shape, self.boundary, self.nk, self.coef = kind, tuple(shape), boundary, nk, coef
         self.crop = tuple(crop) if crop is not None else ((0, 0, 0) if boundary else (1, 1, 1))
+        kw = {} if coef is None else {"coef": coef}                                   # (None: the calls as they were)
         self.x = fields(kind, shape, seed)
-        self.mod = modulation(kind, shape, seed) if with_mod else None
-        r = oracle_residual(kind, self.x.double())
+        self.mod = modulation(kind, shape, seed, **kw) if with_mod else None
+        r = oracle_residual(kind, self.x.double(), **kw)
         self.r_ref = r
         reg = region(self.shape, self.crop)
         self.a = r[reg].abs().reshape(r.shape[0], -1)                                # |r_ref| [B, cells]

@@ -38,10 +38,11 @@ def route(kind, form):
     return "fused:" + ("flat_" if form == "flat" else "") + "pair_" + PAIR_KIND[kind]
 
 
-def modulation(kind, shape, seed=0):
+def modulation(kind, shape, seed=0, coef=None):
     """float32 [T,X,Y]: U[0.5, 2] times the per-cell std of r(cal_a) - r(cal_b) over ``sh.N_CAL`` calibration pairs."""
-    ca = sh.oracle_residual(kind, sh.fields(kind, shape, seed + 100, n=sh.N_CAL).double())
-    cb = sh.oracle_residual(kind, sh.fields(kind, shape, seed + 150, n=sh.N_CAL).double())
+    kw = {} if coef is None else {"coef": coef}
+    ca = sh.oracle_residual(kind, sh.fields(kind, shape, seed + 100, n=sh.N_CAL).double(), **kw)
+    cb = sh.oracle_residual(kind, sh.fields(kind, shape, seed + 150, n=sh.N_CAL).double(), **kw)
     gen = torch.Generator().manual_seed(31 * seed + sum(shape))
     u = 0.5 + 1.5 * torch.rand(ca.shape[1:], generator=gen, dtype=torch.float64)
     return (u * (ca - cb).std(dim=0, unbiased=False)).float()
@@ -50,12 +51,13 @@ def modulation(kind, shape, seed=0):
 class PairCase(sh.Case):
     """``screen_helpers.Case`` for the difference of two residuals: ``x`` the truth, ``y`` the prediction."""
 
-    def __init__(self, kind, shape, boundary, with_mod, nk, seed=0, crop=None):
-        self.kind, self.shape, self.boundary, self.nk, self.seed = kind, tuple(shape), boundary, nk, seed
+    def __init__(self, kind, shape, boundary, with_mod, nk, seed=0, crop=None, coef=None):
+        self.kind, self.shape, self.boundary, self.nk, self.seed, self.coef = kind, tuple(shape), boundary, nk, seed, coef
         self.crop = tuple(crop) if crop is not None else ((0, 0, 0) if boundary else (1, 1, 1))
+        kw = {} if coef is None else {"coef": coef}                                   # (``coef``: as ``sh.Case`` takes it)
         self.x, self.y = sh.fields(kind, shape, seed), sh.fields(kind, shape, seed + 50)
-        self.mod = modulation(kind, shape, seed) if with_mod else None
-        ra, rb = sh.oracle_residual(kind, self.x.double()), sh.oracle_residual(kind, self.y.double())
+        self.mod = modulation(kind, shape, seed, **kw) if with_mod else None
+        ra, rb = sh.oracle_residual(kind, self.x.double(), **kw), sh.oracle_residual(kind, self.y.double(), **kw)
         self.r_ref = r = ra - rb
         reg = sh.region(self.shape, self.crop)
         self.a = r[reg].abs().reshape(r.shape[0], -1)
