@@ -14,7 +14,13 @@
  *
  * Every call is asynchronous on the given HIP stream; no global atomics, no workspace: each workgroup owns the whole
  * column of 64 adjacent cells, so every result is bitwise reproducible.
- * Return codes: 0 ok; < 0 as in cp_pre_hip.h (PRE_E_*); > 0 a hipError_t.
+ * Return codes: 0 ok; < 0 as in cp_pre_hip.h (PRE_E_*); > 0 a hipError_t.  Every refusal is returned before any launch
+ * and writes nothing:
+ *   PRE_E_NULL   a null pointer (scores, an output, a table; only `send` and `vals` may be null, when nothing is sent or
+ *                received), or a source or run that cannot be addressed: n, per, planes, W or Co <= 0, C or c0 < 0,
+ *                C > W*Co, c0 + C > planes*per, row_stride < per with n > 1, plane_stride < per with planes > 1,
+ *                W > 65535 or more than 2^31 - 1 tiles; for the pick W > 64*1024 or Co <= 0;
+ *   PRE_E_RANGE  S or nk outside [1, PRE_DIST_MAX_SLOTS], packed != 0 with n*W > 32767, the pick's Co > 2^31 - 1.
  */
 #ifndef CP_PRE_DIST_H
 #define CP_PRE_DIST_H
@@ -42,8 +48,12 @@ int pre_dist_window_f32(const float *scores, int64_t plane_stride, int64_t row_s
 
 /* params [3, Cp] int32 (the caller derives them from the group's window): params[0][c] = klo, params[1][c] = the bits of
  * the fp32 scale sf > 0 of the value-linear map, or 0 for the key-linear one, params[2][c] = its shift s, or < 0: the
- * cell takes no part (NaN, constant or pad).  bucket(v) = min(NB-1, (int)((v - key2f(klo)) * sf)) (fp32, no contraction)
- * when sf > 0, else (key(v) - klo) >> s.
+ * cell takes no part (NaN, constant or pad).  bucket(v) = max(0, min(NB-1, (int)((v - key2f(klo)) * sf))) (fp32, no
+ * contraction, truncated) when sf > 0, else min(NB-1, (key(v) - klo) >> s) in uint32 arithmetic.  Both forms are clamped
+ * at both ends so that no score can index outside the NB counters; inside the window only the upper clamp of the
+ * value-linear form ever binds (at the window's top).  A score outside the agreed window [klo, khi] is the caller's
+ * error: it is counted in an end bucket, and the two forms do not agree on which (a key below klo wraps to NB-1 in
+ * the key-linear form and clamps to 0 in the value-linear one), so every rank must pass the window the group agreed on.
  * hist: the cell's counts per bucket, laid out [W][words][Co] (rank r's cells are one contiguous block: what a
  * reduce-scatter hands its owner); packed != 0 (n*W <= 32767 group-wide): words = NB/2, word w holds bucket w in its low
  * and bucket w + NB/2 in its high 16 bits; packed == 0: words = NB, one int32 per bucket.  Every word of the run is
