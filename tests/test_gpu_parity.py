@@ -703,9 +703,11 @@ def test_marginal_qhat_window_and_fallback_paths(gpu, n):
 
 @pytest.mark.parametrize("n", [129, 200, 256, 257, 300, 511, 512, 513, 640, 777, 1000, 1023, 1024])
 def test_marginal_qhat_register_resident_tiles(gpu, n):
-    """128 < n <= 1024 (kth_tile_kernel: a persistent workgroup holds a 64-cell tile in registers - 16 / 32 rows per
-    thread with two workgroups per CU, 64 with one -, exact [min, max] window, next tile prefetched into the same
-    registers; tiles its fast form cannot finish are marked and redone by the streaming form once its loop is done): ragged cell counts (fewer tiles than CUs, several tiles per workgroup, a partial
+    """240 < n <= 1024 (kth_tile_kernel: a persistent workgroup holds a 64-cell tile in registers - 16 / 24 / 32 rows per
+    thread with two workgroups per CU, 48 / 64 with one -, exact [min, max] window, next tile prefetched into the same
+    registers; tiles its fast form cannot finish are marked and redone by the streaming form once its loop is done) and,
+    since the dispatcher moved on, n = 129 (kth_small_kernel<136>: the column sorted in its lane's registers) and n = 200
+    (kth_pair_kernel<104>: two lanes per cell): ragged cell counts (fewer tiles than CUs, several tiles per workgroup, a partial
     last tile), one rank / ten / more than ten, both extremes, and every column kind that decides a path - constant,
     two-valued, heavy ties, one huge outlier (stretched window -> marked tile), infinities of either sign, NaNs,
     denormals, sorted columns, mixed signs - against torch.sort, bit for bit."""
@@ -749,9 +751,12 @@ def test_marginal_qhat_register_resident_tiles(gpu, n):
 
 @pytest.mark.parametrize("n", [129, 131, 192, 250, 256])
 def test_marginal_qhat_register_tiles_16_rows(gpu, n):
-    """128 < n <= 256 (kth_tile_kernel with 16 rows per thread, two workgroups per CU; round 2's two-lanes-per-cell
-    register sort, which this replaced, drew these cases): cell counts around the tile sizes, one rank and more than
-    ten, both extremes, ranks 127 / 128, ties, a NaN / an infinity in either half - against torch.sort, bit for bit."""
+    """128 < n <= 256, cases drawn for round 2's two-lanes-per-cell register sort and kept through the 16-row register
+    tiles that replaced it.  Today's dispatcher sends n = 129, 131 to kth_small_kernel<136> (one lane per cell), n = 192 to
+    kth_pair_kernel<96> (two lanes per cell again, pruned Batcher networks) and only n = 250, 256 to kth_tile_kernel with 16
+    rows per thread, two workgroups per CU (tests/SELECT_TESTS.md has every instantiation): cell counts around the tile
+    sizes, one rank and more than ten, both extremes, ranks 127 / 128, ties, a NaN / an infinity in either half - against
+    torch.sort, bit for bit."""
     from cp_pre_amd import inductive_cp as icp
     g = torch.Generator(device=gpu).manual_seed(n)
     for M in (1, 31, 32, 33, 127, 128, 129, 1000, 100003):
@@ -1971,7 +1976,7 @@ def _sharded_worker(rank, world, port, n_local, shape, out_dir):
 @pytest.mark.parametrize("n", [33, 100, 200, 300, 500, 700, 1000, 2049, 5000, 9000, 66000])
 def test_marginal_qhat_rows_with_a_pitch(gpu, n):
     """pre_kth_axis0_strided_f32 / pipeline.row_padded: the per-cell select over rows that are further apart than they are
-    long (every regime of n: register sort, register tiles, streaming fast and general forms, 32-bit counters) equals the
+    long (every regime of n: register sort, two lanes per cell, register tiles, streaming fast forms, 32-bit counters) equals the
     select over a contiguous copy, bit for bit; ragged cell counts, a NaN and a tie column included; the fused residual
     kernel writes through the padded view."""
     from cp_pre_amd import inductive_cp as icp
