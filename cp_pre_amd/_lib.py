@@ -324,6 +324,36 @@ for _form, _tail in (("", _scr), ("flat_", _scrf)):
         "pre_screenpair_%smhd_continuity_f32" % _form: _arr2 + [POINTER(c_float)] * 3 + [c_double] + _tail,
     })
 
+# libcp_pre_screencells.so (include/cp_pre_screencells.h): the two 2-D screens against per-cell sets: each entry takes its
+# joint twin's arguments with nk level fields in place of the nk levels
+SCREENCELLS_SO_PATH = os.path.join(_HERE, "libcp_pre_screencells.so")
+PRE_SCREENCELLS_ABI_VERSION = 1
+
+
+class PreScreenCells(ctypes.Structure):
+    """``pre_screencells_t``: ``pre_screen_t`` with nk level fields (level, plane and row strides) in place of ``q``."""
+    _fields_ = [("levels", c_void_p), ("nk", c_int), ("lK", c_int64), ("lT", c_int64), ("lX", c_int64),
+                ("modulation", c_void_p), ("mT", c_int64), ("mX", c_int64), ("ct", c_int), ("cx", c_int), ("cy", c_int),
+                ("score", c_void_p), ("count", c_void_p), ("count_ld", c_int64)]
+
+
+class PreScreenCellsFlat(ctypes.Structure):
+    """``pre_screencellsflat_t``: ``pre_screenflat_t`` with nk level fields (level stride, then the three logical strides)."""
+    _fields_ = [("levels", c_void_p), ("nk", c_int), ("lK", c_int64), ("lT", c_int64), ("lX", c_int64), ("lY", c_int64),
+                ("modulation", c_void_p), ("mT", c_int64), ("mX", c_int64), ("mY", c_int64), ("ct", c_int), ("cx", c_int),
+                ("cy", c_int), ("score", c_void_p), ("count", c_void_p), ("count_ld", c_int64)]
+
+
+SCREENCELLS_SIGNATURES = {"pre_screencells_abi_version": [], "pre_screencells_sample_group": []}
+for _form, _st in (("", PreScreenCells), ("flat_", PreScreenCellsFlat)):
+    _tail = [POINTER(_st)] + [c_int64] * 4 + [c_int, c_void_p]            # s, B, T, X, Y, flags, stream
+    SCREENCELLS_SIGNATURES.update({
+        "pre_screencells_%sstencil3d_f32" % _form: [_fld, POINTER(c_float), POINTER(c_int32), c_int] + _tail,
+        "pre_screencells_%slinear2_f32" % _form: [_fld, _fld, POINTER(c_float), POINTER(c_float), c_float] + _tail,
+        "pre_screencells_%sns_momentum_f32" % _form: [_fld, _fld, _fld] + [POINTER(c_float)] * 4 + [c_float] * 4 + _tail,
+        "pre_screencells_%smhd_f32" % _form: [c_int, POINTER(PreField)] + [POINTER(c_float)] * 3 + [c_double] + _tail,
+    })
+
 # libcp_pre_screen1dpair.so (include/cp_pre_screen1dpair.h): the 1-D screen for the data-driven scores r(a) - r(b): each entry
 # takes its single-set twin's arguments with the two field sets (pointer, strides each) in place of the twin's field
 SCREEN1DPAIR_SO_PATH = os.path.join(_HERE, "libcp_pre_screen1dpair.so")
@@ -384,8 +414,9 @@ _LIBS_MORE = {
     "vjpjorek": ("_vjpjorek", "VJPJOREK_", "pre_vjpjorek_abi_version", "PRE_VJPJOREK_ABI_VERSION", ()),
     "screenpair": ("_screenpair", "SCREENPAIR_", "pre_screenpair_abi_version", "PRE_SCREENPAIR_ABI_VERSION", ()),
     "screen1dpair": ("_screen1dpair", "SCREEN1DPAIR_", "pre_screen1dpair_abi_version", "PRE_SCREEN1DPAIR_ABI_VERSION", ()),
+    "screencells": ("_screencells", "SCREENCELLS_", "pre_screencells_abi_version", "PRE_SCREENCELLS_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -502,6 +533,10 @@ def load_screenpair():
 
 def load_screen1dpair():
     return _screen1dpair or _load("screen1dpair")
+
+
+def load_screencells():
+    return _screencells or _load("screencells")
 
 
 def require_gpu():

@@ -29,11 +29,13 @@ struct FGeom {
 // the plane loop, and an instantiation with scratch is not built: every functor gets the whole register file here.
 template <class Fn> struct ScreenMinWaves { static constexpr int value = 1; };
 
-template <class Fn>
+template <class Fn, class Sets = ScalarSets>
 __global__ void __launch_bounds__(FLAT_NT, ScreenMinWaves<Fn>::value)
-screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
+screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets)
 {
     constexpr int F = Fn::F;
+    constexpr bool CELLS = Sets::CELLS;
+    constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held at once)
     using SX = Staged<Fn>;
     constexpr bool ANY = SX::count > 0;
     static_assert(256 >= NKMAX + 1, "one thread per result in the combine step (the narrowest chunk has 256 threads)");
@@ -41,9 +43,15 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
     __shared__ unsigned int red[NKMAX + 1][FLAT_NW];
     const int q = threadIdx.x;
     unsigned Lb = xcd_remap(blockIdx.x, gridDim.x);
+    // per-cell sets: a group of CELLS_G samples is the fastest index, so the workgroups an XCD runs together (contiguous in
+    // Lb) read the same level quads and find them in its L2; the last group is partial when B % CELLS_G != 0
+    const int bl = CELLS ? Lb % CELLS_G : 0;
+    if constexpr (CELLS) Lb /= CELLS_G;
     const int ch = Lb % g.nCh; Lb /= g.nCh;
     const int ts = Lb % g.nTSeg;
-    const int b = Lb / g.nTSeg;
+    const int b = CELLS ? (Lb / g.nTSeg) * CELLS_G + bl : Lb / g.nTSeg;
+    if constexpr (CELLS)
+        if (b >= g.B) return;                      // (workgroup-uniform: no such sample in the last group)
     const int Ty = g.Y, L = g.X * g.Y;
     const int NT = blockDim.x;                     // threads per chunk, chosen by the host (the LDS image is sized for 512)
 
@@ -131,12 +139,32 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
         }
     };
 
-    // the levels: wave-uniform, read once
+    // per-cell sets: the quads of levels [k0, k0 + LB) at plane t, loaded like the modulation - only by threads with a
+    // counted cell, and t is always a plane of this segment
+    [[maybe_unused]] float4 ql[CELLS ? LB : 1];
+    [[maybe_unused]] auto load_lev = [&](int t, int k0) __attribute__((always_inline)) {
+        if constexpr (CELLS) {
+#pragma unroll
+            for (int k = 0; k < LB; ++k) {
+                if (anykeep && k0 + k < g.nk) {
+                    const float *p = g.q + ((long long)(k0 + k) * sets.qK + (long long)t * sets.qT);
+                    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
+                        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, -1, 0x00020000), (int)voff, 0, 0);
+                    ql[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+                } else {
+                    ql[k] = f4(0.f);
+                }
+            }
+        }
+    };
+
+    // the levels: wave-uniform, read once (per-cell sets: a quad per level and plane, load_lev)
     float qk[NKMAX];
     unsigned int cnt[NKMAX];
 #pragma unroll
     for (int k = 0; k < NKMAX; ++k) {
-        qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
+        if constexpr (CELLS) qk[k] = 0.f;
+        else qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
         cnt[k] = 0;
     }
     float smax = 0.f, sthr = 0.f;
@@ -145,6 +173,9 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
     auto step = [&](int t, float4(&P)[F], float4(&C)[F], float4(&N)[F], float4(&D)[F], FlatHalo<F> &hc, FlatHalo<F> &hn,
                     float4 &mc, float4 &mn) __attribute__((always_inline)) {
         const int bi = (t - t0) & 1;
+        // per-cell sets: this plane's first LB level quads go out BEFORE the field loads below, so the wait for them at the
+        // end of the plane (vmcnt retires in issue order) leaves the loads of the coming planes in flight
+        load_lev(t, 0);
 #pragma unroll
         for (int i = 0; i < F; ++i) {
             if (!SX::has(i)) continue;
@@ -191,7 +222,20 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
             n[i].yp = make_float4(rok[0] ? C[i].y : 0.f, rok[1] ? C[i].z : 0.f, rok[2] ? C[i].w : 0.f, rok[3] ? rgt : 0.f);
         }
         const float4 r = Fn::eval(n, prm);
-        screen_plane(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+        if constexpr (!CELLS) {
+            screen_plane(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+        } else if constexpr (LB == NKMAX) {
+            screen_plane_cells(r, mc, keep, g.nk, ql, cnt, smax, sthr, snan);
+        } else {
+            float ac[4], sv[4];
+            screen_plane_score(r, mc, keep, ac, sv, smax, sthr, snan);
+#pragma unroll
+            for (int k0 = 0; k0 < NKMAX; k0 += LB) {
+                if (k0 >= g.nk) break;                     // (wave-uniform)
+                if (k0 > 0) load_lev(t, k0);
+                screen_plane_count<LB>(ac, sv, k0, g.nk, ql, cnt);
+            }
+        }
     };
 
     float4 w0[F], w1[F], w2[F], w3[F], md0, md1;
@@ -235,8 +279,8 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm)
 }
 
 // ------------------------------------------------------------------ host side
-template <class Fn>
-int launch_screen_flat(FGeom &g, const typename Fn::Params &prm, hipStream_t st)
+template <class Fn, class Sets = ScalarSets>
+int launch_screen_flat(FGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets = Sets())
 {
     static_assert(2 * Staged<Fn>::FX * (FLAT_NT + 2 * FLAT_H) * 16 + (NKMAX + 1) * FLAT_NW * 4 <= 160 * 1024, "chunk does not fit the 160 KiB LDS");
     static_assert(FLAT_NOLDS_NT <= FLAT_NT, "the kernel's launch bound and its reduction buffer are sized for FLAT_NT threads");
@@ -245,20 +289,22 @@ int launch_screen_flat(FGeom &g, const typename Fn::Params &prm, hipStream_t st)
     g.nCh = (int)((quads + nt - 1) / nt);
     static std::atomic<int> per_cu[FLAT_NT / 64 + 1] = {};         // (by chunk width)
     unsigned grid;
-    const int rc = flat_split(screen_flat_kernel<Fn>, nt, per_cu, g, (long long)g.B * g.nCh, g.T, &grid);
+    // (per-cell sets: the grid covers whole groups of CELLS_G samples)
+    const long long nb = Sets::CELLS ? ((long long)g.B + CELLS_G - 1) / CELLS_G * CELLS_G : g.B;
+    const int rc = flat_split(screen_flat_kernel<Fn, Sets>, nt, per_cu, g, nb * g.nCh, g.T, &grid);
     if (rc) return rc;
-    hipLaunchKernelGGL((screen_flat_kernel<Fn>), dim3(grid), dim3(nt), 0, st, g, prm);
+    hipLaunchKernelGGL((screen_flat_kernel<Fn, Sets>), dim3(grid), dim3(nt), 0, st, g, prm, sets);
     PRE_LAUNCH_CHECK();
     return PRE_OK;
 }
 
 // the tap structures an Nt-fastest view runs (relabeled_mode: the reference's construction, the y-fixed one, the general star)
-template <template <int> class FnT, class P>
-int launch_screen_flat_mode(int mode, FGeom &g, const P &prm, hipStream_t st)
+template <template <int> class FnT, class P, class Sets = ScalarSets>
+int launch_screen_flat_mode(int mode, FGeom &g, const P &prm, hipStream_t st, const Sets &sets = Sets())
 {
-    if (mode == 3) return launch_screen_flat<FnT<3>>(g, prm, st);
-    if (mode == 4) return launch_screen_flat<FnT<4>>(g, prm, st);
-    return launch_screen_flat<FnT<2>>(g, prm, st);
+    if (mode == 3) return launch_screen_flat<FnT<3>>(g, prm, st, sets);
+    if (mode == 4) return launch_screen_flat<FnT<4>>(g, prm, st, sets);
+    return launch_screen_flat<FnT<2>>(g, prm, st, sets);
 }
 
 // Null / empty / range / layout checks of everything an entry hands to the kernel, and the geometry on the kernel's axes.

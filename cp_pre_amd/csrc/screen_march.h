@@ -22,11 +22,13 @@ struct SGeom {
     int ct, cx, cy, nk;
 };
 
-template <class Fn, int NR, int TYQ>
+template <class Fn, int NR, int TYQ, class Sets = ScalarSets>
 __global__ void __launch_bounds__(NR *TYQ, MinWaves<Fn>::value)
-screen_march_kernel(const SGeom g, const typename Fn::Params prm)
+screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets sets)
 {
     constexpr int F = Fn::F;
+    constexpr bool CELLS = Sets::CELLS;
+    constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held at once)
     using SX = Staged<Fn>;
     constexpr int NW = NR * TYQ / 64;
     static_assert(NR >= 8 && (4 * TYQ) % 64 == 0 && (NR * TYQ) % 64 == 0, "the two halo rows are fetched by the first 8*TYQ threads, a wave per 64 floats");
@@ -36,10 +38,16 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm)
 
     const int q = threadIdx.x, ty = threadIdx.y;
     unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    // per-cell sets: a group of CELLS_G samples is the fastest index, so the workgroups an XCD runs together (contiguous in
+    // L) read the same level quads and find them in its L2; the last group is partial when B % CELLS_G != 0
+    const int bl = CELLS ? L % CELLS_G : 0;
+    if constexpr (CELLS) L /= CELLS_G;
     const int yt = L % g.nYT; L /= g.nYT;
     const int xt = L % g.nXT; L /= g.nXT;
     const int ts = L % g.nTSeg;
-    const int b = L / g.nTSeg;
+    const int b = CELLS ? (L / g.nTSeg) * CELLS_G + bl : L / g.nTSeg;
+    if constexpr (CELLS)
+        if (b >= g.B) return;                      // (workgroup-uniform: no such sample in the last group)
 
     // the planes this workgroup evaluates: its segment, less the planes outside the counted region
     const int tc = (g.flags & PRE_FLAG_INTERIOR_T) ? max(g.ct, 1) : g.ct;
@@ -132,12 +140,33 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm)
         }
     };
 
-    // the levels: wave-uniform, read once
+    // per-cell sets: the quads of levels [k0, k0 + LB) at plane t, loaded like the modulation - only by threads with a
+    // counted cell, and t is always a plane of this segment
+    [[maybe_unused]] float4 ql[CELLS ? LB : 1];
+    [[maybe_unused]] auto load_lev = [&](int t, int k0) __attribute__((always_inline)) {
+        if constexpr (CELLS) {
+#pragma unroll
+            for (int k = 0; k < LB; ++k) {
+                if (anykeep && k0 + k < g.nk) {
+                    const float *p = g.q + ((long long)(k0 + k) * sets.qK + (long long)t * sets.qT);
+                    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
+                        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, -1, 0x00020000),
+                        (int)(unsigned int)(((long long)x * sets.qX + y) * 4), 0, 0);
+                    ql[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+                } else {
+                    ql[k] = f4(0.f);
+                }
+            }
+        }
+    };
+
+    // the levels: wave-uniform, read once (per-cell sets: a quad per level and plane, load_lev)
     float qk[NKMAX];
     unsigned int cnt[NKMAX];
 #pragma unroll
     for (int k = 0; k < NKMAX; ++k) {
-        qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
+        if constexpr (CELLS) qk[k] = 0.f;
+        else qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
         cnt[k] = 0;
     }
     float smax = 0.f, sthr = 0.f;
@@ -149,6 +178,9 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm)
     auto step = [&](int t, float4(&P)[F], float4(&C)[F], float4(&N)[F], float4(&D)[F],
                     Halo<F, false, COOP> &hc, Halo<F, false, COOP> &hn, float4 &mc, float4 &mn) __attribute__((always_inline)) {
         const int bi = (t - t0) & 1;
+        // per-cell sets: this plane's first LB level quads go out BEFORE the field loads below, so the wait for them at the
+        // end of the plane (vmcnt retires in issue order) leaves the loads of the coming planes in flight
+        load_lev(t, 0);
 #pragma unroll
         for (int i = 0; i < F; ++i) {
             if (!SX::has(i)) continue;
@@ -187,7 +219,20 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm)
             n[i].yp = make_float4(C[i].y, C[i].z, C[i].w, rgt);
         }
         const float4 r = Fn::eval(n, prm);
-        screen_plane(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+        if constexpr (!CELLS) {
+            screen_plane(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+        } else if constexpr (LB == NKMAX) {
+            screen_plane_cells(r, mc, keep, g.nk, ql, cnt, smax, sthr, snan);
+        } else {
+            float ac[4], sv[4];
+            screen_plane_score(r, mc, keep, ac, sv, smax, sthr, snan);
+#pragma unroll
+            for (int k0 = 0; k0 < NKMAX; k0 += LB) {
+                if (k0 >= g.nk) break;                     // (wave-uniform)
+                if (k0 > 0) load_lev(t, k0);
+                screen_plane_count<LB>(ac, sv, k0, g.nk, ql, cnt);
+            }
+        }
     };
 
     Halo<F, false, COOP> h0, h1;
@@ -232,8 +277,8 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm)
 }
 
 // ------------------------------------------------------------------ host side
-template <class Fn, int NR, int TYQ>
-int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st)
+template <class Fn, int NR, int TYQ, class Sets>
+int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets)
 {
     static_assert(2 * Staged<Fn>::FX * (NR + 2) * TYQ * 16 + (NKMAX + 1) * (NR * TYQ / 64) * 4 <= 160 * 1024, "tile does not fit the 160 KiB LDS");
     g.nXT = (g.X + NR - 1) / NR;
@@ -241,34 +286,39 @@ int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st
     for (int i = 0; i < Fn::F; ++i)            // a thread's place in a plane is a 32-bit byte offset (from one row before row 0)
         if (g.sX[i] < 0 || ((long long)(g.X + 2 + NR) * g.sX[i] + g.Y + 8) * 4 >= (1LL << 32)) return PRE_E_SHAPE;
     if (g.mod && (g.mX < 0 || ((long long)(g.X + NR) * g.mX + g.Y + 8) * 4 >= (1LL << 32))) return PRE_E_SHAPE;
-    long long tiles = (long long)g.B * g.nXT * g.nYT;
-    static const int per_cu = resident_per_cu(screen_march_kernel<Fn, NR, TYQ>, NR * TYQ);
+    long long nb = g.B;                        // samples the grid covers: per-cell sets, whole groups of CELLS_G
+    if constexpr (Sets::CELLS) {
+        nb = (nb + CELLS_G - 1) / CELLS_G * CELLS_G;
+        if (sets.qX < 0 || ((long long)(g.X + NR) * sets.qX + g.Y + 8) * 4 >= (1LL << 32)) return PRE_E_SHAPE;
+    }
+    long long tiles = nb * g.nXT * g.nYT;
+    static const int per_cu = resident_per_cu(screen_march_kernel<Fn, NR, TYQ, Sets>, NR * TYQ);
     int tSeg = pick_tseg(tiles, g.T, (long long)per_cu * chip_cus());
     if (TFREE_TSEG > 0 && g.tfree && tSeg > TFREE_TSEG) tSeg = TFREE_TSEG;     // (segments cost no window prologue then)
     g.tSeg = tSeg;
     g.nTSeg = (g.T + tSeg - 1) / tSeg;
     tiles *= g.nTSeg;
     if (tiles <= 0 || tiles * TYQ > 0xffffffffLL) return PRE_E_SHAPE;      // the dispatch packet counts work-items in 32 bits
-    hipLaunchKernelGGL((screen_march_kernel<Fn, NR, TYQ>), dim3((unsigned)tiles), dim3(TYQ, NR), 0, st, g, prm);
+    hipLaunchKernelGGL((screen_march_kernel<Fn, NR, TYQ, Sets>), dim3((unsigned)tiles), dim3(TYQ, NR), 0, st, g, prm, sets);
     PRE_LAUNCH_CHECK();
     return PRE_OK;
 }
 
-template <class Fn>
-int launch_screen(SGeom &g, const typename Fn::Params &prm, hipStream_t st)
+template <class Fn, class Sets = ScalarSets>
+int launch_screen(SGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets = Sets())
 {
     // the tiles of star_march.h's launch()
-    if (g.Y >= 192) return launch_screen_tiled<Fn, 8, 64>(g, prm, st);
-    if (g.Y >= 96) return launch_screen_tiled<Fn, 16, 32>(g, prm, st);
-    return launch_screen_tiled<Fn, 32, 16>(g, prm, st);
+    if (g.Y >= 192) return launch_screen_tiled<Fn, 8, 64>(g, prm, st, sets);
+    if (g.Y >= 96) return launch_screen_tiled<Fn, 16, 32>(g, prm, st, sets);
+    return launch_screen_tiled<Fn, 32, 16>(g, prm, st, sets);
 }
 
-template <template <int> class FnT, class P>
-int launch_screen_mode(int mode, SGeom &g, const P &prm, hipStream_t st)
+template <template <int> class FnT, class P, class Sets = ScalarSets>
+int launch_screen_mode(int mode, SGeom &g, const P &prm, hipStream_t st, const Sets &sets = Sets())
 {
-    if (mode == 0) return launch_screen<FnT<0>>(g, prm, st);
-    if (mode == 1) return launch_screen<FnT<1>>(g, prm, st);
-    return launch_screen<FnT<2>>(g, prm, st);
+    if (mode == 0) return launch_screen<FnT<0>>(g, prm, st, sets);
+    if (mode == 1) return launch_screen<FnT<1>>(g, prm, st, sets);
+    return launch_screen<FnT<2>>(g, prm, st, sets);
 }
 
 // Null / empty / layout / range checks of everything an entry hands to the kernel, and the geometry.  No axis relabelling

@@ -55,4 +55,75 @@ __device__ __forceinline__ void screen_plane(const float4 &r, const float4 &mm, 
     }
 }
 
+// What the per-cell screen (screen_cells.hip) adds to the two marches, as compile-time constants of its library.
+// CELLS_G: the samples of a group, the fastest index of its block order (1: the order of the joint screens).
+#ifndef PRE_SCREENCELLS_GROUP
+#define PRE_SCREENCELLS_GROUP 16
+#endif
+constexpr int CELLS_G = PRE_SCREENCELLS_GROUP;
+static_assert(CELLS_G >= 1, "a group has at least one sample");
+// The sets a launch screens against, a compile-time policy of the two marches and their last kernel argument.  ScalarSets
+// (the default): g.q is nk wave-uniform levels.  CellSets: g.q is nk level FIELDS [T,X,Y] shared by all samples, with unit
+// stride on the fields' unit-stride axis; a thread loads nk level quads per plane next to the modulation quad.
+struct ScalarSets { static constexpr bool CELLS = false; };
+struct CellSets {
+    static constexpr bool CELLS = true;
+    long long qK, qT, qX;      // level, marched-plane and row strides of g.q in elements (the merged-row march has no rows)
+};
+// CellsBatch<Fn>: the level quads a thread holds at once.  NKMAX: all of a plane's quads are issued before its field loads
+// and counted after its functor; a functor whose instantiation would carry scratch with 16 more quads gets fewer (screen_cells.hip), and
+// the quads beyond the first batch are fetched after the functor, a batch at a time.
+#ifndef PRE_SCREENCELLS_BATCH
+#define PRE_SCREENCELLS_BATCH 16
+#endif
+static_assert(PRE_SCREENCELLS_BATCH >= 1 && PRE_SCREENCELLS_BATCH <= NKMAX && NKMAX % PRE_SCREENCELLS_BATCH == 0, "whole batches");
+template <class Fn, class = void> struct CellsBatch { static constexpr int value = PRE_SCREENCELLS_BATCH; };
+
+// The same end of a plane for per-cell levels (screen_cells.hip): ql[k] is the quad of level k's field at the thread's four
+// cells, so hw = ql[k][j] * m[j], the product of pre_cov_levels_f32 with a level field (q_ld != 0); without a modulation
+// mm is 1 and 1.0f * q == q exactly, NaN, inf and sign included.  In two parts, so that a functor that leaves no room for
+// nk quads can take them in batches: the score and the masked |r| once per plane, then the counts of levels [k0, k0 + NB).
+__device__ __forceinline__ void screen_plane_score(const float4 &r, const float4 &mm, const bool (&keep)[4], float (&ac)[4],
+                                                   float (&sv)[4], float &m, float &thr, bool &nan)
+{
+    const float rv[4] = {r.x, r.y, r.z, r.w}, mv[4] = {mm.x, mm.y, mm.z, mm.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float a = fabsf(rv[j]);
+        sv[j] = keep[j] ? mv[j] : 1.0f;
+        score_update(keep[j] ? a : 0.0f, sv[j], m, thr, nan);
+        ac[j] = keep[j] ? a : __builtin_nanf("");
+    }
+}
+
+template <int NB>
+__device__ __forceinline__ void screen_plane_count(const float (&ac)[4], const float (&sv)[4], int k0, int nk,
+                                                   const float4 (&ql)[NB], unsigned int (&cnt)[NKMAX])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        if (k0 + k < nk) {                                   // (wave-uniform)
+            const float qv[4] = {ql[k].x, ql[k].y, ql[k].z, ql[k].w};
+            unsigned int c = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float hw = qv[j] * sv[j];
+                c += (unsigned int)__popcll(__builtin_amdgcn_fcmpf(ac[j], hw, 5));      // 5: ordered <= (NaN: outside)
+            }
+            cnt[k0 + k] += c;
+        }
+    }
+}
+
+// screen_plane with a level quad per k in place of the wave-uniform qk[]
+__device__ __forceinline__ void screen_plane_cells(const float4 &r, const float4 &mm, const bool (&keep)[4], int nk,
+                                                   const float4 (&ql)[NKMAX], unsigned int (&cnt)[NKMAX], float &m, float &thr,
+                                                   bool &nan)
+{
+    float ac[4], sv[4];
+    screen_plane_score(r, mm, keep, ac, sv, m, thr, nan);
+    screen_plane_count<NKMAX>(ac, sv, 0, nk, ql, cnt);
+}
+
 }  // namespace

@@ -80,6 +80,17 @@ alpha, where the calibration left a quantile per cell - need no entry of their o
 modulation and one level of 1, ``screen(method, vars, torch.ones(1), modulation=qhat_cells, [minus=pred, pair=True])``.
 ``1.0f * m == m`` exactly, so ``inside[0]`` counts ``|d| <= qhat_cells`` exactly (``emp_cov_levels``'s count per sample).
 
+Per-cell sets at SEVERAL levels - how every ``Marginal/*_Residuals_CP.py`` script ends (``Marginal/NS_Residuals_CP.py:307-337``,
+``Marginal/MHD_Residuals_CP.py:408-418``, ``Marginal/Wave_Residuals_CP.py:284-288``): ``calibrate_multi`` leaves a quantile per
+cell at ten alphas, and each is checked against the residual of every held-out prediction - have an entry of their own,
+``screen_cells(method, vars, qcells, modulation=None)`` / ``ScreenCells`` (``libcp_pre_screencells.so``,
+``include/cp_pre_screencells.h``): both marches above with nk level quads per cell and plane next to the field loads, the
+samples taken in groups (``sample_group()``) so that a group shares its level quads in an XCD's L2.  ``inside[k, b]`` counts
+``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with one): ``emp_cov_levels``'s count with per-cell levels, per sample.
+Routes ``fused:cells_<kind>`` / ``fused:flat_cells_<kind>`` for the kinds of the first paragraph; the 1-D family, JOREK,
+``minus=`` and every reason above keep the three-pass route (one ``CoverageLevels`` pass per sample with the per-cell
+levels).  Without a call to these two the library is never loaded.
+
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
@@ -171,6 +182,8 @@ _JOREK_ENTRY = {"": "pre_screenjorek_f32", "flat": "pre_screenjorek_flat_f32"}
 # the kinds with a paired screen (opt-in, ``pair=True`` with ``minus=``), a library of their own: form -> prefix of its entries
 _PAIR_KINDS = ("stencil3d", "linear2", "ns_momentum", "mhd_continuity")
 _PAIR_ENTRY = {"": "pre_screenpair_", "flat": "pre_screenpair_flat_"}
+# the per-cell screens (``screen_cells`` / ``ScreenCells``), a library of their own: form -> prefix of its entries
+_CELLS_ENTRY = {"": "pre_screencells_", "flat": "pre_screencells_flat_"}
 # the paired screen of the 1-D family (opt-in, ``pair="rows"`` with ``minus=``), one more library: the prefix of its entries
 _PAIR_ROWS_ENTRY = "pre_screen1dpair_"
 
@@ -330,8 +343,11 @@ class _Spec(Method):
         return minus.dim() == 3 and minus.stride(ax) != 1 and minus.stride(3 - ax) == 1
 
     # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
-    def entry(self, form, pair=False):
-        """The entry point of this method's fused screen in the library of ``form`` (``pair``: of its paired screen)."""
+    def entry(self, form, pair=False, cells=False):
+        """The entry point of this method's fused screen in the library of ``form`` (``pair``: of its paired screen,
+        ``cells``: of its per-cell screen)."""
+        if cells:
+            return _CELLS_ENTRY[form] + ("mhd" if self.kind in _MHD_EQ else self.kind) + "_f32"
         if pair:
             return _PAIR_ROWS_ENTRY + self.rows_kind + "_f32" if form == "rows" else _PAIR_ENTRY[form] + self.kind + "_f32"
         if self.kind in _JOREK_EQ and form != "rows":
@@ -339,13 +355,16 @@ class _Spec(Method):
         kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
         return _FORMS[form][1] + kind + "_f32"
 
-    def route(self, form, pair=False):
+    def route(self, form, pair=False, cells=False):
+        if cells:
+            return "fused:" + _FORMS[form][2] + "cells_" + self.kind
         return "fused:" + _FORMS[form][2] + ("pair_" if pair else "") + (self.rows_kind if form == "rows" else self.kind)
 
-    def launch(self, kernels, x, st, flags, form="", minus=None):
+    def launch(self, kernels, x, st, flags, form="", minus=None, cells=False):
         """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code.
         ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so`` for forms '' and 'flat',
-        ``libcp_pre_screen1dpair.so`` for 'rows')."""
+        ``libcp_pre_screen1dpair.so`` for 'rows').  ``cells``: the per-cell screen (``libcp_pre_screencells.so``, forms ''
+        and 'flat'; ``st`` is then its set descriptor)."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
         if minus is not None and form == "rows":
             sets = (_lib.ptr(x), _lib.iarr64(x.stride()), _lib.ptr(minus), _lib.iarr64(minus.stride()))
@@ -362,7 +381,7 @@ class _Spec(Method):
             fn = getattr(_lib.load_screenpair(), self.entry(form, True))
             return fn(*views, *kernels, *self.scalars(), ctypes.byref(st), *fa[0].shape, flags, _lib.stream())
         kind = self.rows_kind if form == "rows" else self.kind
-        lib = getattr(_lib, "load_screenjorek" if kind in _JOREK_EQ else _FORMS[form][0])()
+        lib = _lib.load_screencells() if cells else getattr(_lib, "load_screenjorek" if kind in _JOREK_EQ else _FORMS[form][0])()
         if form == "rows":
             views, shape = (_lib.ptr(x), _lib.iarr64(x.stride())), x.shape
         else:
@@ -379,7 +398,8 @@ class _Spec(Method):
                 views = [ctypes.byref(_lib.field(f)) for f in fs]
         if kind.startswith("stencil"):
             kernels = _dispatch.tap_args(*kernels)
-        return getattr(lib, self.entry(form))(*views, *kernels, *self.scalars(), ctypes.byref(st), *shape, flags, _lib.stream())
+        return getattr(lib, self.entry(form, cells=cells))(*views, *kernels, *self.scalars(), ctypes.byref(st), *shape, flags,
+                                                           _lib.stream())
 
     def launch_flat(self, kernels, x, st, flags):
         return self.launch(kernels, x, st, flags, "flat")
@@ -528,7 +548,8 @@ class Screen:
         self.cells += cells
 
     def _fallback(self, spec, vars, qhats, modulation, crop, halo_x, minus):
-        """What a user writes today: the residual by the existing pass with ``boundary=True``, ``ncf_metric_joint`` over
+        """(``qhats``: [nk], or for ``ScreenCells`` the level fields [nk, *uncropped residual extents].)
+        What a user writes today: the residual by the existing pass with ``boundary=True``, ``ncf_metric_joint`` over
         the cropped interior, ``CoverageLevels`` for the counts.  ``CoverageLevels`` counts over all the samples it is
         given, so the per-sample counts take one pass PER SAMPLE (n launches over a sample each; together they read the
         residual once): this route is for correctness where the fused launch cannot run, not for speed."""
@@ -547,7 +568,7 @@ class Screen:
             s = (r64 / m64 if m64 is not None else r64).reshape(res.shape[0], -1)
             score = s.max(dim=1).values
             score = torch.where(torch.isnan(s).any(dim=1), torch.full_like(score, float("nan")), score).float()
-            hw = q.double().reshape(-1, *([1] * (res.dim() - 1)))
+            hw = q[(slice(None),) + sl[1:]].double() if q.dim() > 1 else q.double().reshape(-1, *([1] * (res.dim() - 1)))
             hw = hw * m64 if m64 is not None else hw
             counts = torch.stack([(r64 <= hw[k]).reshape(res.shape[0], -1).sum(dim=1) for k in range(self.nk)])
         else:
@@ -558,6 +579,8 @@ class Screen:
                 score = icp.ncf_metric_joint(res[sl].contiguous(), None, ones[sl[1:]].contiguous())
             # the counts per sample: a CoverageLevels pass per sample (its marginal count is a total over its samples)
             rows, mrows = res[sl], (mod[sl[1:]] if mod is not None else None)
+            if q.dim() > 1:                                  # (per-cell levels, ``ScreenCells``: the counted cells' ones)
+                q = q[(slice(None),) + sl[1:]]
             counts = torch.empty(self.nk, res.shape[0], dtype=torch.int64, device=res.device)
             cov = pipeline.CoverageLevels(1, self.nk, res.device)
             for i in range(res.shape[0]):
@@ -592,4 +615,134 @@ def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=
     out = s.finish()
     if not vars.is_cuda:                                     # (staged inputs: the verdicts come home, as elsewhere)
         out.score, out.inside = out.score.to(vars.device), out.inside.to(vars.device)
+    return out
+
+
+# ------------------------------------------------------------------------------------------- per-cell sets
+def sample_group():
+    """Samples per group in the block order of the per-cell screens (``pre_screencells_sample_group``): speed only."""
+    return int(_lib.load_screencells().pre_screencells_sample_group())
+
+
+def _check_cells(spec, vars, qcells, modulation, minus, crop, nk=None):
+    """``_check_inputs`` for level fields: every error before any device work.  Returns (uncropped residual shape, crop,
+    counted cells per sample); ``qcells`` has the uncropped extents or (``cropped`` in the caller) the cropped ones."""
+    if not isinstance(qcells, torch.Tensor):
+        raise TypeError("qcells must be a torch.Tensor [nk, *residual extents]")
+    if qcells.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"qcells has dtype {qcells.dtype}: float32 levels (float64 ones take the fallback)")
+    if qcells.dim() < 2 or not 1 <= qcells.shape[0] <= _lib.PRE_SCREEN_MAX_LEVELS or qcells.numel() == 0:
+        raise ValueError(f"qcells has shape {tuple(qcells.shape)}, expected [nk, *residual extents] with 1 <= nk <= "
+                         f"{_lib.PRE_SCREEN_MAX_LEVELS}")
+    # (the checks of vars, modulation, minus and crop, with one level value per k standing in for the [nk] levels)
+    return _check_inputs(spec, vars, qcells[(slice(None),) + (0,) * (qcells.dim() - 1)], modulation, minus, crop, nk)
+
+
+class ScreenCells(Screen):
+    """``Screen`` against per-cell sets: ``add_slab`` takes the level fields of the slab in place of the nk levels.
+    Accumulation, ``crop``, ``halo_x`` and ``finish`` are ``Screen``'s: slabs compose to the bits of the whole grid."""
+
+    def add_slab(self, method, vars_slab, qcells_slab, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None):
+        """``qcells_slab``: fp32 [nk, *uncropped residual extents of the slab] on the slab's device, shared by all samples
+        (its values outside the counted region are never used); the other arguments as ``Screen.add_slab`` takes them.
+        Level fields whose unit-stride axis is not the fields' are copied once into the matching layout, as the
+        modulation is.  ``minus`` keeps the three-pass route (``fallback:minus=``)."""
+        global _last_route
+        spec = method if isinstance(method, _Spec) else _Spec(method)
+        shape, crop, cells = _check_cells(spec, vars_slab, qcells_slab, modulation_slab, minus, crop, self.nk)
+        if tuple(qcells_slab.shape[1:]) != tuple(shape[1:]):
+            raise ValueError(f"qcells has shape {tuple(qcells_slab.shape)}, expected {(self.nk,) + tuple(shape[1:])}: the "
+                             "uncropped extents of the residual")
+        if shape[0] != self.n_local:
+            raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
+        if _dev_key(vars_slab.device) != _dev_key(self.device):
+            raise ValueError(f"slab on {vars_slab.device}, this Screen was made for {self.device}")
+        why, kernels = spec.prepare(vars_slab, minus, qcells_slab, modulation_slab)
+        if halo_x and not vars_slab.is_cuda:
+            raise ValueError("halo_x needs a device-resident view of a larger grid (a staged copy has no halo rows)")
+        if halo_x and why is not None and not spec.reads_halo():
+            raise RuntimeError(f"halo_x: the fused screen cannot run ({why}) and no other pass of this method reads the halo rows")
+        flat = spec.kind is not None and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
+        if flat:
+            why, kernels = spec.prepare_flat(vars_slab, minus, qcells_slab, modulation_slab)
+        if why is None:
+            acc = self._buffers(vars_slab.device)
+            mod, lev = modulation_slab, qcells_slab
+            if flat:
+                if mod is not None and (mod.stride(0) != 1 or mod.stride(2) != mod.shape[0]):
+                    mod = mod.permute(1, 2, 0).contiguous().permute(2, 0, 1)       # (one sample-sized copy, memory [X,Y,T])
+                if lev.stride(1) != 1 or lev.stride(3) != lev.shape[1]:
+                    lev = lev.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)  # (nk of them, memory [nk,X,Y,T])
+                st = _lib.PreScreenCellsFlat(_lib.ptr(lev), self.nk, *lev.stride(), _lib.ptr(mod),
+                                             *(mod.stride() if mod is not None else (0, 0, 0)), crop[0], crop[1], crop[2],
+                                             ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
+            else:
+                if mod is not None and mod.stride(-1) != 1:
+                    mod = mod.contiguous()
+                if lev.stride(-1) != 1:
+                    lev = lev.contiguous()
+                st = _lib.PreScreenCells(_lib.ptr(lev), self.nk, *lev.stride()[:3], _lib.ptr(mod),
+                                         mod.stride(0) if mod is not None else 0, mod.stride(1) if mod is not None else 0,
+                                         crop[0], crop[1], crop[2], ctypes.c_void_p(acc[0].data_ptr()),
+                                         ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
+            form = "flat" if flat else ""
+            with torch.no_grad(), torch.cuda.device(vars_slab.device):
+                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0, form, cells=True)
+            if rc == _lib.PRE_E_UNSUPPORTED:
+                why = "declined by the library"
+                if halo_x and not spec.reads_halo():
+                    raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
+            else:
+                _lib.check(rc, spec.entry(form, cells=True))
+                _last_route = spec.route(form, cells=True)
+                self.cells += cells
+                return
+        _last_route = "fallback:" + why
+        self._fallback(spec, vars_slab, qcells_slab, modulation_slab, crop, halo_x, minus)
+        self.cells += cells
+
+
+def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False, minus=None):
+    """Screen the predictions ``vars`` against the per-cell sets ``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with a
+    modulation) at every level k in one launch; the residual is never stored.  ``qcells``: fp32 ``[nk, *uncropped residual
+    extents]`` on ``vars``' device, 1 <= nk <= 16.  ``boundary=False``: the counted cells are the interior ``[1:-1]`` of
+    every residual axis, and ``qcells`` may instead have the CROPPED extents - what ``calibrate_multi`` returns for scores
+    taken from ``res[..., 1:-1, 1:-1, 1:-1]``; it is then padded once with NaN to the uncropped extents (one copy of nk
+    sample-sized fields, in the fields' layout).  ``boundary=True``: every cell, uncropped extents only.  Inside the counted
+    region a NaN level or a NaN residual puts the cell outside at that level, a negative level puts it outside, ``+inf``
+    puts it inside for every non-NaN residual.  ``minus`` (the data-driven score) keeps the three-pass route.  Returns a
+    :class:`Screened`: ``inside``, ``accept()``, ``coverage_marginal(group=)``, ``within()`` and ``score`` as for
+    ``screen``; the samples may be sharded by the batch axis with nothing exchanged.
+
+    Measured (nk = 10): this launch is SLOWER than the residual pass followed by ONE ``CoverageLevels`` pass
+    with per-cell levels (``emp_cov_levels``) - 3.8 against 2.6 ms for the wave residual on [512,32,256,256], 69 against 34 ms
+    for NS momentum on Nt-fastest [512,3,64,512,512].  That route gives the totals of the coverage curve only; who needs
+    nothing else should keep it.  This one gives per-sample counts - ``accept``, ``within``, the score - stores no residual,
+    takes slabs, and is 4-6 times faster than ten calls of the one-level trick, the other way to the same answer."""
+    spec = _Spec(residual_method)
+    crop = (0,) * spec.nd if boundary else (1,) * spec.nd
+    shape, _, _ = _check_cells(spec, vars, qcells, modulation, minus, crop)
+    full, cropped = tuple(shape[1:]), tuple(n - 2 * c for n, c in zip(shape[1:], crop))
+    if tuple(qcells.shape[1:]) != full:
+        if boundary or tuple(qcells.shape[1:]) != cropped:
+            raise ValueError(f"qcells has shape {tuple(qcells.shape)}, expected [nk, *{full}]" +
+                             ("" if boundary else f" or the cropped [nk, *{cropped}]"))
+        qcells = _pad_levels(qcells, full, vars.is_cuda and spec.nt_fastest(vars))
+    s = ScreenCells(shape[0], qcells.shape[0], vars.device)
+    s.add_slab(spec, vars, qcells, modulation, crop=crop, minus=minus)
+    out = s.finish()
+    if not vars.is_cuda:                                     # (staged inputs: the verdicts come home, as elsewhere)
+        out.score, out.inside = out.score.to(vars.device), out.inside.to(vars.device)
+    return out
+
+
+def _pad_levels(qcells, full, nt_fastest):
+    """Cropped level fields [nk, *cropped] inside NaN fields of the uncropped extents ``full`` (a NaN level is outside:
+    the rim is never counted anyway); ``nt_fastest``: memory [nk,X,Y,T], the layout of an Nt-fastest view's fields."""
+    nk = qcells.shape[0]
+    if nt_fastest and len(full) == 3:
+        out = torch.full((nk, full[1], full[2], full[0]), float("nan"), dtype=qcells.dtype, device=qcells.device).permute(0, 3, 1, 2)
+    else:
+        out = torch.full((nk,) + tuple(full), float("nan"), dtype=qcells.dtype, device=qcells.device)
+    out[(slice(None),) + (slice(1, -1),) * len(full)] = qcells
     return out

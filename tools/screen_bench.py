@@ -48,6 +48,17 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                takes no ``out=``: it allocates its result on every call).  There is no (B): a user composes nothing
                shorter for per-sample verdicts of this family.  Lines go to profiles/screen1dpair/screen_bench_pair.jsonl
 
+    c2_wave_cells / c3_rank8_ntfast_cells
+               the per-cell screen (``screen.ScreenCells``: ``libcp_pre_screencells.so``) at nk = 10 level fields, no modulation:
+               the wave residual on [512,32,256,256], Ny-fastest, and NS momentum in the shape and layout of c3_rank8_ntfast.
+               Routes, alternated call by call: (F) the fused launch, once per library of ``--cells-libs G=path,...`` (build
+               variants of the sample group, ``make SCREENCELLS_GROUP=G``; default: the package's own library); (A) the
+               fastest existing route to the coverage curve - the residual pass into a buffer plus ONE marginal
+               ``CoverageLevels`` pass with per-cell levels, which gives totals, not per-sample counts; (B) nk calls of the
+               one-level trick (the level field as the modulation of ``screen.Screen``); (C) the joint screen of the same
+               fields at nk scalar levels - the same march without the per-cell reads, the floor.  Lines go to
+               profiles/screencells/screen_bench_cells.jsonl unless --out says otherwise
+
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
@@ -261,6 +272,103 @@ def run_pair(name, args, dev):
     return line
 
 
+CELLS_CASES = {"c2_wave_cells": "c2_wave", "c3_rank8_ntfast_cells": "c3_rank8_ntfast"}
+
+
+def run_cells(name, args, dev):
+    """One per-cell case: (F) per library, (A), (B), (C) alternated, one JSON line."""
+    from cp_pre_amd import _lib
+    method, v, crop, halo_x, residual_into, fbytes = case(CELLS_CASES[name], args.div, dev)
+    n = v.shape[0]
+    nt_fast = v.stride(-1) != 1
+    shape = (n,) + tuple(v.shape[-3:])
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    if nt_fast:
+        out = torch.empty((n,) + shape[2:] + shape[1:2], dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+    reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
+    # level fields in the fields' layout: level k about (k + 1) / nk of twice the mean |r|, scattered per cell by +-50 %
+    residual_into(out)
+    scale = float(out[:min(n, 8)].abs().mean())
+    qc = torch.rand((NK,) + shape[1:], device=dev) + 0.5
+    qc *= (2.0 * scale / NK) * torch.arange(1, NK + 1, device=dev, dtype=torch.float32).reshape(NK, 1, 1, 1)
+    if nt_fast:
+        qc = qc.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    qs = torch.linspace(0.2, 2.0, NK, device=dev) * scale
+    one = torch.ones(1, device=dev)
+    # the libraries of (F): handles loaded once, swapped into the loader's cache before each call
+    libs = {}
+    if args.cells_libs:
+        for item in args.cells_libs.split(","):
+            g, path = item.split("=", 1)
+            _lib._screencells, _lib.SCREENCELLS_SO_PATH = None, os.path.abspath(path)
+            libs[int(g)] = _lib.load_screencells()
+            assert libs[int(g)].pre_screencells_sample_group() == int(g), item
+    else:
+        libs[screen.sample_group()] = _lib.load_screencells()
+
+    def fused_with(g):
+        def fused():
+            _lib._screencells = libs[g]
+            s = screen.ScreenCells(n, NK, dev)
+            s.add_slab(method, v, qc, None, crop=crop)
+            return s
+        return fused
+
+    def curve():                                             # (A)
+        residual_into(out)
+        cov = pipeline.CoverageLevels(n, NK, dev)
+        cov.add_slab(out[reg], qc[(slice(None),) + reg[1:]])
+        return cov
+
+    def trick():                                             # (B)
+        outs = []
+        for k in range(NK):
+            s = screen.Screen(n, 1, dev)
+            s.add_slab(method, v, one, qc[k], crop=crop)
+            outs.append(s)
+        return outs
+
+    def joint():                                             # (C)
+        s = screen.Screen(n, NK, dev)
+        s.add_slab(method, v, qs, None, crop=crop)
+        return s
+
+    fns = {"fused_G%d" % g: fused_with(g) for g in sorted(libs)}
+    got = {k: f().finish() for k, f in fns.items()}
+    route = screen.last_route()
+    first = got[next(iter(got))]
+    cov = curve()
+    tr = trick()
+    torch.cuda.synchronize()
+    totals = first.inside.sum(dim=1)
+    line = {"case": name, "shape": list(v.shape), "nk": NK, "route": route, "sample_groups": sorted(libs),
+            "every_G_bit_identical": all(torch.equal(o.inside, first.inside) and
+                                         torch.equal(o.score.view(torch.int32), first.score.view(torch.int32)) for o in got.values()),
+            "totals_equal_to_coverage_levels": bool(torch.equal(totals, cov.acc.to(totals.dtype))),
+            "counts_equal_to_one_level_trick": bool(torch.equal(first.inside, torch.cat([t.finish().inside for t in tr]))),
+            "coverage_curve": [round(float(c), 4) for c in first.coverage_marginal()]}
+    fns.update({"curve_A": curve, "trick_B": trick, "joint_C": joint})
+    if args.only == "fused":
+        pick = [k for k in fns if k.startswith("fused_G")]
+    elif args.only is not None:
+        raise SystemExit("--only fused is the one single-route run of the per-cell cases")
+    else:
+        pick = list(fns)
+    res = blocks_of([fns[k] for k in pick], args.reps, args.blocks, args.warmup)
+    cells = 1
+    for d in shape:
+        cells *= d
+    line.update({"cells": cells, "field_bytes_per_cell": fbytes, "level_bytes_per_cell": 4 * NK})
+    for k, (med, lo, hi) in zip(pick, res):
+        line[k + "_ms"] = round(med, 4)
+        line[k + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
+        if k.startswith("fused_G"):
+            # bytes per cell over time: the fields alone (levels from L2), and with the level fields read once per sample
+            line[k + "_fraction_of_8TBps_fields"] = round(cells * fbytes / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+            line[k + "_fraction_of_8TBps_fields_and_levels"] = round(cells * (fbytes + 4 * NK) / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
@@ -271,9 +379,20 @@ def main():
     ap.add_argument("--only", choices=["fused", "three", "residual", "parent", "composed"], default=None,
                     help="run one route alone (for a profiler)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--cells-libs", default=None,
+                    help="per-cell cases: G=path,... of libcp_pre_screencells.so builds to time as (F) (default: the package's)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in args.cases.split(","):
+        if name in CELLS_CASES:
+            path = args.out or os.path.join(ROOT, "profiles", "screencells", "screen_bench_cells.jsonl")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            txt = json.dumps(run_cells(name, args, dev))
+            print(txt, flush=True)
+            with open(path, "a") as f:
+                f.write(txt + "\n")
+            torch.cuda.empty_cache()
+            continue
         pair = name in PAIR_CASES
         folder = "screen1dpair" if name in PAIR1D_CASES else "screenpair" if pair else "screen"
         path = args.out or os.path.join(ROOT, "profiles", folder,
