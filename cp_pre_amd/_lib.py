@@ -365,6 +365,30 @@ SCREEN1DPAIR_SIGNATURES = {
     "pre_screen1dpair_burgers_f32": _sets1 + SCREEN1D_SIGNATURES["pre_screen1d_burgers_f32"][2:],
 }
 
+# libcp_pre_screen1dcells.so (include/cp_pre_screen1dcells.h): the 1-D screens (one field set, and the pair a / b) against
+# per-cell sets: each entry takes its joint twin's arguments with nk level fields in place of the nk levels
+SCREEN1DCELLS_SO_PATH = os.path.join(_HERE, "libcp_pre_screen1dcells.so")
+PRE_SCREEN1DCELLS_ABI_VERSION = 1
+
+
+class PreScreen1dCells(ctypes.Structure):
+    """``pre_screen1dcells_t``: ``pre_screen_t`` as the 1-D screens read it, with nk level fields [Nt,Nx] (level, Nt and Nx
+    strides) in place of ``q``."""
+    _fields_ = [("levels", c_void_p), ("nk", c_int), ("lK", c_int64), ("lT", c_int64), ("lX", c_int64),
+                ("modulation", c_void_p), ("mT", c_int64), ("mX", c_int64), ("ct", c_int), ("cx", c_int),
+                ("score", c_void_p), ("count", c_void_p), ("count_ld", c_int64)]
+
+
+_scr1c = [POINTER(PreScreen1dCells)] + _scr1[1:]                        # s, B, T, X, flags, stream
+SCREEN1DCELLS_SIGNATURES = {
+    "pre_screen1dcells_abi_version": [],
+    "pre_screen1dcells_sample_group": [],
+    "pre_screen1dcells_stencil2d_f32": SCREEN1D_SIGNATURES["pre_screen1d_stencil2d_f32"][:-len(_scr1)] + _scr1c,
+    "pre_screen1dcells_burgers_f32": SCREEN1D_SIGNATURES["pre_screen1d_burgers_f32"][:-len(_scr1)] + _scr1c,
+    "pre_screen1dcells_pair_stencil2d_f32": SCREEN1DPAIR_SIGNATURES["pre_screen1dpair_stencil2d_f32"][:-len(_scr1)] + _scr1c,
+    "pre_screen1dcells_pair_burgers_f32": SCREEN1DPAIR_SIGNATURES["pre_screen1dpair_burgers_f32"][:-len(_scr1)] + _scr1c,
+}
+
 # libcp_pre_vjpflatmhd.so (include/cp_pre_vjpflatmhd.h): the entries of libcp_pre_vjpmhd.so for Nt-fastest views (the march of
 # libcp_pre_vjpflat.so), argument for argument
 VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
@@ -415,8 +439,9 @@ _LIBS_MORE = {
     "screenpair": ("_screenpair", "SCREENPAIR_", "pre_screenpair_abi_version", "PRE_SCREENPAIR_ABI_VERSION", ()),
     "screen1dpair": ("_screen1dpair", "SCREEN1DPAIR_", "pre_screen1dpair_abi_version", "PRE_SCREEN1DPAIR_ABI_VERSION", ()),
     "screencells": ("_screencells", "SCREENCELLS_", "pre_screencells_abi_version", "PRE_SCREENCELLS_ABI_VERSION", ()),
+    "screen1dcells": ("_screen1dcells", "SCREEN1DCELLS_", "pre_screen1dcells_abi_version", "PRE_SCREEN1DCELLS_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -537,6 +562,10 @@ def load_screen1dpair():
 
 def load_screencells():
     return _screencells or _load("screencells")
+
+
+def load_screen1dcells():
+    return _screen1dcells or _load("screen1dcells")
 
 
 def require_gpu():

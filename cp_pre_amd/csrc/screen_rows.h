@@ -40,6 +40,22 @@
 // the sample the slowest index (as screen_march_kernel: the XCDs walk different samples through the same rows).
 //
 // The buffer descriptors carry no record limit: every load of every set is guarded by the lane's `inb` and the row range.
+//
+// PER-CELL SETS (screen_rows_cells.hip, libcp_pre_screen1dcells.so): the kernel takes screen_plane.h's sets policy as the two
+// 2-D marches do.  ScalarSets (the default) is everything above.  Under CellSets g.q is nk level FIELDS [R,C] shared by all
+// samples (level stride sets.qK, row stride sets.qT, unit stride on C) and three things change, nothing else:
+//   sets    a lane with a counted cell loads the quads of levels [0, LB) of row r (load_lev, as load_mod loads the modulation
+//           quad: one wave-uniform descriptor per level and row, no record limit, guarded by `anykeep` and the counted row
+//           range) as the FIRST loads of the row's step, ahead of the edge of r+1, the own quads of r+2 and the modulation
+//           of r+1: vmcnt retires in issue order, so the wait for the level quads after the functor leaves those in flight.
+//           LB = CellsBatch<Fn>: 16 unless the functor leaves no room; then later batches are fetched after the functor;
+//   row     screen_plane_score + screen_plane_count<LB>: hw = ql[k][j] * m[j] in place of qk[k] * m[j];
+//   order   the sample of a group of ROWS_CELLS_G is the fastest logical block index, then the column tile, the chunk, the
+//           group: the workgroups an XCD runs together (xcd_remap makes them contiguous) are ROWS_CELLS_G samples at ONE
+//           (chunk, tile) and read the same level quads from its L2.  nk = 10 level fields of a [200,512] plane are 4 MB, an
+//           XCD's whole L2, against 0.4 MB of one sample's field: with the sample slowest every sample would drag 40 B of
+//           levels per cell across the fabric against 4 B of field.  The grid covers whole groups; the surplus workgroups of
+//           a partial last group return as a whole before the combine barrier.  rows_split does not know of it.
 #pragma once
 #include "screen_plane.h"
 
@@ -48,13 +64,20 @@ namespace {
 constexpr int ROWS_NW = 4;                   // waves per workgroup
 constexpr int ROWS_MINSEG = 8;               // fewest rows per wave segment the split goes down to
 constexpr int ROWS_MAXSETS = 2;              // field sets a march reads: 1, or the truth and the prediction
+// per-cell sets: the samples of a group, the fastest index of the block order (1: the order of the joint screens); a build
+// constant of libcp_pre_screen1dcells.so, speed only
+#ifndef PRE_SCREEN1DCELLS_GROUP
+#define PRE_SCREEN1DCELLS_GROUP 16
+#endif
+constexpr int ROWS_CELLS_G = PRE_SCREEN1DCELLS_GROUP;
+static_assert(ROWS_CELLS_G >= 1, "a group has at least one sample");
 
 struct RGeom {
     const float *f[ROWS_MAXSETS];
     long long sB[ROWS_MAXSETS], sR[ROWS_MAXSETS];   // sample and row strides of each set (elements); columns have unit stride
     const float *mod;            // nullptr: m == 1
     long long mR;
-    const float *q;              // device, nk levels
+    const float *q;              // device, nk levels (per-cell sets: nk level fields [R,C], strides in CellSets)
     unsigned int *score;         // [B]
     unsigned int *count;         // [nk][cld]
     long long cld;
@@ -80,11 +103,41 @@ RSplit rows_split(long long B, int R, int C, long long slots)
     return s;
 }
 
+// What the march evaluates per row: Fn::eval, except where the four unrolled row steps of the march would not round alike.
+// Under fma contraction the compiler is free to fuse either product of a sum of two products, and for Burgers<3> (Nt-fastest,
+// reference taps) it fused dx * D_t(u) + (dt * u) * D_x(u) as fma(dx, D_t, fl((dt u) D_x)) in the first step and as
+// fma(dt u, D_x, fl(dx D_t)) in the other three: r of a row then depended, by 1-2 ulp, on the row's place in its wave's
+// segment, and row slabs did not compose to the bits of the whole plane.  The specialisation states the order of the last
+// three operations - the first form, which every step of Burgers<0> and Burgers<2> has - and leaves the stencil sums, which
+// every step fused alike, to apply<>.  Registers, LDS and occupancy stay what they were.  Every other instantiation built
+// rounds its four steps alike (read in the code objects).
 template <class Fn>
+struct RowsFn {
+    static __device__ __forceinline__ float4 eval(const Nbr (&n)[Fn::F], const typename Fn::Params &p) { return Fn::eval(n, p); }
+};
+template <>
+struct RowsFn<Burgers<3>> {
+    static __device__ __forceinline__ float4 eval(const Nbr (&n)[1], const BurgersParams &p)
+    {
+#pragma clang fp contract(off)
+        typedef float f32x2 __attribute__((ext_vector_type(2)));     // (a pair per operation: the packed fma of the other modes)
+        const Nbr &u = n[0];
+        const float4 dt = apply<K_Y3>(p.Dt, u), a = (p.dt * u.c) * apply<K_X3>(p.Dx, u), t = p.nu * apply<K_X3>(p.Dxx, u);
+        const f32x2 dx = {p.dx, p.dx}, c3 = {p.c3, p.c3};
+        // r = fma(-fl(nu D_xx), c3, fma(dx, D_t, fl(fl(dt u) D_x)))
+        const f32x2 lo = __builtin_elementwise_fma(-f32x2{t.x, t.y}, c3, __builtin_elementwise_fma(dx, f32x2{dt.x, dt.y}, f32x2{a.x, a.y}));
+        const f32x2 hi = __builtin_elementwise_fma(-f32x2{t.z, t.w}, c3, __builtin_elementwise_fma(dx, f32x2{dt.z, dt.w}, f32x2{a.z, a.w}));
+        return make_float4(lo.x, lo.y, hi.x, hi.y);
+    }
+};
+
+template <class Fn, class Sets = ScalarSets>
 __global__ void __launch_bounds__(64 * ROWS_NW)
-screen_rows_kernel(const RGeom g, const typename Fn::Params prm)
+screen_rows_kernel(const RGeom g, const typename Fn::Params prm, const Sets sets)
 {
     constexpr int NS = Fn::F;                      // field sets
+    constexpr bool CELLS = Sets::CELLS;
+    constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held at once)
     static_assert(NS >= 1 && NS <= ROWS_MAXSETS, "one field per set, one or two sets");
     static_assert(64 * ROWS_NW >= NKMAX + 1, "one thread per result in the combine step");
     __shared__ unsigned int red[NKMAX + 1][ROWS_NW];
@@ -92,9 +145,14 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    // per-cell sets: the sample of a group the fastest index; the last group is partial when B % ROWS_CELLS_G != 0
+    const int bl = CELLS ? L % ROWS_CELLS_G : 0;
+    if constexpr (CELLS) L /= ROWS_CELLS_G;
     const int ct = L % g.nCT; L /= g.nCT;
     const int ch = L % g.nChunk;
-    const int b = L / g.nChunk;
+    const int b = CELLS ? (L / g.nChunk) * ROWS_CELLS_G + bl : L / g.nChunk;
+    if constexpr (CELLS)
+        if (b >= g.B) return;                      // (workgroup-uniform: no such sample in the last group; before the barrier)
 
     // this wave's strip and the rows it evaluates: its segment, cut to the chunk and to the counted rows
     const int strip = ct * g.ws + wv % g.ws;
@@ -107,11 +165,12 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm)
                           inb && y + 2 >= g.cc && y + 2 < g.C - g.cc, inb && y + 3 >= g.cc && y + 3 < g.C - g.cc};
     const bool anykeep = keep[0] || keep[1] || keep[2] || keep[3];
 
-    float qk[NKMAX];
+    [[maybe_unused]] float qk[NKMAX];              // (per-cell sets: a quad per level and row, load_lev)
     unsigned int cnt[NKMAX];
 #pragma unroll
     for (int k = 0; k < NKMAX; ++k) {
-        qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
+        if constexpr (CELLS) qk[k] = 0.f;
+        else qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
         cnt[k] = 0;
     }
     float smax = 0.f, sthr = 0.f;
@@ -160,10 +219,31 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm)
             }
         };
 
+        // per-cell sets: the quads of levels [k0, k0 + LB) at row r, loaded like the modulation - only by lanes with a counted
+        // cell and only for counted rows; a rim cell of a level field shares its quad with counted ones and is masked
+        [[maybe_unused]] float4 ql[CELLS ? LB : 1];
+        [[maybe_unused]] auto load_lev = [&](int r, int k0) __attribute__((always_inline)) {
+            if constexpr (CELLS) {
+#pragma unroll
+                for (int k = 0; k < LB; ++k) {
+                    if (anykeep && r < r1 && k0 + k < g.nk) {
+                        const float *p = g.q + ((long long)(k0 + k) * sets.qK + (long long)r * sets.qT);
+                        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
+                            __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, -1, 0x00020000), voff, 0, 0);
+                        ql[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+                    } else {
+                        ql[k] = f4(0.f);
+                    }
+                }
+            }
+        };
+
         // One row.  P,C,N hold rows r-1,r,r+1 of the own quad of every set; D receives row r+2; ec / mc are the edge scalars
         // and the modulation of row r, en / mn receive those of row r+1.  The caller rotates the roles.
         auto step = [&](int r, float4 (&P)[NS], float4 (&C)[NS], float4 (&N)[NS], float4 (&D)[NS], float (&ec)[NS],
                         float (&en)[NS], float4 &mc, float4 &mn) __attribute__((always_inline)) {
+            // per-cell sets: this row's first LB level quads go out BEFORE the field loads below (vmcnt retires in issue order)
+            load_lev(r, 0);
             load_edge(r + 1, en);
             load_own(r + 2, D);
             load_mod(r + 1, mn);
@@ -181,8 +261,19 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm)
                 n[s].ym = make_float4(lft, C[s].x, C[s].y, C[s].z);
                 n[s].yp = make_float4(C[s].y, C[s].z, C[s].w, rgt);
             }
-            const float4 res = Fn::eval(n, prm);
-            screen_plane(res, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+            const float4 res = RowsFn<Fn>::eval(n, prm);
+            if constexpr (!CELLS) {
+                screen_plane(res, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
+            } else {
+                float ac[4], sv[4];
+                screen_plane_score(res, mc, keep, ac, sv, smax, sthr, snan);
+#pragma unroll
+                for (int k0 = 0; k0 < NKMAX; k0 += LB) {
+                    if (k0 >= g.nk) break;                     // (wave-uniform)
+                    if (k0 > 0) load_lev(r, k0);
+                    screen_plane_count<LB>(ac, sv, k0, g.nk, ql, cnt);
+                }
+            }
         };
 
         float4 w0[NS], w1[NS], w2[NS], w3[NS], m0, m1;
@@ -227,15 +318,17 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm)
 }
 
 // ------------------------------------------------------------------ host side
-template <class Fn>
-int launch_rows(RGeom &g, const typename Fn::Params &prm, hipStream_t st)
+template <class Fn, class Sets = ScalarSets>
+int launch_rows(RGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets = Sets())
 {
-    static const int per_cu = resident_per_cu(screen_rows_kernel<Fn>, 64 * ROWS_NW);
+    static const int per_cu = resident_per_cu(screen_rows_kernel<Fn, Sets>, 64 * ROWS_NW);
     const RSplit s = rows_split(g.B, g.R, g.C, (long long)per_cu * chip_cus());
     g.ws = s.ws; g.nCT = s.nCT; g.rc = s.rc; g.nChunk = s.nChunk; g.rSeg = s.rSeg;
-    const long long wgs = (long long)g.B * g.nChunk * g.nCT;
+    long long nb = g.B;                        // samples the grid covers: per-cell sets, whole groups of ROWS_CELLS_G
+    if constexpr (Sets::CELLS) nb = (nb + ROWS_CELLS_G - 1) / ROWS_CELLS_G * ROWS_CELLS_G;
+    const long long wgs = nb * g.nChunk * g.nCT;
     if (wgs <= 0 || wgs * 64 * ROWS_NW > 0xffffffffLL) return PRE_E_SHAPE;      // the dispatch packet counts work-items in 32 bits
-    hipLaunchKernelGGL((screen_rows_kernel<Fn>), dim3((unsigned)wgs), dim3(64 * ROWS_NW), 0, st, g, prm);
+    hipLaunchKernelGGL((screen_rows_kernel<Fn, Sets>), dim3((unsigned)wgs), dim3(64 * ROWS_NW), 0, st, g, prm, sets);
     PRE_LAUNCH_CHECK();
     return PRE_OK;
 }

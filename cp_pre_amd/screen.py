@@ -87,15 +87,32 @@ cell at ten alphas, and each is checked against the residual of every held-out p
 ``include/cp_pre_screencells.h``): both marches above with nk level quads per cell and plane next to the field loads, the
 samples taken in groups (``sample_group()``) so that a group shares its level quads in an XCD's L2.  ``inside[k, b]`` counts
 ``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with one): ``emp_cov_levels``'s count with per-cell levels, per sample.
-Routes ``fused:cells_<kind>`` / ``fused:flat_cells_<kind>`` for the kinds of the first paragraph; the 1-D family, JOREK,
-``minus=`` and every reason above keep the three-pass route (one ``CoverageLevels`` pass per sample with the per-cell
-levels).  Without a call to these two the library is never loaded.
+Routes ``fused:cells_<kind>`` / ``fused:flat_cells_<kind>`` for the kinds of the first paragraph; the 1-D family (without
+``rows=True``, below), JOREK, ``minus=`` and every reason above keep the three-pass route (one ``CoverageLevels`` pass per
+sample with the per-cell levels).  Without a call to these two the library is never loaded.
+
+The 1-D family has per-cell screens as well, asked for by ``rows=True`` on ``screen_cells`` / ``ScreenCells.add_slab``
+(``Active_Learning/Advection_AL_Marginal.py:169-198, 290-311`` keeps or rejects every candidate by ``within(threshold)`` on
+per-cell sets; ``Marginal/Burgers_Residuals_CP.py:274-283`` and ``Marginal/Advection_Residuals_CP.py`` check ``±qhat[cell]``
+at ten alphas; ``libcp_pre_screen1dcells.so``, ``include/cp_pre_screen1dcells.h``: the row march of the rows route with nk
+level quads per cell and row, the samples in groups of ``sample_group_rows()``).  ``vars`` is ``[BS,Nt,Nx]`` in either layout,
+``qcells`` fp32 ``[nk,Nt,Nx]`` (with ``boundary=False`` also the cropped ``[nk,Nt-2,Nx-2]``, padded once with NaN in the
+fields' layout); levels and a modulation whose unit-stride axis is not the fields' are copied once.  Routes
+``fused:rows_cells_stencil2d`` / ``fused:rows_cells_burgers``.  With ``minus=`` the paired entries run - the data-driven form
+``|r(vars) - r(minus)| <= qcells[k][cell] (* m)`` of ``Marginal/Burgers_Residuals_CP.py:249-259``, the one-sided test of the
+paragraphs above - with routes ``fused:rows_cells_pair_stencil2d`` / ``fused:rows_cells_pair_burgers``; both sets in the same
+layout, each with its own pitches.  The reasons that keep the three-pass route are ``prepare_rows``', in its order (CPU
+inputs, float64 levels, a ``[BS,1,Nt,Nx]`` input, no unit-stride axis, a contiguous axis that is no multiple of 4, sets in
+different layouts, kernels off the star or requiring grad, ``declined by the library``); ``halo_x`` raises.  Row slabs with
+crops compose to the bits of the whole plane.  Without ``rows=True`` the family keeps ``fallback:1-D family: the marched
+axis is the batch`` and the library is never loaded; on a method outside the family the keyword has no effect.
 
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
 ``_method.Method`` (shared with ``losses``); ``_Spec`` adds the kinds that have a fused screen, the order of the reasons of
-``prepare`` / ``prepare_flat`` / ``prepare_rows`` and ONE launcher for the three libraries (``launch``, by ``form``).
+``prepare`` / ``prepare_flat`` / ``prepare_rows`` and ONE launcher for all the libraries (``launch``, by ``form``, ``minus``
+and ``cells``).
 """
 from __future__ import annotations
 
@@ -186,6 +203,9 @@ _PAIR_ENTRY = {"": "pre_screenpair_", "flat": "pre_screenpair_flat_"}
 _CELLS_ENTRY = {"": "pre_screencells_", "flat": "pre_screencells_flat_"}
 # the paired screen of the 1-D family (opt-in, ``pair="rows"`` with ``minus=``), one more library: the prefix of its entries
 _PAIR_ROWS_ENTRY = "pre_screen1dpair_"
+# the per-cell screens of the 1-D family (opt-in, ``rows=True`` of ``screen_cells`` / ``ScreenCells``; with ``minus=`` its
+# paired entries), one more library: the prefix of its entries
+_CELLS_ROWS_ENTRY = "pre_screen1dcells_"
 
 
 def _pair_mode(pair, minus):
@@ -345,7 +365,9 @@ class _Spec(Method):
     # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
     def entry(self, form, pair=False, cells=False):
         """The entry point of this method's fused screen in the library of ``form`` (``pair``: of its paired screen,
-        ``cells``: of its per-cell screen)."""
+        ``cells``: of its per-cell screen; form 'rows' has both at once)."""
+        if cells and form == "rows":
+            return _CELLS_ROWS_ENTRY + ("pair_" if pair else "") + self.rows_kind + "_f32"
         if cells:
             return _CELLS_ENTRY[form] + ("mhd" if self.kind in _MHD_EQ else self.kind) + "_f32"
         if pair:
@@ -356,6 +378,8 @@ class _Spec(Method):
         return _FORMS[form][1] + kind + "_f32"
 
     def route(self, form, pair=False, cells=False):
+        if cells and form == "rows":
+            return "fused:rows_cells_" + ("pair_" if pair else "") + self.rows_kind
         if cells:
             return "fused:" + _FORMS[form][2] + "cells_" + self.kind
         return "fused:" + _FORMS[form][2] + ("pair_" if pair else "") + (self.rows_kind if form == "rows" else self.kind)
@@ -363,14 +387,14 @@ class _Spec(Method):
     def launch(self, kernels, x, st, flags, form="", minus=None, cells=False):
         """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code.
         ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so`` for forms '' and 'flat',
-        ``libcp_pre_screen1dpair.so`` for 'rows').  ``cells``: the per-cell screen (``libcp_pre_screencells.so``, forms ''
-        and 'flat'; ``st`` is then its set descriptor)."""
+        ``libcp_pre_screen1dpair.so`` for 'rows').  ``cells``: the per-cell screen (``libcp_pre_screencells.so`` for forms ''
+        and 'flat', ``libcp_pre_screen1dcells.so`` for 'rows', there with ``minus`` too; ``st`` is then its set descriptor)."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
         if minus is not None and form == "rows":
             sets = (_lib.ptr(x), _lib.iarr64(x.stride()), _lib.ptr(minus), _lib.iarr64(minus.stride()))
             if self.rows_kind.startswith("stencil"):
                 kernels = _dispatch.tap_args(*kernels)
-            fn = getattr(_lib.load_screen1dpair(), self.entry(form, True))
+            fn = getattr(_lib.load_screen1dcells() if cells else _lib.load_screen1dpair(), self.entry(form, True, cells))
             return fn(*sets, *kernels, *self.scalars(), ctypes.byref(st), *x.shape, flags, _lib.stream())
         if minus is not None:
             fa, fb = self.fields(x), self.fields(minus)
@@ -381,7 +405,10 @@ class _Spec(Method):
             fn = getattr(_lib.load_screenpair(), self.entry(form, True))
             return fn(*views, *kernels, *self.scalars(), ctypes.byref(st), *fa[0].shape, flags, _lib.stream())
         kind = self.rows_kind if form == "rows" else self.kind
-        lib = _lib.load_screencells() if cells else getattr(_lib, "load_screenjorek" if kind in _JOREK_EQ else _FORMS[form][0])()
+        if cells and form == "rows":
+            lib = _lib.load_screen1dcells()
+        else:
+            lib = _lib.load_screencells() if cells else getattr(_lib, "load_screenjorek" if kind in _JOREK_EQ else _FORMS[form][0])()
         if form == "rows":
             views, shape = (_lib.ptr(x), _lib.iarr64(x.stride())), x.shape
         else:
@@ -624,6 +651,12 @@ def sample_group():
     return int(_lib.load_screencells().pre_screencells_sample_group())
 
 
+def sample_group_rows():
+    """Samples per group in the block order of the per-cell screens of the 1-D family
+    (``pre_screen1dcells_sample_group``): speed only."""
+    return int(_lib.load_screen1dcells().pre_screen1dcells_sample_group())
+
+
 def _check_cells(spec, vars, qcells, modulation, minus, crop, nk=None):
     """``_check_inputs`` for level fields: every error before any device work.  Returns (uncropped residual shape, crop,
     counted cells per sample); ``qcells`` has the uncropped extents or (``cropped`` in the caller) the cropped ones."""
@@ -642,13 +675,18 @@ class ScreenCells(Screen):
     """``Screen`` against per-cell sets: ``add_slab`` takes the level fields of the slab in place of the nk levels.
     Accumulation, ``crop``, ``halo_x`` and ``finish`` are ``Screen``'s: slabs compose to the bits of the whole grid."""
 
-    def add_slab(self, method, vars_slab, qcells_slab, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None):
+    def add_slab(self, method, vars_slab, qcells_slab, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None,
+                 rows=False):
         """``qcells_slab``: fp32 [nk, *uncropped residual extents of the slab] on the slab's device, shared by all samples
         (its values outside the counted region are never used); the other arguments as ``Screen.add_slab`` takes them.
         Level fields whose unit-stride axis is not the fields' are copied once into the matching layout, as the
-        modulation is.  ``minus`` keeps the three-pass route (``fallback:minus=``)."""
+        modulation is.  ``minus`` keeps the three-pass route (``fallback:minus=``).  ``rows=True``: the opt-in per-cell
+        screen of the 1-D family (``crop`` of two axes; with ``minus`` its paired entries; module docstring); no effect on
+        any other method."""
         global _last_route
         spec = method if isinstance(method, _Spec) else _Spec(method)
+        rows = bool(rows) and spec.rows_kind is not None
+        pair = "rows" if rows and minus is not None else False  # (the paired entries of the rows form take ``minus``)
         shape, crop, cells = _check_cells(spec, vars_slab, qcells_slab, modulation_slab, minus, crop, self.nk)
         if tuple(qcells_slab.shape[1:]) != tuple(shape[1:]):
             raise ValueError(f"qcells has shape {tuple(qcells_slab.shape)}, expected {(self.nk,) + tuple(shape[1:])}: the "
@@ -662,13 +700,24 @@ class ScreenCells(Screen):
             raise ValueError("halo_x needs a device-resident view of a larger grid (a staged copy has no halo rows)")
         if halo_x and why is not None and not spec.reads_halo():
             raise RuntimeError(f"halo_x: the fused screen cannot run ({why}) and no other pass of this method reads the halo rows")
+        if rows:                                              # (the 1-D family: halo_x has raised above)
+            why, kernels = spec.prepare_rows(vars_slab, minus, qcells_slab, modulation_slab, pair)
         flat = spec.kind is not None and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
         if flat:
             why, kernels = spec.prepare_flat(vars_slab, minus, qcells_slab, modulation_slab)
         if why is None:
             acc = self._buffers(vars_slab.device)
             mod, lev = modulation_slab, qcells_slab
-            if flat:
+            if rows:
+                nt_fast = vars_slab.stride(2) != 1            # the unit-stride axis of modulation and levels must be the field's
+                if mod is not None and mod.stride(0 if nt_fast else 1) != 1:
+                    mod = mod.t().contiguous().t() if nt_fast else mod.contiguous()
+                if lev.stride(1 if nt_fast else 2) != 1:      # (nk of them, memory [nk,Nx,Nt] for Nt-fastest fields)
+                    lev = lev.transpose(1, 2).contiguous().transpose(1, 2) if nt_fast else lev.contiguous()
+                st = _lib.PreScreen1dCells(_lib.ptr(lev), self.nk, *lev.stride(), _lib.ptr(mod),
+                                           *(mod.stride() if mod is not None else (0, 0)), crop[0], crop[1],
+                                           ctypes.c_void_p(acc[0].data_ptr()), ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
+            elif flat:
                 if mod is not None and (mod.stride(0) != 1 or mod.stride(2) != mod.shape[0]):
                     mod = mod.permute(1, 2, 0).contiguous().permute(2, 0, 1)       # (one sample-sized copy, memory [X,Y,T])
                 if lev.stride(1) != 1 or lev.stride(3) != lev.shape[1]:
@@ -685,16 +734,17 @@ class ScreenCells(Screen):
                                          mod.stride(0) if mod is not None else 0, mod.stride(1) if mod is not None else 0,
                                          crop[0], crop[1], crop[2], ctypes.c_void_p(acc[0].data_ptr()),
                                          ctypes.c_void_p(acc[1].data_ptr()), acc.stride(0))
-            form = "flat" if flat else ""
+            form = "rows" if rows else "flat" if flat else ""
             with torch.no_grad(), torch.cuda.device(vars_slab.device):
-                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0, form, cells=True)
+                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x else 0, form,
+                                 minus if pair else None, cells=True)
             if rc == _lib.PRE_E_UNSUPPORTED:
                 why = "declined by the library"
                 if halo_x and not spec.reads_halo():
                     raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
             else:
-                _lib.check(rc, spec.entry(form, cells=True))
-                _last_route = spec.route(form, cells=True)
+                _lib.check(rc, spec.entry(form, bool(pair), cells=True))
+                _last_route = spec.route(form, bool(pair), cells=True)
                 self.cells += cells
                 return
         _last_route = "fallback:" + why
@@ -702,7 +752,7 @@ class ScreenCells(Screen):
         self.cells += cells
 
 
-def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False, minus=None):
+def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False, minus=None, rows=False):
     """Screen the predictions ``vars`` against the per-cell sets ``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with a
     modulation) at every level k in one launch; the residual is never stored.  ``qcells``: fp32 ``[nk, *uncropped residual
     extents]`` on ``vars``' device, 1 <= nk <= 16.  ``boundary=False``: the counted cells are the interior ``[1:-1]`` of
@@ -710,7 +760,11 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
     taken from ``res[..., 1:-1, 1:-1, 1:-1]``; it is then padded once with NaN to the uncropped extents (one copy of nk
     sample-sized fields, in the fields' layout).  ``boundary=True``: every cell, uncropped extents only.  Inside the counted
     region a NaN level or a NaN residual puts the cell outside at that level, a negative level puts it outside, ``+inf``
-    puts it inside for every non-NaN residual.  ``minus`` (the data-driven score) keeps the three-pass route.  Returns a
+    puts it inside for every non-NaN residual.  ``minus`` (the data-driven score) keeps the three-pass route.
+    ``rows=True``: the opt-in per-cell screen of the 1-D family (``vars`` [BS,Nt,Nx] in either layout, ``qcells``
+    [nk,Nt,Nx] or the cropped [nk,Nt-2,Nx-2]; routes ``fused:rows_cells_<kind>``); ``minus`` with it takes the paired
+    entries, the one-sided test ``|r(vars) - r(minus)| <= qcells[k][cell] (* m)`` (``fused:rows_cells_pair_<kind>``).
+    Without it the 1-D family keeps the three-pass route; on any other method it has no effect.  Returns a
     :class:`Screened`: ``inside``, ``accept()``, ``coverage_marginal(group=)``, ``within()`` and ``score`` as for
     ``screen``; the samples may be sharded by the batch axis with nothing exchanged.
 
@@ -718,7 +772,10 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
     with per-cell levels (``emp_cov_levels``) - 3.8 against 2.6 ms for the wave residual on [512,32,256,256], 69 against 34 ms
     for NS momentum on Nt-fastest [512,3,64,512,512].  That route gives the totals of the coverage curve only; who needs
     nothing else should keep it.  This one gives per-sample counts - ``accept``, ``within``, the score - stores no residual,
-    takes slabs, and is 4-6 times faster than ten calls of the one-level trick, the other way to the same answer."""
+    takes slabs, and is 4-6 times faster than ten calls of the one-level trick, the other way to the same answer.
+    The same holds for ``rows=True`` (Burgers on [8192,200,512], nk = 10): SLOWER than that route - 2.56
+    against 2.06 ms Nx-fastest, 3.34 against 2.25 ms Nt-fastest, 4.63 against 3.07 ms for a pair - and 4.4-4.9 times faster
+    than ten one-level calls of the joint rows screen."""
     spec = _Spec(residual_method)
     crop = (0,) * spec.nd if boundary else (1,) * spec.nd
     shape, _, _ = _check_cells(spec, vars, qcells, modulation, minus, crop)
@@ -727,9 +784,10 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
         if boundary or tuple(qcells.shape[1:]) != cropped:
             raise ValueError(f"qcells has shape {tuple(qcells.shape)}, expected [nk, *{full}]" +
                              ("" if boundary else f" or the cropped [nk, *{cropped}]"))
-        qcells = _pad_levels(qcells, full, vars.is_cuda and spec.nt_fastest(vars))
+        rows_nt = bool(rows) and spec.rows_kind is not None and vars.dim() == 3 and vars.stride(2) != 1 and vars.stride(1) == 1
+        qcells = _pad_levels(qcells, full, vars.is_cuda and (rows_nt or spec.nt_fastest(vars)))
     s = ScreenCells(shape[0], qcells.shape[0], vars.device)
-    s.add_slab(spec, vars, qcells, modulation, crop=crop, minus=minus)
+    s.add_slab(spec, vars, qcells, modulation, crop=crop, minus=minus, rows=rows)
     out = s.finish()
     if not vars.is_cuda:                                     # (staged inputs: the verdicts come home, as elsewhere)
         out.score, out.inside = out.score.to(vars.device), out.inside.to(vars.device)
@@ -738,9 +796,12 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
 
 def _pad_levels(qcells, full, nt_fastest):
     """Cropped level fields [nk, *cropped] inside NaN fields of the uncropped extents ``full`` (a NaN level is outside:
-    the rim is never counted anyway); ``nt_fastest``: memory [nk,X,Y,T], the layout of an Nt-fastest view's fields."""
+    the rim is never counted anyway); ``nt_fastest``: memory [nk,X,Y,T], the layout of an Nt-fastest view's fields (for the
+    1-D family's [Nt,Nx] extents: memory [nk,Nx,Nt])."""
     nk = qcells.shape[0]
-    if nt_fastest and len(full) == 3:
+    if nt_fastest and len(full) == 2:
+        out = torch.full((nk, full[1], full[0]), float("nan"), dtype=qcells.dtype, device=qcells.device).transpose(1, 2)
+    elif nt_fastest and len(full) == 3:
         out = torch.full((nk, full[1], full[2], full[0]), float("nan"), dtype=qcells.dtype, device=qcells.device).permute(0, 3, 1, 2)
     else:
         out = torch.full((nk,) + tuple(full), float("nan"), dtype=qcells.dtype, device=qcells.device)

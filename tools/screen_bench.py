@@ -59,6 +59,19 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                fields at nk scalar levels - the same march without the per-cell reads, the floor.  Lines go to
                profiles/screencells/screen_bench_cells.jsonl unless --out says otherwise
 
+    c5_burgers_cells_nx / c5_burgers_cells_nt / c5_burgers_cells_pair_nt
+               the per-cell screen of the 1-D family (``screen.ScreenCells(...).add_slab(rows=True)``:
+               ``libcp_pre_screen1dcells.so``) at nk = 10 level fields, no modulation: Burgers on [8192,200,512], Nx-fastest
+               and Nt-fastest, and the pair of two such sets, Nt-fastest (the second the first plus noise).  Routes,
+               alternated call by call: (F) the fused launch, once per library of ``--cells1d-libs G=path,...`` (build variants
+               of the sample group, ``make SCREEN1DCELLS_GROUP=G``; default: the package's own library); (B) nk calls of the
+               one-level trick (the level field as the modulation of the joint rows screen), which delivers the same
+               per-sample answer; (A) the residual pass plus ONE marginal ``CoverageLevels`` pass with per-cell levels,
+               totals only; (C) the joint rows screen at nk scalar levels, the floor.  Then, on a batch of its own of
+               ``--parent-batch`` samples (default 64; nothing is scaled), (P) the three-pass route the package takes
+               without ``rows=True`` - one ``CoverageLevels`` pass per sample - next to (F) on that batch.  Lines go to
+               profiles/screen1dcells/screen_bench_cells1d.jsonl unless --out says otherwise
+
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
@@ -369,6 +382,137 @@ def run_cells(name, args, dev):
     return line
 
 
+CELLS1D_CASES = {"c5_burgers_cells_nx": ("c5_burgers_nx", False), "c5_burgers_cells_nt": ("c5_burgers_nt", False),
+                 "c5_burgers_cells_pair_nt": ("c5_burgers_nt", True)}
+
+
+def run_cells1d(name, args, dev):
+    """One per-cell case of the 1-D family: (F) per library, (B), (A), (C) alternated, then (P) on its own small batch; one
+    JSON line."""
+    from cp_pre_amd import _lib
+    base, pair = CELLS1D_CASES[name]
+    method, v, crop, _, _, fbytes = case(base, args.div, dev)
+    n = v.shape[0]
+    nt_fast = v.stride(-1) != 1
+    w = None
+    if pair:                                                 # the second set: the first plus noise, in the same layout
+        w = v + 0.05 * torch.randn(v.shape, device=dev)
+        w = w.transpose(1, 2).contiguous().transpose(1, 2) if nt_fast else w.contiguous()
+        fbytes *= 2
+    kw = {"minus": w} if pair else {}
+    shape = tuple(v.shape)
+    reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
+    # level fields in the fields' layout: level k about (k + 1) / nk of twice the mean |r|, scattered per cell by +-50 %
+    scale = float(method(v[:min(n, 8)], boundary=True, **({"minus": w[:min(n, 8)]} if pair else {})).abs().mean())
+    qc = torch.rand((NK,) + shape[1:], device=dev) + 0.5
+    qc *= (2.0 * scale / NK) * torch.arange(1, NK + 1, device=dev, dtype=torch.float32).reshape(NK, 1, 1)
+    if nt_fast:
+        qc = qc.transpose(1, 2).contiguous().transpose(1, 2)
+    qs = torch.linspace(0.2, 2.0, NK, device=dev) * scale
+    one = torch.ones(1, device=dev)
+    libs = {}
+    if args.cells1d_libs:
+        for item in args.cells1d_libs.split(","):
+            g, path = item.split("=", 1)
+            _lib._screen1dcells, _lib.SCREEN1DCELLS_SO_PATH = None, os.path.abspath(path)
+            libs[int(g)] = _lib.load_screen1dcells()
+            assert libs[int(g)].pre_screen1dcells_sample_group() == int(g), item
+    else:
+        libs[screen.sample_group_rows()] = _lib.load_screen1dcells()
+
+    def fused_with(g):
+        def fused():
+            _lib._screen1dcells = libs[g]
+            s = screen.ScreenCells(n, NK, dev)
+            s.add_slab(method, v, qc, None, crop=crop, rows=True, **kw)
+            return s
+        return fused
+
+    def trick():                                             # (B)
+        outs = []
+        for k in range(NK):
+            s = screen.Screen(n, 1, dev)
+            s.add_slab(method, v, one, qc[k], crop=crop, pair="rows", **kw)
+            outs.append(s)
+        return outs
+
+    def curve():                                             # (A)
+        res = method(v, boundary=True, **kw)
+        cov = pipeline.CoverageLevels(n, NK, dev)
+        cov.add_slab(res[reg], qc[(slice(None),) + reg[1:]])
+        return cov
+
+    def joint():                                             # (C)
+        s = screen.Screen(n, NK, dev)
+        s.add_slab(method, v, qs, None, crop=crop, pair="rows", **kw)
+        return s
+
+    fns = {"fused_G%d" % g: fused_with(g) for g in sorted(libs)}
+    got = {}
+    for k, f in fns.items():
+        got[k] = f().finish()
+        assert screen.last_route().startswith("fused:rows_cells_"), screen.last_route()
+    route = screen.last_route()
+    first = got[next(iter(got))]
+    cov = curve()
+    tr = trick()
+    trick_route = screen.last_route()
+    torch.cuda.synchronize()
+    totals = first.inside.sum(dim=1)
+    line = {"case": name, "shape": list(shape), "sets": 2 if pair else 1, "nk": NK, "route": route, "trick_route": trick_route,
+            "sample_groups": sorted(libs),
+            "every_G_bit_identical": all(torch.equal(o.inside, first.inside) and
+                                         torch.equal(o.score.view(torch.int32), first.score.view(torch.int32)) for o in got.values()),
+            "totals_equal_to_coverage_levels": bool(torch.equal(totals, cov.acc.to(totals.dtype))),
+            "counts_equal_to_one_level_trick": bool(torch.equal(first.inside, torch.cat([t.finish().inside for t in tr]))),
+            "coverage_curve": [round(float(c), 4) for c in first.coverage_marginal()]}
+    fns.update({"trick_B": trick, "curve_A": curve, "joint_C": joint})
+    if args.only == "fused":
+        pick = [k for k in fns if k.startswith("fused_G")]
+    elif args.only is not None:
+        raise SystemExit("--only fused is the one single-route run of the per-cell cases")
+    else:
+        pick = list(fns)
+    res = blocks_of([fns[k] for k in pick], args.reps, args.blocks, args.warmup)
+    cells = 1
+    for d in shape:
+        cells *= d
+    line.update({"cells": cells, "field_bytes_per_cell": fbytes, "level_bytes_per_cell": 4 * NK})
+    for k, (med, lo, hi) in zip(pick, res):
+        line[k + "_ms"] = round(med, 4)
+        line[k + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
+        line[k + "_block_spread"] = round(hi / lo, 4)
+        if k.startswith("fused_G"):
+            line[k + "_fraction_of_8TBps_fields"] = round(cells * fbytes / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+            line[k + "_fraction_of_8TBps_fields_and_levels"] = round(cells * (fbytes + 4 * NK) / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+    if args.only is None and args.parent_batch > 0:
+        # (P) the three-pass route the package takes without rows=True, on a batch of its own: one CoverageLevels pass per
+        # sample.  The figure is of THAT batch; nothing is scaled
+        nb = min(n, args.parent_batch)
+        vb, kb = v[:nb], ({"minus": w[:nb]} if pair else {})
+
+        def parent():
+            s = screen.ScreenCells(nb, NK, dev)
+            s.add_slab(method, vb, qc, None, crop=crop, **kb)
+            return s
+
+        def fused_small():
+            _lib._screen1dcells = libs[max(libs)]
+            s = screen.ScreenCells(nb, NK, dev)
+            s.add_slab(method, vb, qc, None, crop=crop, rows=True, **kb)
+            return s
+        p = parent().finish()
+        line["parent_route"] = screen.last_route()
+        f = fused_small().finish()
+        line["parent_batch"] = nb
+        line["bit_identical_to_parent_route"] = bool(torch.equal(p.inside, f.inside)) and \
+            bool(torch.equal(p.score.view(torch.int32), f.score.view(torch.int32)))
+        (pm, plo, phi), (fm, flo, fhi) = blocks_of([parent, fused_small], 1, 3, 0)
+        line.update({"parent_P_ms_at_parent_batch": round(pm, 4), "parent_P_ms_blocks_min_max": [round(plo, 4), round(phi, 4)],
+                     "fused_ms_at_parent_batch": round(fm, 4), "fused_ms_at_parent_batch_blocks_min_max": [round(flo, 4), round(fhi, 4)]})
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
@@ -381,9 +525,22 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--cells-libs", default=None,
                     help="per-cell cases: G=path,... of libcp_pre_screencells.so builds to time as (F) (default: the package's)")
+    ap.add_argument("--cells1d-libs", default=None,
+                    help="per-cell cases of the 1-D family: G=path,... of libcp_pre_screen1dcells.so builds to time as (F)")
+    ap.add_argument("--parent-batch", type=int, default=64,
+                    help="per-cell cases of the 1-D family: samples of the batch (P), the three-pass route, is timed on (0: not at all)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in args.cases.split(","):
+        if name in CELLS1D_CASES:
+            path = args.out or os.path.join(ROOT, "profiles", "screen1dcells", "screen_bench_cells1d.jsonl")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            txt = json.dumps(run_cells1d(name, args, dev))
+            print(txt, flush=True)
+            with open(path, "a") as f:
+                f.write(txt + "\n")
+            torch.cuda.empty_cache()
+            continue
         if name in CELLS_CASES:
             path = args.out or os.path.join(ROOT, "profiles", "screencells", "screen_bench_cells.jsonl")
             os.makedirs(os.path.dirname(path), exist_ok=True)
