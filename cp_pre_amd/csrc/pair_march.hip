@@ -185,16 +185,14 @@ int pre_pair_ns_momentum_f32(const pre_field_t a[3], const pre_field_t b[3], con
     int rc = check_sets(fs, 6, out, B, T, X, Y, flags);
     if (rc) return rc;
     NSParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) ||
-        !star_from_dense27(K_y, &prm.Dy) || !star_from_dense27(K_xx_yy, &prm.L))
-        return PRE_E_UNSUPPORTED;
-    const int mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, &prm.L);      // on the caller's axes
+    int mode;
+    rc = ns_params(prm, &mode, K_t, K_x, K_y, K_xx_yy, dt, dx, dy, nu);
+    if (rc) return rc;
     Star *stars[4] = {&prm.Dt, &prm.Dx, &prm.Dy, &prm.L};
     Geom g;
     int rel;
     rc = prepare(g, rel, fs, 6, out, B, T, X, Y, flags, stars, 4);
     if (rc) return rc;
-    prm.dxdy = dx * dy; prm.dtdy = dt * dy; prm.dtdx = dt * dx; prm.nudt = nu * dt;
     g.tfree = no_t_taps(stars, 4);
     return launch_pair_mode<PairedNS, false>(relabeled_mode(mode, rel), g, prm, as_stream(stream));
 }
@@ -208,11 +206,9 @@ int pre_pair_mhd_continuity_f32(const pre_field_t a[3], const pre_field_t b[3], 
     int rc = check_sets(fs, 6, out, B, T, X, Y, flags);
     if (rc) return rc;
     MHDParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) || !star_from_dense27(K_y, &prm.Dy))
-        return PRE_E_UNSUPPORTED;
-    prm.gamma = (float)gamma;
-    prm.gm2 = (float)(gamma - 2.0);
-    const int mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, nullptr);
+    int mode;
+    rc = mhd_params(prm, &mode, K_t, K_x, K_y, gamma);
+    if (rc) return rc;
     Star *stars[3] = {&prm.Dt, &prm.Dx, &prm.Dy};
     Geom g;
     int rel;

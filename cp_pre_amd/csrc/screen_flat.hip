@@ -28,9 +28,13 @@
 //           of chunks x (chunk + staged halo quads); the staged halo is 2 * min(32, ceil(Nt/4)) quads for a functor that
 //           stages a field, none otherwise (launch_flat's rule);
 //   march   pick_tseg(B * chunks, Nx, resident workgroups): the marched axis in segments of tSeg planes.
+//
+// The host side of an entry is screen_entries.h's: the entry names the views its residual reads and forwards to the body
+// of its kind, here with <FlatForm, Single, ScalarSets>.
 #include "screen_plane.h"
 #include "../../include/cp_pre_screenflat.h"
 #include "screen_flat.h"       // the kernel, its geometry, launchers, host checks and the relabelling of the stars
+#include "screen_entries.h"    // the bodies of the entries, shared by the five 2-D screen libraries
 
 extern "C" {
 
@@ -39,33 +43,13 @@ int pre_screenflat_abi_version(void) { return PRE_SCREENFLAT_ABI_VERSION; }
 int pre_screenflat_stencil3d_f32(const pre_field_t *f, const float *tap_w, const int32_t *tap_off, int ntaps,
                                  const pre_screenflat_t *s, int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (ntaps < 0 || (ntaps > 0 && (!tap_w || !tap_off))) return PRE_E_NULL;
-    if (ntaps > 343) return PRE_E_SHAPE;
-    const pre_field_t *fs[1] = {f};
-    FGeom g;
-    int rc = prepare_flat(g, fs, 1, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    Linear1::Params p;
-    if (!star_of_taps(tap_w, tap_off, ntaps, &p.s, &rc)) return rc ? rc : PRE_E_UNSUPPORTED;
-    Star *stars[1] = {&p.s};
-    relabel_stars(stars, 1);
-    return launch_screen_flat<Linear1>(g, p, as_stream(stream));
+    return stencil3d<FlatForm, Single, ScalarSets>({{f}, 1}, tap_w, tap_off, ntaps, s, B, T, X, Y, flags, stream);
 }
 
 int pre_screenflat_linear2_f32(const pre_field_t *f0, const pre_field_t *f1, const float *K_a, const float *K_b, float ratio,
                                const pre_screenflat_t *s, int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (!K_a || !K_b) return PRE_E_NULL;
-    const pre_field_t *fs[2] = {f0, f1};
-    FGeom g;
-    int rc = prepare_flat(g, fs, 2, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    Linear2::Params prm;
-    if (!star_from_dense27(K_a, &prm.a) || !star_from_dense27(K_b, &prm.b)) return PRE_E_UNSUPPORTED;
-    prm.ratio = ratio;
-    Star *stars[2] = {&prm.a, &prm.b};
-    relabel_stars(stars, 2);
-    return launch_screen_flat<Linear2>(g, prm, as_stream(stream));
+    return linear2<FlatForm, Single, ScalarSets>({{f0, f1}, 2}, K_a, K_b, ratio, s, B, T, X, Y, flags, stream);
 }
 
 int pre_screenflat_ns_momentum_f32(const pre_field_t *u, const pre_field_t *v, const pre_field_t *p,
@@ -73,52 +57,15 @@ int pre_screenflat_ns_momentum_f32(const pre_field_t *u, const pre_field_t *v, c
                                    float dt, float dx, float dy, float nu, const pre_screenflat_t *s,
                                    int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (!K_t || !K_x || !K_y || !K_xx_yy) return PRE_E_NULL;
-    const pre_field_t *fs[3] = {u, v, p};
-    FGeom g;
-    int rc = prepare_flat(g, fs, 3, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    NSParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) ||
-        !star_from_dense27(K_y, &prm.Dy) || !star_from_dense27(K_xx_yy, &prm.L))
-        return PRE_E_UNSUPPORTED;
-    const int mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, &prm.L);      // on the caller's axes
-    prm.dxdy = dx * dy; prm.dtdy = dt * dy; prm.dtdx = dt * dx; prm.nudt = nu * dt;      // (as pre_residual_ns_momentum_f32)
-    Star *stars[4] = {&prm.Dt, &prm.Dx, &prm.Dy, &prm.L};
-    relabel_stars(stars, 4);
-    return launch_screen_flat_mode<NSMomentum>(relabeled_mode(mode, 1), g, prm, as_stream(stream));
+    return ns_momentum<FlatForm, Single, ScalarSets>({{u, v, p}, 3}, K_t, K_x, K_y, K_xx_yy, dt, dx, dy, nu, s, B, T, X, Y, flags,
+                                                     stream);
 }
 
 int pre_screenflat_mhd_f32(int eq, const pre_field_t fields[6], const float *K_t, const float *K_x, const float *K_y, double gamma,
                            const pre_screenflat_t *s, int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (!fields || !K_t || !K_x || !K_y) return PRE_E_NULL;
-    if (eq < 0 || eq > 3) return PRE_E_RANGE;
-    const pre_field_t *all[6] = {&fields[0], &fields[1], &fields[2], &fields[3], &fields[4], &fields[5]};
-    const pre_field_t *c3[3] = {all[0], all[1], all[2]}, *i4[4] = {all[1], all[2], all[4], all[5]};
-    FGeom g;
-    int rc = eq == 0 ? prepare_flat(g, c3, 3, s, B, T, X, Y, flags)
-           : eq == 3 ? prepare_flat(g, i4, 4, s, B, T, X, Y, flags) : prepare_flat(g, all, 6, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    MHDParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) || !star_from_dense27(K_y, &prm.Dy))
-        return PRE_E_UNSUPPORTED;
-    prm.gamma = (float)gamma;
-    prm.gm2 = (float)(gamma - 2.0);   // (as pre_residual_mhd_f32)
-    const int mode = relabeled_mode(pick_mode(prm.Dt, prm.Dx, prm.Dy, nullptr), 1);
-    Star *stars[3] = {&prm.Dt, &prm.Dx, &prm.Dy};
-    relabel_stars(stars, 3);
-    hipStream_t st = as_stream(stream);
-    if (eq == 0) return launch_screen_flat_mode<MHDContinuity>(mode, g, prm, st);
-    if (eq == 1) {
-        // the general-star instantiation of the momentum functor (six fields, all but rho staged) does not fit 256 registers
-        // with the epilogue (20 bytes of scratch): not built, as MHDEnergy<2> in libcp_pre_screen.so; the caller takes its
-        // three-pass route
-        if (mode == 2) return PRE_E_UNSUPPORTED;
-        return mode == 3 ? launch_screen_flat<MHDMomentum<3>>(g, prm, st) : launch_screen_flat<MHDMomentum<4>>(g, prm, st);
-    }
-    if (eq == 2) return launch_screen_flat_mode<MHDEnergy>(mode, g, prm, st);
-    return launch_screen_flat_mode<MHDInduction>(mode, g, prm, st);
+    if (!fields) return PRE_E_NULL;
+    return mhd<FlatForm, Single, ScalarSets>(eq, mhd_views(eq, fields), K_t, K_x, K_y, gamma, s, B, T, X, Y, flags, stream);
 }
 
 }  // extern "C"

@@ -19,8 +19,12 @@
 // by the other seven: at most an eighth of 4 B per cell from HBM even if nothing of it survives until the next sample,
 // while the field halos keep meeting in one L2.  (Sample-fastest order would hold a modulation tile in L2 across samples
 // but put neighbouring tiles of a sample far apart: every halo row, 2/NR of the input, would be fetched twice.)
+//
+// The host side of an entry is screen_entries.h's: the entry names the views its residual reads and forwards to the body
+// of its kind, here with <NyForm, Single, ScalarSets>.
 #include "screen_plane.h"
 #include "screen_march.h"      // the kernel, its geometry, launchers and host checks
+#include "screen_entries.h"    // the bodies of the entries, shared by the five 2-D screen libraries
 
 extern "C" {
 
@@ -29,33 +33,13 @@ int pre_screen_abi_version(void) { return PRE_SCREEN_ABI_VERSION; }
 int pre_screen_stencil3d_f32(const pre_field_t *f, const float *tap_w, const int32_t *tap_off, int ntaps, const pre_screen_t *s,
                              int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (ntaps < 0 || (ntaps > 0 && (!tap_w || !tap_off))) return PRE_E_NULL;
-    if (ntaps > 343) return PRE_E_SHAPE;
-    const pre_field_t *fs[1] = {f};
-    SGeom g;
-    int rc = prepare_screen(g, fs, 1, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    Linear1::Params p;
-    if (!star_of_taps(tap_w, tap_off, ntaps, &p.s, &rc)) return rc ? rc : PRE_E_UNSUPPORTED;
-    Star *stars[1] = {&p.s};
-    g.tfree = no_t_taps(stars, 1);
-    return launch_screen<Linear1>(g, p, as_stream(stream));
+    return stencil3d<NyForm, Single, ScalarSets>({{f}, 1}, tap_w, tap_off, ntaps, s, B, T, X, Y, flags, stream);
 }
 
 int pre_screen_linear2_f32(const pre_field_t *f0, const pre_field_t *f1, const float *K_a, const float *K_b, float ratio,
                            const pre_screen_t *s, int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (!K_a || !K_b) return PRE_E_NULL;
-    const pre_field_t *fs[2] = {f0, f1};
-    SGeom g;
-    int rc = prepare_screen(g, fs, 2, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    Linear2::Params prm;
-    if (!star_from_dense27(K_a, &prm.a) || !star_from_dense27(K_b, &prm.b)) return PRE_E_UNSUPPORTED;
-    prm.ratio = ratio;
-    Star *stars[2] = {&prm.a, &prm.b};
-    g.tfree = no_t_taps(stars, 2);
-    return launch_screen<Linear2>(g, prm, as_stream(stream));
+    return linear2<NyForm, Single, ScalarSets>({{f0, f1}, 2}, K_a, K_b, ratio, s, B, T, X, Y, flags, stream);
 }
 
 int pre_screen_ns_momentum_f32(const pre_field_t *u, const pre_field_t *v, const pre_field_t *p,
@@ -63,51 +47,15 @@ int pre_screen_ns_momentum_f32(const pre_field_t *u, const pre_field_t *v, const
                                float dt, float dx, float dy, float nu, const pre_screen_t *s,
                                int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (!K_t || !K_x || !K_y || !K_xx_yy) return PRE_E_NULL;
-    const pre_field_t *fs[3] = {u, v, p};
-    SGeom g;
-    int rc = prepare_screen(g, fs, 3, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    NSParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) ||
-        !star_from_dense27(K_y, &prm.Dy) || !star_from_dense27(K_xx_yy, &prm.L))
-        return PRE_E_UNSUPPORTED;
-    const int mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, &prm.L);
-    prm.dxdy = dx * dy; prm.dtdy = dt * dy; prm.dtdx = dt * dx; prm.nudt = nu * dt;      // (as pre_residual_ns_momentum_f32)
-    Star *stars[4] = {&prm.Dt, &prm.Dx, &prm.Dy, &prm.L};
-    g.tfree = no_t_taps(stars, 4);
-    return launch_screen_mode<NSMomentum>(mode, g, prm, as_stream(stream));
+    return ns_momentum<NyForm, Single, ScalarSets>({{u, v, p}, 3}, K_t, K_x, K_y, K_xx_yy, dt, dx, dy, nu, s, B, T, X, Y, flags,
+                                                   stream);
 }
 
 int pre_screen_mhd_f32(int eq, const pre_field_t fields[6], const float *K_t, const float *K_x, const float *K_y, double gamma,
                        const pre_screen_t *s, int64_t B, int64_t T, int64_t X, int64_t Y, int flags, void *stream)
 {
-    if (!fields || !K_t || !K_x || !K_y) return PRE_E_NULL;
-    if (eq < 0 || eq > 3) return PRE_E_RANGE;
-    const pre_field_t *all[6] = {&fields[0], &fields[1], &fields[2], &fields[3], &fields[4], &fields[5]};
-    const pre_field_t *c3[3] = {all[0], all[1], all[2]}, *i4[4] = {all[1], all[2], all[4], all[5]};
-    SGeom g;
-    int rc = eq == 0 ? prepare_screen(g, c3, 3, s, B, T, X, Y, flags)
-           : eq == 3 ? prepare_screen(g, i4, 4, s, B, T, X, Y, flags) : prepare_screen(g, all, 6, s, B, T, X, Y, flags);
-    if (rc) return rc;
-    MHDParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) || !star_from_dense27(K_y, &prm.Dy))
-        return PRE_E_UNSUPPORTED;
-    prm.gamma = (float)gamma;
-    prm.gm2 = (float)(gamma - 2.0);   // (as pre_residual_mhd_f32)
-    const int mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, nullptr);
-    Star *stars[3] = {&prm.Dt, &prm.Dx, &prm.Dy};
-    g.tfree = no_t_taps(stars, 3);
-    hipStream_t st = as_stream(stream);
-    if (eq == 0) return launch_screen_mode<MHDContinuity>(mode, g, prm, st);
-    if (eq == 1) return launch_screen_mode<MHDMomentum>(mode, g, prm, st);
-    if (eq == 2) {
-        // the general-star instantiation of the energy functor does not fit 256 registers with the epilogue (24-28 bytes
-        // of scratch): not built; the caller takes its three-pass route
-        if (mode == 2) return PRE_E_UNSUPPORTED;
-        return mode == 0 ? launch_screen<MHDEnergy<0>>(g, prm, st) : launch_screen<MHDEnergy<1>>(g, prm, st);
-    }
-    return launch_screen_mode<MHDInduction>(mode, g, prm, st);
+    if (!fields) return PRE_E_NULL;
+    return mhd<NyForm, Single, ScalarSets>(eq, mhd_views(eq, fields), K_t, K_x, K_y, gamma, s, B, T, X, Y, flags, stream);
 }
 
 }  // extern "C"

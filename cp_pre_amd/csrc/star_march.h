@@ -787,6 +787,45 @@ int pick_mode(const Star &Dt, const Star &Dx, const Star &Dy, const Star *L)
     return 2;
 }
 
+// The parameter block of a fused residual from its dense kernels and scalars, for every pass that evaluates it (residual,
+// paired, screens): PRE_E_UNSUPPORTED if a kernel has weight off the star, else *mode = its tap structure on the caller's axes.
+int ns_params(NSParams &prm, int *mode, const float *K_t, const float *K_x, const float *K_y, const float *K_xx_yy, float dt,
+              float dx, float dy, float nu)
+{
+    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) || !star_from_dense27(K_y, &prm.Dy) ||
+        !star_from_dense27(K_xx_yy, &prm.L))
+        return PRE_E_UNSUPPORTED;
+    *mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, &prm.L);
+    prm.dxdy = dx * dy; prm.dtdy = dt * dy; prm.dtdx = dt * dx; prm.nudt = nu * dt;
+    return PRE_OK;
+}
+
+int mhd_params(MHDParams &prm, int *mode, const float *K_t, const float *K_x, const float *K_y, double gamma)
+{
+    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) || !star_from_dense27(K_y, &prm.Dy))
+        return PRE_E_UNSUPPORTED;
+    prm.gamma = (float)gamma;
+    prm.gm2 = (float)(gamma - 2.0);   // "(gamma-2)" is a float64 Python scalar in the reference
+    *mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, nullptr);
+    return PRE_OK;
+}
+
+int jorek_params(JorekParams &prm, int *mode, const float *K_t, const float *K_R, const float *K_Z, const float *K_RR,
+                 const float *K_ZZ, const float coef[4])
+{
+    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_R, &prm.DR) || !star_from_dense27(K_Z, &prm.DZ) ||
+        !star_from_dense27(K_RR, &prm.DRR) || !star_from_dense27(K_ZZ, &prm.DZZ))
+        return PRE_E_UNSUPPORTED;
+    prm.a0 = coef[0]; prm.a1 = coef[1]; prm.a2 = coef[2]; prm.a3 = coef[3];
+    // D_RR must fit D_R's compiled tap structure and D_ZZ that of D_Z, else every operator is a general star
+    int m = pick_mode(prm.Dt, prm.DR, prm.DZ, nullptr);
+    const Shape rr = shape_of(prm.DRR), zz = shape_of(prm.DZZ);
+    const bool rr_ok = !rr.t && !rr.y, zz_ok = m == 0 ? (!zz.x && !zz.y) : (!zz.x && !zz.t);
+    if (m != 2 && !(rr_ok && zz_ok)) m = 2;
+    *mode = m;
+    return PRE_OK;
+}
+
 // ---- how finely to cut the marched axis (round 6) ------------------------------------------------------------------
 // A workgroup marches a whole t segment; the chip holds `slots` workgroups at once, so a launch runs in rounds and the
 // last round is as full as it happens to be: 3200 workgroups on 768 slots are 4.2 rounds - the fifth runs a sixth full

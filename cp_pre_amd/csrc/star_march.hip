@@ -39,16 +39,14 @@ int pre_residual_ns_momentum_f32(const pre_field_t *u, const pre_field_t *v, con
     if (!K_t || !K_x || !K_y || !K_xx_yy) return PRE_E_NULL;
     const pre_field_t *fs[3] = {u, v, p};
     NSParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) ||
-        !star_from_dense27(K_y, &prm.Dy) || !star_from_dense27(K_xx_yy, &prm.L))
-        return PRE_E_UNSUPPORTED;
-    const int mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, &prm.L);      // on the caller's axes
+    int mode;
+    int rc = ns_params(prm, &mode, K_t, K_x, K_y, K_xx_yy, dt, dx, dy, nu);
+    if (rc) return rc;
     Star *stars[4] = {&prm.Dt, &prm.Dx, &prm.Dy, &prm.L};
     Geom g;
     int rel;
-    int rc = prepare(g, rel, fs, 3, out, B, T, X, Y, flags, stars, 4);
+    rc = prepare(g, rel, fs, 3, out, B, T, X, Y, flags, stars, 4);
     if (rc) return rc;
-    prm.dxdy = dx * dy; prm.dtdy = dt * dy; prm.dtdx = dt * dx; prm.nudt = nu * dt;
     g.tfree = no_t_taps(stars, 4);
     return launch_mode<NSMomentum>(relabeled_mode(mode, rel), g, prm, as_stream(stream));
 }
@@ -110,11 +108,9 @@ int pre_residual_mhd_f32(int eq, const pre_field_t fields[6], const pre_out_t *o
     if (!fields || !K_t || !K_x || !K_y) return PRE_E_NULL;
     if (eq < 0 || eq > 3) return PRE_E_RANGE;
     MHDParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_x, &prm.Dx) || !star_from_dense27(K_y, &prm.Dy))
-        return PRE_E_UNSUPPORTED;
-    prm.gamma = (float)gamma;
-    prm.gm2 = (float)(gamma - 2.0);   // "(gamma-2)" is a float64 Python scalar in the reference
-    int mode = pick_mode(prm.Dt, prm.Dx, prm.Dy, nullptr);
+    int mode;
+    int rc = mhd_params(prm, &mode, K_t, K_x, K_y, gamma);
+    if (rc) return rc;
     const pre_field_t *all[6] = {&fields[0], &fields[1], &fields[2], &fields[3], &fields[4], &fields[5]};
     Star *stars[3] = {&prm.Dt, &prm.Dx, &prm.Dy};
     Geom g;
@@ -122,19 +118,19 @@ int pre_residual_mhd_f32(int eq, const pre_field_t fields[6], const pre_out_t *o
     hipStream_t st = as_stream(stream);
     if (eq == 0) {
         const pre_field_t *fs[3] = {all[0], all[1], all[2]};
-        int rc = prepare(g, rel, fs, 3, out, B, T, X, Y, flags, stars, 3);
+        rc = prepare(g, rel, fs, 3, out, B, T, X, Y, flags, stars, 3);
         if (rc) return rc;
         g.tfree = no_t_taps(stars, 3);
         return launch_mode<MHDContinuity>(relabeled_mode(mode, rel), g, prm, st);
     }
     if (eq == 3) {
         const pre_field_t *fs[4] = {all[1], all[2], all[4], all[5]};
-        int rc = prepare(g, rel, fs, 4, out, B, T, X, Y, flags, stars, 3);
+        rc = prepare(g, rel, fs, 4, out, B, T, X, Y, flags, stars, 3);
         if (rc) return rc;
         g.tfree = no_t_taps(stars, 3);
         return launch_mode<MHDInduction>(relabeled_mode(mode, rel), g, prm, st);
     }
-    int rc = prepare(g, rel, all, 6, out, B, T, X, Y, flags, stars, 3);
+    rc = prepare(g, rel, all, 6, out, B, T, X, Y, flags, stars, 3);
     if (rc) return rc;
     g.tfree = no_t_taps(stars, 3);
     if (eq == 1) return launch_mode<MHDMomentum>(relabeled_mode(mode, rel), g, prm, st);
@@ -148,30 +144,22 @@ int pre_residual_jorek_f32(int eq, const pre_field_t fields[3], const pre_field_
     if (!fields || !Rb || !K_t || !K_R || !K_Z || !K_RR || !K_ZZ || !coef) return PRE_E_NULL;
     if (eq < 0 || eq > 1) return PRE_E_RANGE;
     JorekParams prm;
-    if (!star_from_dense27(K_t, &prm.Dt) || !star_from_dense27(K_R, &prm.DR) || !star_from_dense27(K_Z, &prm.DZ) ||
-        !star_from_dense27(K_RR, &prm.DRR) || !star_from_dense27(K_ZZ, &prm.DZZ))
-        return PRE_E_UNSUPPORTED;
-    prm.a0 = coef[0]; prm.a1 = coef[1]; prm.a2 = coef[2]; prm.a3 = coef[3];
-    // D_RR must fit D_R's compiled tap structure and D_ZZ that of D_Z, else every operator is a general star
-    int mode = pick_mode(prm.Dt, prm.DR, prm.DZ, nullptr);
-    {
-        const Shape rr = shape_of(prm.DRR), zz = shape_of(prm.DZZ);
-        const bool rr_ok = !rr.t && !rr.y, zz_ok = mode == 0 ? (!zz.x && !zz.y) : (!zz.x && !zz.t);
-        if (mode != 2 && !(rr_ok && zz_ok)) mode = 2;
-    }
+    int mode;
+    int rc = jorek_params(prm, &mode, K_t, K_R, K_Z, K_RR, K_ZZ, coef);
+    if (rc) return rc;
     Star *stars[5] = {&prm.Dt, &prm.DR, &prm.DZ, &prm.DRR, &prm.DZZ};
     Geom g;
     int rel;
     hipStream_t st = as_stream(stream);
     if (eq == 0) {
         const pre_field_t *fs[3] = {&fields[0], &fields[1], Rb};
-        int rc = prepare(g, rel, fs, 3, out, B, T, X, Y, flags, stars, 5);
+        rc = prepare(g, rel, fs, 3, out, B, T, X, Y, flags, stars, 5);
         if (rc) return rc;
         g.tfree = no_t_taps(stars, 5);
         return launch_mode<JorekContinuity>(relabeled_mode(mode, rel), g, prm, st);
     }
     const pre_field_t *fs[4] = {&fields[0], &fields[1], &fields[2], Rb};
-    int rc = prepare(g, rel, fs, 4, out, B, T, X, Y, flags, stars, 5);
+    rc = prepare(g, rel, fs, 4, out, B, T, X, Y, flags, stars, 5);
     if (rc) return rc;
     g.tfree = no_t_taps(stars, 5);
     return launch_mode<JorekTemperature>(relabeled_mode(mode, rel), g, prm, st);

@@ -173,6 +173,51 @@ class Case:
         return share, dist, split
 
 
+# ------------------------------------------------------------------ the tap structures beside the reference's
+# The kinds whose functor is compiled per tap structure, and the two structures no default operator set has: 'yfix' is
+# ``y_axis_fix=True`` (D_y's taps on the true Ny axis: <1> on Ny-fastest fields, <4> on Nt-fastest ones), 'general' a D_t
+# with a tap along Nx as well (<2> in either layout).  The oracle has the reference's operators only, so these cases are
+# held against the residual the package's own pass STORES with the same operators (``check_against_stored``).
+TAP_KINDS = ("ns_momentum", "mhd_continuity", "mhd_momentum", "mhd_energy", "mhd_induction")
+TAP_STRUCTURES = ("yfix", "general")
+
+
+def method_with_taps(kind, structure, device):
+    from cp_pre_amd import residuals as R
+    fix = structure == "yfix"
+    obj = (R.NavierStokes(NS_DT, NS_DX, NS_DY, nu=NS_NU, device=device, y_axis_fix=fix) if kind.startswith("ns_")
+           else R.MHD(device=device, y_axis_fix=fix))
+    if structure == "general":
+        obj.D_t.kernel.data[1, 0, 1] = 0.25
+    return getattr(obj, "residual_" + kind.split("_", 1)[1])
+
+
+def check_against_stored(case, s, res, q, what):
+    """``s`` (a ``Screened``) against ``res``, the uncropped fp32 residual [B,T,X,Y] that the residual pass stored for the
+    same fields and operators; ``q``: the levels [nk] or level fields [nk,T,X,Y] the screen was given.  Modulation, crop and
+    shape are ``case``'s.  The bounds: the stored residual and the one the screen holds in registers are each within
+    tau = 1e-5 max |res| of the exact residual, so within 2 tau of each other: the score within
+    2 tau / m_min (and one rounding of the divide) of the stored one's, a count off by no more than the cells whose stored
+    |res| lies within 2 tau of that level's edge."""
+    reg = region(case.shape, case.crop)
+    d = res[reg].abs().double().flatten(1).cpu()                                      # [B, cells]
+    m = (case.mod.double() if case.mod is not None else torch.ones(case.shape[1:], dtype=torch.float64))[reg[1:]].flatten()
+    tau = 1e-5 * float(res.abs().max())
+    tol = 2 * tau / float(m.min())
+    want = (d / m).max(dim=1).values
+    q = q.double().cpu()
+    hw = (q[:, None] if q.dim() == 1 else q[(slice(None),) + reg[1:]].flatten(1)) * m[None]      # [nk, cells]
+    gap = d[None] - hw[:, None]                                                       # [nk, B, cells]
+    und = (gap.abs() <= 2 * tau).sum(dim=2)
+    err = (s.score.double().cpu() - want).abs()
+    dcount = (s.inside.cpu() - (gap <= 0).sum(dim=2)).abs()
+    print(f"{what}: score diff {float(err.max()):.3e} (allowed {tol:.3e} + ulp), count diff max {int(dcount.max())} "
+          f"(within 2 tau of an edge: max {int(und.max())} of {m.numel()} cells)")
+    assert s.cells == m.numel() and tuple(s.inside.shape) == (hw.shape[0], case.shape[0])
+    assert bool((err <= tol + 1.2e-7 * want).all()), (what, err, tol)
+    assert bool((dcount <= und).all()), (what, dcount, und)
+
+
 # (B, T, X, Y) of the GPU cases, by the seam they cross (screen_march_kernel: 32 rows x 64 columns for Ny < 96, 16 x 128
 # below 192, 8 x 256 from there; pick_tseg halves T until <= 16; tap-free marches of 8 planes)
 SEAM_SHAPES = {

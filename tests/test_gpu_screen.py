@@ -21,11 +21,11 @@ def gpu():
     return torch.device("cuda:0")
 
 
-def run(case, gpu, x=None, mod=None):
+def run(case, gpu, x=None, mod=None, method=None):
     from cp_pre_amd import screen
     xd = case.x.to(gpu) if x is None else x
     md = (case.mod.to(gpu) if case.mod is not None else None) if mod is None else mod
-    return screen.screen(sh.method_of(case.kind, gpu), xd, case.q.to(gpu), md, boundary=case.boundary)
+    return screen.screen(method or sh.method_of(case.kind, gpu), xd, case.q.to(gpu), md, boundary=case.boundary)
 
 
 def check_against_ref(case, s, what):
@@ -334,3 +334,23 @@ def test_screen_ns_momentum_memory(gpu):
     print(f"peak beyond the inputs: {extra} bytes (one field: {field})")
     assert extra < field
     assert s.cells == 30 * 254 * 254
+
+
+# ------------------------------------------------------------------ the tap structures beside the reference's
+@pytest.mark.parametrize("structure", sh.TAP_STRUCTURES)
+@pytest.mark.parametrize("kind", sh.TAP_KINDS)
+def test_screen_other_tap_structures_against_the_stored_residual(gpu, kind, structure):
+    """The y-fixed (<1>) and general-star (<2>) instantiations of every functor compiled per tap structure, which the
+    default operators never reach, against the residual stored with the same operators (``sh.check_against_stored`` has the
+    bounds; the levels are the default operators' case's: what they split does not matter here) - and not the default
+    operators' answer.  The general star of the MHD energy is not built: the library declines."""
+    from cp_pre_amd import screen
+    case = sh.Case(kind, sh.SEAM_SHAPES["two_tseg"], False, True, 10)
+    method = sh.method_with_taps(kind, structure, gpu)
+    xd = case.x.to(gpu)
+    s = run(case, gpu, x=xd, method=method)
+    built = (kind, structure) != ("mhd_energy", "general")
+    assert screen.last_route() == ("fused:" + sh.FUSED_KIND[kind] if built else "fallback:declined by the library")
+    plain = run(case, gpu, x=xd)
+    assert not (torch.equal(sg.bits(s.score), sg.bits(plain.score)) and torch.equal(s.inside, plain.inside))
+    sh.check_against_stored(case, s, method(xd, boundary=True), case.q, f"{kind} {structure}")

@@ -21,12 +21,12 @@ def gpu():
     return torch.device("cuda:0")
 
 
-def run(c, gpu, x=None, q=None, mod=None):
+def run(c, gpu, x=None, q=None, mod=None, method=None):
     from cp_pre_amd import screen
     xd = fh.to_layout(c.x, gpu) if x is None else x
     qd = fh.to_layout(c.q, gpu) if q is None else q
     md = (fh.to_layout(c.mod, gpu) if c.mod is not None else None) if mod is None else mod
-    return screen.screen_cells(sh.method_of(c.kind, gpu), xd, qd, md, boundary=c.boundary)
+    return screen.screen_cells(method or sh.method_of(c.kind, gpu), xd, qd, md, boundary=c.boundary)
 
 
 def same(a, b):
@@ -152,3 +152,24 @@ def test_screencells_flat_t_slab_is_not_dense(gpu):
     s = screen.ScreenCells(shape[0], 10, gpu)
     s.add_slab(sh.method_of("ns_momentum", gpu), xd[:, :, sl], qd[:, sl], md[sl])
     assert screen.last_route() == "fallback:rows not dense"
+
+
+# ------------------------------------------------------------------ the tap structures beside the reference's
+@pytest.mark.parametrize("structure", sh.TAP_STRUCTURES)
+@pytest.mark.parametrize("kind", sh.TAP_KINDS)
+def test_screencells_flat_other_tap_structures_against_the_stored_residual(gpu, kind, structure):
+    """The y-fixed (<4>) and general-star (<2>) instantiations of every functor compiled per tap structure, which the
+    default operators never reach, against the residual stored with the same operators on the same Nt-fastest views
+    (``sh.check_against_stored`` has the bounds; the level fields are the default operators' case's) - and not the default
+    operators' answer.  The general stars of the MHD momentum and energy are not built with per-cell sets: the library
+    declines."""
+    from cp_pre_amd import screen
+    nk, name = ch.MAIN[0]
+    c = ch.case(kind, sh.SEAM_SHAPES[name], False, True, nk)
+    method = sh.method_with_taps(kind, structure, gpu)
+    xd = fh.to_layout(c.x, gpu)
+    s = run(c, gpu, x=xd, method=method)
+    built = structure != "general" or kind not in ("mhd_momentum", "mhd_energy")
+    assert screen.last_route() == (ch.route(kind, flat=True) if built else "fallback:declined by the library")
+    assert not same(s, run(c, gpu, x=xd))
+    sh.check_against_stored(c, s, method(xd, boundary=True), c.q, f"{kind} {structure} flat")

@@ -383,3 +383,22 @@ def test_screenflat_c_client_runs(gpu, tmp_path):
     print(out.stdout[-4000:])
     assert out.returncode == 0 and "FAIL" not in out.stdout, out.stdout + out.stderr
     assert "no device" not in out.stdout and out.stdout.count("ok:") >= 35, out.stdout
+
+
+# ------------------------------------------------------------------ the tap structures beside the reference's
+@pytest.mark.parametrize("structure", sh.TAP_STRUCTURES)
+@pytest.mark.parametrize("kind", sh.TAP_KINDS)
+def test_screenflat_other_tap_structures_against_the_stored_residual(gpu, kind, structure):
+    """The y-fixed (<4>) and general-star (<2>) instantiations of every functor compiled per tap structure, which the
+    default operators never reach, against the residual stored with the same operators on the same Nt-fastest views
+    (``sh.check_against_stored`` has the bounds; the levels are the default operators' case's) - and not the default
+    operators' answer.  The general star of the MHD momentum is not built: the library declines."""
+    from cp_pre_amd import screen
+    case = case_of(kind, sf.SEAM_SHAPES["straddle_10"])
+    method = sh.method_with_taps(kind, structure, gpu)
+    xd = sf.to_layout(case.x, gpu)
+    s = run(case, gpu, x=xd, method=method)
+    built = (kind, structure) != ("mhd_momentum", "general")
+    assert screen.last_route() == (sf.ROUTE[kind] if built else "fallback:declined by the library")
+    assert not same(s, run(case, gpu, x=xd))
+    sh.check_against_stored(case, s, method(xd, boundary=True), case.q, f"{kind} {structure} flat")
