@@ -389,6 +389,17 @@ SCREEN1DCELLS_SIGNATURES = {
     "pre_screen1dcells_pair_burgers_f32": SCREEN1DPAIR_SIGNATURES["pre_screen1dpair_burgers_f32"][:-len(_scr1)] + _scr1c,
 }
 
+# libcp_pre_screencellspair.so (include/cp_pre_screencellspair.h): the two 2-D screens against per-cell sets for the data-driven
+# scores r(a) - r(b): each entry takes its twin's arguments in libcp_pre_screenpair.so with the set descriptor swapped for the
+# per-cell one (PreScreenCells / PreScreenCellsFlat reused)
+SCREENCELLSPAIR_SO_PATH = os.path.join(_HERE, "libcp_pre_screencellspair.so")
+PRE_SCREENCELLSPAIR_ABI_VERSION = 1
+_CELLS_DESC = {POINTER(PreScreen): POINTER(PreScreenCells), POINTER(PreScreenFlat): POINTER(PreScreenCellsFlat)}
+SCREENCELLSPAIR_SIGNATURES = {"pre_screencellspair_abi_version": [], "pre_screencellspair_sample_group": []}
+SCREENCELLSPAIR_SIGNATURES.update({
+    _name.replace("pre_screenpair_", "pre_screencellspair_"): [_CELLS_DESC.get(_a, _a) for _a in _sig]
+    for _name, _sig in SCREENPAIR_SIGNATURES.items() if _sig})
+
 # libcp_pre_vjpflatmhd.so (include/cp_pre_vjpflatmhd.h): the entries of libcp_pre_vjpmhd.so for Nt-fastest views (the march of
 # libcp_pre_vjpflat.so), argument for argument
 VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
@@ -440,8 +451,10 @@ _LIBS_MORE = {
     "screen1dpair": ("_screen1dpair", "SCREEN1DPAIR_", "pre_screen1dpair_abi_version", "PRE_SCREEN1DPAIR_ABI_VERSION", ()),
     "screencells": ("_screencells", "SCREENCELLS_", "pre_screencells_abi_version", "PRE_SCREENCELLS_ABI_VERSION", ()),
     "screen1dcells": ("_screen1dcells", "SCREEN1DCELLS_", "pre_screen1dcells_abi_version", "PRE_SCREEN1DCELLS_ABI_VERSION", ()),
+    "screencellspair": ("_screencellspair", "SCREENCELLSPAIR_", "pre_screencellspair_abi_version",
+                        "PRE_SCREENCELLSPAIR_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -566,6 +579,10 @@ def load_screencells():
 
 def load_screen1dcells():
     return _screen1dcells or _load("screen1dcells")
+
+
+def load_screencellspair():
+    return _screencellspair or _load("screencellspair")
 
 
 def require_gpu():

@@ -11,7 +11,8 @@
 //           issue order, so the wait for the level quads at the end of the plane leaves those later loads in flight, and the
 //           quads have the LDS staging, the barrier and the functor to arrive in.  LB = CellsBatch<Fn>: 16 (all of them at
 //           once: 64 registers) unless the functor leaves no room; then the quads beyond the first batch are fetched after
-//           the functor, a batch at a time (the specialisations below; DESIGN 4.25 has the measurements);
+//           the functor (load_late), CellsLate<Fn> at a time - here the first batch's size, the default (the specialisations
+//           below; DESIGN 4.25 has the measurements; screen_cells_pair.hip sizes the two apart);
 //   plane   screen_plane_cells (screen_plane.h): screen_plane with ql[k][j] in place of the wave-uniform qk[k];
 //   order   the logical block index is decoded with the sample of a group of CELLS_G fastest, then the tile, the segment,
 //           the group.  With the joint screens' order (sample slowest) every sample re-reads nk * 4 bytes of levels per

@@ -1,5 +1,5 @@
 // screen_entries.h - the host side of the 2-D calibrated-set screens, stated once for screen_march.hip, screen_flat.hip,
-// screen_pair.hip, screen_cells.hip and screen_jorek.hip: what an entry does between its arguments and its launch.  An entry
+// screen_pair.hip, screen_cells.hip, screen_cells_pair.hip and screen_jorek.hip: what an entry does between its arguments and its launch.  An entry
 // of those files assembles the views its residual reads and forwards to one of the five bodies below (stencil3d, linear2,
 // ns_momentum, mhd, jorek), which is templated on what differs between the libraries:
 //   Form   NyForm (Ny-fastest fields, screen_march.h) or FlatForm (Nt-fastest fields, screen_flat.h);
@@ -90,8 +90,8 @@ template <class Fn> using Single = Fn;
 
 // ---- what is built ----------------------------------------------------------------------------------------------------
 // Every (form, set policy, functor<tap structure>) is built but the ones below: an instantiation with scratch is not built,
-// its tap structure returns PRE_E_UNSUPPORTED and the caller takes its three-pass route (resources.sh on the five files:
-// scratch 0 throughout).  All of them are general stars (<2>) but the last.
+// its tap structure returns PRE_E_UNSUPPORTED and the caller takes its three-pass route (resources.sh on the six files:
+// scratch 0 throughout).  All of them are general stars (<2>) but the y-fixed paired NS momentum.
 template <class Form, class Sets, class Fn> struct Built : std::true_type {};
 // Ny-fastest, nk levels: the energy functor does not fit 256 registers with the epilogue (24-28 bytes of scratch)
 template <> struct Built<NyForm, ScalarSets, MHDEnergy<2>> : std::false_type {};
@@ -109,6 +109,14 @@ template <class Form> struct Built<Form, ScalarSets, PairedMHDContinuity<2>> : s
 // chunk.  (On the 512-thread tiles of launch_screen the paired NS momentum takes 250-256 registers and the paired MHD
 // continuity 169-199, none with scratch, so the tiles stay launch_screen's.)
 template <> struct Built<FlatForm, ScalarSets, PairedNS<4>> : std::false_type {};
+// two field sets against per-cell sets (screen_cells_pair.hip): the general stars of the six-view functors stay unbuilt (with
+// ONE level quad held across the functor and one per later batch, the least there is: the NS momentum 44-48 bytes of scratch
+// Ny-fastest and 8 Nt-fastest, the MHD continuity 60-68 and 40), and so does the y-fixed paired NS momentum in BOTH forms
+// (8-16 bytes Ny-fastest, 8 Nt-fastest)
+template <class Form> struct Built<Form, CellSets, PairedNS<2>> : std::false_type {};
+template <class Form> struct Built<Form, CellSets, PairedMHDContinuity<2>> : std::false_type {};
+template <> struct Built<NyForm, CellSets, PairedNS<1>> : std::false_type {};
+template <> struct Built<FlatForm, CellSets, PairedNS<4>> : std::false_type {};
 
 template <class Form, class Fn, class P, class Sets>
 int launch_built(typename Form::Geom &g, const P &prm, hipStream_t st, const Sets &sets)
@@ -136,6 +144,18 @@ Views mhd_views(int eq, const pre_field_t *f)
     if (eq == 0) return {{&f[0], &f[1], &f[2]}, 3};
     if (eq == 3) return {{&f[1], &f[2], &f[4], &f[5]}, 4};
     return {{&f[0], &f[1], &f[2], &f[3], &f[4], &f[5]}, 6};
+}
+
+// two field sets of F views each (screen_pair.hip, screen_cells_pair.hip): views [0, F) the set a, [F, 2F) the set b
+template <int F>
+Views pair_views(const pre_field_t *a, const pre_field_t *b)
+{
+    Views v = {{}, 2 * F};
+    for (int i = 0; i < F; ++i) {
+        v.fs[i] = &a[i];
+        v.fs[F + i] = &b[i];
+    }
+    return v;
 }
 
 // ---- the five bodies ----------------------------------------------------------------------------------------------------

@@ -28,7 +28,9 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
 {
     constexpr int F = Fn::F;
     constexpr bool CELLS = Sets::CELLS;
-    constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held at once)
+    constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held across the functor ...
+    constexpr int LL = CellsLate<Fn>::value;       //  ... and per batch fetched after it)
+    static_assert(LB >= 1 && LB <= NKMAX && (LB == NKMAX || (LL >= 1 && (NKMAX - LB) % LL == 0)), "whole batches");
     using SX = Staged<Fn>;
     constexpr int NW = NR * TYQ / 64;
     static_assert(NR >= 8 && (4 * TYQ) % 64 == 0 && (NR * TYQ) % 64 == 0, "the two halo rows are fetched by the first 8*TYQ threads, a wave per 64 floats");
@@ -140,24 +142,32 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
         }
     };
 
-    // per-cell sets: the quads of levels [k0, k0 + LB) at plane t, loaded like the modulation - only by threads with a
-    // counted cell, and t is always a plane of this segment
-    [[maybe_unused]] float4 ql[CELLS ? LB : 1];
-    [[maybe_unused]] auto load_lev = [&](int t, int k0) __attribute__((always_inline)) {
+    // per-cell sets: the quads of levels [k0, k0 + N) at plane t into dst[N], loaded like the modulation - only by threads
+    // with a counted cell, and t is always a plane of this segment.  ql: the first batch, held across the functor (load_lev);
+    // qm: a later batch, fetched after it (load_late)
+    [[maybe_unused]] float4 ql[CELLS ? LB : 1], qm[CELLS && LB < NKMAX && LL != LB ? LL : 1];
+    [[maybe_unused]] auto load_quads = [&](int t, int k0, auto &dst) __attribute__((always_inline)) {
         if constexpr (CELLS) {
+            constexpr int N = std::extent<std::remove_reference_t<decltype(dst)>>::value;
 #pragma unroll
-            for (int k = 0; k < LB; ++k) {
+            for (int k = 0; k < N; ++k) {
                 if (anykeep && k0 + k < g.nk) {
                     const float *p = g.q + ((long long)(k0 + k) * sets.qK + (long long)t * sets.qT);
                     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
                         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, -1, 0x00020000),
                         (int)(unsigned int)(((long long)x * sets.qX + y) * 4), 0, 0);
-                    ql[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+                    dst[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
                 } else {
-                    ql[k] = f4(0.f);
+                    dst[k] = f4(0.f);
                 }
             }
         }
+    };
+    [[maybe_unused]] auto load_lev = [&](int t) __attribute__((always_inline)) {
+        load_quads(t, 0, ql);
+    };
+    [[maybe_unused]] auto load_late = [&](int t, int k0) __attribute__((always_inline)) {
+        load_quads(t, k0, qm);
     };
 
     // the levels: wave-uniform, read once (per-cell sets: a quad per level and plane, load_lev)
@@ -180,7 +190,7 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
         const int bi = (t - t0) & 1;
         // per-cell sets: this plane's first LB level quads go out BEFORE the field loads below, so the wait for them at the
         // end of the plane (vmcnt retires in issue order) leaves the loads of the coming planes in flight
-        load_lev(t, 0);
+        load_lev(t);
 #pragma unroll
         for (int i = 0; i < F; ++i) {
             if (!SX::has(i)) continue;
@@ -226,11 +236,23 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
         } else {
             float ac[4], sv[4];
             screen_plane_score(r, mc, keep, ac, sv, smax, sthr, snan);
+            if constexpr (LL == LB) {
+                // later batches of the first one's size reuse its registers: in a second array they cost the six-field
+                // functors of screen_cells.hip a register
 #pragma unroll
-            for (int k0 = 0; k0 < NKMAX; k0 += LB) {
-                if (k0 >= g.nk) break;                     // (wave-uniform)
-                if (k0 > 0) load_lev(t, k0);
-                screen_plane_count<LB>(ac, sv, k0, g.nk, ql, cnt);
+                for (int k0 = 0; k0 < NKMAX; k0 += LB) {
+                    if (k0 >= g.nk) break;                 // (wave-uniform)
+                    if (k0 > 0) load_quads(t, k0, ql);
+                    screen_plane_count<LB>(ac, sv, k0, g.nk, ql, cnt);
+                }
+            } else {
+                screen_plane_count<LB>(ac, sv, 0, g.nk, ql, cnt);
+#pragma unroll
+                for (int k0 = LB; k0 < NKMAX; k0 += LL) {
+                    if (k0 >= g.nk) break;                 // (wave-uniform)
+                    load_late(t, k0);
+                    screen_plane_count<LL>(ac, sv, k0, g.nk, qm, cnt);
+                }
             }
         }
     };

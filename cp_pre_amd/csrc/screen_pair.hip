@@ -6,7 +6,7 @@
 // Nothing new runs on the device: the marches are screen_march.h's and screen_flat.h's, the functor is Paired<Fn>
 // (paired_functor.h, shared with pair_march.hip) over star_march.h's Linear1, Linear2, NSMomentum and MHDContinuity - views
 // [0, F) the truth set, [F, 2F) the prediction set, each half rounded to fp32 before the subtraction.  The host side of an
-// entry is screen_entries.h's: the entry hands the 2F views of both sets to the body of its kind with <Form, Paired,
+// entry is screen_entries.h's: the entry hands the 2F views of both sets (pair_views) to the body of its kind with <Form, Paired,
 // ScalarSets>, so every check of host_checks.h is made of every view of both sets; this object's flags are star_march.o's
 // (csrc/Makefile), so each half in registers is the residual the single-set pass would have stored.
 //
@@ -19,22 +19,6 @@
 #include "paired_functor.h"
 #include "../../include/cp_pre_screenpair.h"
 #include "screen_entries.h"
-
-namespace {
-
-// views [0, F) the set a, [F, 2F) the set b
-template <int F>
-Views pair_views(const pre_field_t *a, const pre_field_t *b)
-{
-    Views v = {{}, 2 * F};
-    for (int i = 0; i < F; ++i) {
-        v.fs[i] = &a[i];
-        v.fs[F + i] = &b[i];
-    }
-    return v;
-}
-
-}  // namespace
 
 extern "C" {
 

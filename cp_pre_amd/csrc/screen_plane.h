@@ -70,14 +70,19 @@ struct CellSets {
     static constexpr bool CELLS = true;
     long long qK, qT, qX;      // level, marched-plane and row strides of g.q in elements (the merged-row march has no rows)
 };
-// CellsBatch<Fn>: the level quads a thread holds at once.  NKMAX: all of a plane's quads are issued before its field loads
-// and counted after its functor; a functor whose instantiation would carry scratch with 16 more quads gets fewer (screen_cells.hip), and
-// the quads beyond the first batch are fetched after the functor, a batch at a time.
+// CellsBatch<Fn>: the level quads a thread holds ACROSS the functor.  NKMAX: all of a plane's quads are issued before its
+// field loads and counted after its functor; a functor whose instantiation would carry scratch with 16 more quads gets fewer
+// (screen_cells.hip, screen_cells_pair.hip), and the quads beyond that first batch are fetched after the functor, a batch at a
+// time.
+// CellsLate<Fn>: the size of those later batches.  After the functor its neighbourhood is dead, so a functor that has room
+// for ONE quad across its evaluation (the paired NS momentum: CellsBatch 1) can still take the other fifteen in one batch
+// and one wait; by default the later batches have the first one's size.  Whole batches: (NKMAX - CellsBatch) % CellsLate == 0.
 #ifndef PRE_SCREENCELLS_BATCH
 #define PRE_SCREENCELLS_BATCH 16
 #endif
 static_assert(PRE_SCREENCELLS_BATCH >= 1 && PRE_SCREENCELLS_BATCH <= NKMAX && NKMAX % PRE_SCREENCELLS_BATCH == 0, "whole batches");
 template <class Fn, class = void> struct CellsBatch { static constexpr int value = PRE_SCREENCELLS_BATCH; };
+template <class Fn, class = void> struct CellsLate { static constexpr int value = CellsBatch<Fn>::value; };
 
 // The same end of a plane for per-cell levels (screen_cells.hip): ql[k] is the quad of level k's field at the thread's four
 // cells, so hw = ql[k][j] * m[j], the product of pre_cov_levels_f32 with a level field (q_ld != 0); without a modulation

@@ -88,7 +88,7 @@ cell at ten alphas, and each is checked against the residual of every held-out p
 samples taken in groups (``sample_group()``) so that a group shares its level quads in an XCD's L2.  ``inside[k, b]`` counts
 ``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with one): ``emp_cov_levels``'s count with per-cell levels, per sample.
 Routes ``fused:cells_<kind>`` / ``fused:flat_cells_<kind>`` for the kinds of the first paragraph; the 1-D family (without
-``rows=True``, below), JOREK, ``minus=`` and every reason above keep the three-pass route (one ``CoverageLevels`` pass per
+``rows=True``, below), JOREK, ``minus=`` (without ``pair=True``, further below) and every reason above keep the three-pass route (one ``CoverageLevels`` pass per
 sample with the per-cell levels).  Without a call to these two the library is never loaded.
 
 The 1-D family has per-cell screens as well, asked for by ``rows=True`` on ``screen_cells`` / ``ScreenCells.add_slab``
@@ -106,6 +106,18 @@ inputs, float64 levels, a ``[BS,1,Nt,Nx]`` input, no unit-stride axis, a contigu
 different layouts, kernels off the star or requiring grad, ``declined by the library``); ``halo_x`` raises.  Row slabs with
 crops compose to the bits of the whole plane.  Without ``rows=True`` the family keeps ``fallback:1-D family: the marched
 axis is the batch`` and the library is never loaded; on a method outside the family the keyword has no effect.
+
+Per-cell sets for the data-driven score of the 2-D residuals - how every ``Marginal/*_Residuals_CP.py`` script validates its
+held-out pairs (``Marginal/NS_Residuals_CP.py:282-312``, ``Marginal/MHD_Residuals_CP.py:350-392``,
+``Marginal/Wave_Residuals_CP.py:219-254``: a quantile per cell at ten alphas on ``|r(y) - r(y_hat)|``, then ``r(y)`` inside
+``r(y_hat) ± qhat[k][cell]``) - are screened in one launch only where the caller asks for it: ``screen_cells(method, vars,
+qcells, minus=pred, pair=True)`` / ``ScreenCells.add_slab(..., minus=, pair=True)`` (``libcp_pre_screencellspair.so``,
+``include/cp_pre_screencellspair.h``: both marches above with the paired functor AND the level quads; the samples in groups of
+``sample_group_pair()``).  Routes ``fused:cells_pair_<kind>`` / ``fused:flat_cells_pair_<kind>`` for the kinds of
+``pair=True`` on ``screen``; the reasons that keep the three-pass route, their order, ``halo_x`` and the semantics (the
+one-sided test on ``d``) are that paragraph's, the level fields' layout and rim this one's predecessor's.  Without
+``pair=True`` a ``minus=`` call keeps ``fallback:minus=`` and the library is never loaded; ``pair=True`` without ``minus``
+has no effect, and ``rows=True`` with ``minus=`` is as before.
 
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
@@ -206,6 +218,9 @@ _PAIR_ROWS_ENTRY = "pre_screen1dpair_"
 # the per-cell screens of the 1-D family (opt-in, ``rows=True`` of ``screen_cells`` / ``ScreenCells``; with ``minus=`` its
 # paired entries), one more library: the prefix of its entries
 _CELLS_ROWS_ENTRY = "pre_screen1dcells_"
+# the per-cell screens of the data-driven scores (opt-in, ``pair=True`` with ``minus=`` on ``screen_cells`` / ``ScreenCells``;
+# the kinds of ``_PAIR_KINDS``), one more library: form -> prefix of its entries
+_CELLS_PAIR_ENTRY = {"": "pre_screencellspair_", "flat": "pre_screencellspair_flat_"}
 
 
 def _pair_mode(pair, minus):
@@ -368,6 +383,8 @@ class _Spec(Method):
         ``cells``: of its per-cell screen; form 'rows' has both at once)."""
         if cells and form == "rows":
             return _CELLS_ROWS_ENTRY + ("pair_" if pair else "") + self.rows_kind + "_f32"
+        if cells and pair:
+            return _CELLS_PAIR_ENTRY[form] + self.kind + "_f32"
         if cells:
             return _CELLS_ENTRY[form] + ("mhd" if self.kind in _MHD_EQ else self.kind) + "_f32"
         if pair:
@@ -381,14 +398,15 @@ class _Spec(Method):
         if cells and form == "rows":
             return "fused:rows_cells_" + ("pair_" if pair else "") + self.rows_kind
         if cells:
-            return "fused:" + _FORMS[form][2] + "cells_" + self.kind
+            return "fused:" + _FORMS[form][2] + "cells_" + ("pair_" if pair else "") + self.kind
         return "fused:" + _FORMS[form][2] + ("pair_" if pair else "") + (self.rows_kind if form == "rows" else self.kind)
 
     def launch(self, kernels, x, st, flags, form="", minus=None, cells=False):
         """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code.
         ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so`` for forms '' and 'flat',
         ``libcp_pre_screen1dpair.so`` for 'rows').  ``cells``: the per-cell screen (``libcp_pre_screencells.so`` for forms ''
-        and 'flat', ``libcp_pre_screen1dcells.so`` for 'rows', there with ``minus`` too; ``st`` is then its set descriptor)."""
+        and 'flat', with ``minus`` ``libcp_pre_screencellspair.so``; ``libcp_pre_screen1dcells.so`` for 'rows', there with
+        ``minus`` too; ``st`` is then its set descriptor)."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
         if minus is not None and form == "rows":
             sets = (_lib.ptr(x), _lib.iarr64(x.stride()), _lib.ptr(minus), _lib.iarr64(minus.stride()))
@@ -402,7 +420,8 @@ class _Spec(Method):
             views = [ctypes.byref(_lib.field(f[0])) if one else R._arr(f) for f in (fa, fb)]
             if one:
                 kernels = _dispatch.tap_args(*kernels)
-            fn = getattr(_lib.load_screenpair(), self.entry(form, True))
+            # (the per-cell paired library by its row of ``_lib``'s loader table: loaded on this route only)
+            fn = getattr(_lib._load("screencellspair") if cells else _lib.load_screenpair(), self.entry(form, True, cells))
             return fn(*views, *kernels, *self.scalars(), ctypes.byref(st), *fa[0].shape, flags, _lib.stream())
         kind = self.rows_kind if form == "rows" else self.kind
         if cells and form == "rows":
@@ -657,6 +676,12 @@ def sample_group_rows():
     return int(_lib.load_screen1dcells().pre_screen1dcells_sample_group())
 
 
+def sample_group_pair():
+    """Samples per group in the block order of the per-cell screens of the data-driven scores
+    (``pre_screencellspair_sample_group``): speed only."""
+    return int(_lib._load("screencellspair").pre_screencellspair_sample_group())
+
+
 def _check_cells(spec, vars, qcells, modulation, minus, crop, nk=None):
     """``_check_inputs`` for level fields: every error before any device work.  Returns (uncropped residual shape, crop,
     counted cells per sample); ``qcells`` has the uncropped extents or (``cropped`` in the caller) the cropped ones."""
@@ -676,17 +701,20 @@ class ScreenCells(Screen):
     Accumulation, ``crop``, ``halo_x`` and ``finish`` are ``Screen``'s: slabs compose to the bits of the whole grid."""
 
     def add_slab(self, method, vars_slab, qcells_slab, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None,
-                 rows=False):
+                 rows=False, pair=False):
         """``qcells_slab``: fp32 [nk, *uncropped residual extents of the slab] on the slab's device, shared by all samples
         (its values outside the counted region are never used); the other arguments as ``Screen.add_slab`` takes them.
         Level fields whose unit-stride axis is not the fields' are copied once into the matching layout, as the
-        modulation is.  ``minus`` keeps the three-pass route (``fallback:minus=``).  ``rows=True``: the opt-in per-cell
-        screen of the 1-D family (``crop`` of two axes; with ``minus`` its paired entries; module docstring); no effect on
-        any other method."""
+        modulation is.  ``minus`` keeps the three-pass route (``fallback:minus=``) unless ``pair=True``: the opt-in per-cell
+        screen of the data-driven score ``r(vars_slab) - r(minus)`` for the 2-D kinds with a paired screen (no effect
+        without ``minus``; under ``halo_x`` both sets must be Ny-contiguous device views with rows -1 and X in memory;
+        module docstring).  ``rows=True``: the opt-in per-cell screen of the 1-D family (``crop`` of two axes; with
+        ``minus`` its paired entries; module docstring); no effect on any other method."""
         global _last_route
         spec = method if isinstance(method, _Spec) else _Spec(method)
         rows = bool(rows) and spec.rows_kind is not None
-        pair = "rows" if rows and minus is not None else False  # (the paired entries of the rows form take ``minus``)
+        # (the paired entries of the rows form take ``minus``; the 2-D kinds take it where the caller asks with ``pair=True``)
+        pair = "rows" if rows and minus is not None else spec.rows_kind is None and minus is not None and bool(pair)
         shape, crop, cells = _check_cells(spec, vars_slab, qcells_slab, modulation_slab, minus, crop, self.nk)
         if tuple(qcells_slab.shape[1:]) != tuple(shape[1:]):
             raise ValueError(f"qcells has shape {tuple(qcells_slab.shape)}, expected {(self.nk,) + tuple(shape[1:])}: the "
@@ -695,7 +723,9 @@ class ScreenCells(Screen):
             raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
         if _dev_key(vars_slab.device) != _dev_key(self.device):
             raise ValueError(f"slab on {vars_slab.device}, this Screen was made for {self.device}")
-        why, kernels = spec.prepare(vars_slab, minus, qcells_slab, modulation_slab)
+        if halo_x and pair is True and vars_slab.is_cuda:
+            R._check_minus(vars_slab, minus, device_view=True)
+        why, kernels = spec.prepare(vars_slab, minus, qcells_slab, modulation_slab, pair is True)
         if halo_x and not vars_slab.is_cuda:
             raise ValueError("halo_x needs a device-resident view of a larger grid (a staged copy has no halo rows)")
         if halo_x and why is not None and not spec.reads_halo():
@@ -704,7 +734,7 @@ class ScreenCells(Screen):
             why, kernels = spec.prepare_rows(vars_slab, minus, qcells_slab, modulation_slab, pair)
         flat = spec.kind is not None and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
         if flat:
-            why, kernels = spec.prepare_flat(vars_slab, minus, qcells_slab, modulation_slab)
+            why, kernels = spec.prepare_flat(vars_slab, minus, qcells_slab, modulation_slab, pair is True)
         if why is None:
             acc = self._buffers(vars_slab.device)
             mod, lev = modulation_slab, qcells_slab
@@ -752,7 +782,7 @@ class ScreenCells(Screen):
         self.cells += cells
 
 
-def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False, minus=None, rows=False):
+def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False, minus=None, rows=False, pair=False):
     """Screen the predictions ``vars`` against the per-cell sets ``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with a
     modulation) at every level k in one launch; the residual is never stored.  ``qcells``: fp32 ``[nk, *uncropped residual
     extents]`` on ``vars``' device, 1 <= nk <= 16.  ``boundary=False``: the counted cells are the interior ``[1:-1]`` of
@@ -760,7 +790,13 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
     taken from ``res[..., 1:-1, 1:-1, 1:-1]``; it is then padded once with NaN to the uncropped extents (one copy of nk
     sample-sized fields, in the fields' layout).  ``boundary=True``: every cell, uncropped extents only.  Inside the counted
     region a NaN level or a NaN residual puts the cell outside at that level, a negative level puts it outside, ``+inf``
-    puts it inside for every non-NaN residual.  ``minus`` (the data-driven score) keeps the three-pass route.
+    puts it inside for every non-NaN residual.  ``minus`` (the data-driven score) keeps the three-pass route unless
+    ``pair=True``: the opt-in per-cell screen of ``d = fl(fl(r(vars)) - fl(r(minus)))`` in one launch over both sets, for the
+    kinds with a paired screen (routes ``fused:cells_pair_<kind>`` / ``fused:flat_cells_pair_<kind>``): ``score = max |d| /
+    m``, ``inside[k] = #{|d| <= fl(qcells[k][cell] * m[cell])}`` - the one-sided test on the difference, NOT the reference's
+    two-sided form ``fl(pred - q) <= y <= fl(pred + q)`` on the two residual arrays; the two can differ in a cell within
+    rounding of the band's edge.  A caller who needs only the coverage totals keeps ``emp_cov_levels`` on the stored
+    difference (below).  Without ``minus`` the keyword has no effect.
     ``rows=True``: the opt-in per-cell screen of the 1-D family (``vars`` [BS,Nt,Nx] in either layout, ``qcells``
     [nk,Nt,Nx] or the cropped [nk,Nt-2,Nx-2]; routes ``fused:rows_cells_<kind>``); ``minus`` with it takes the paired
     entries, the one-sided test ``|r(vars) - r(minus)| <= qcells[k][cell] (* m)`` (``fused:rows_cells_pair_<kind>``).
@@ -775,7 +811,10 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
     takes slabs, and is 4-6 times faster than ten calls of the one-level trick, the other way to the same answer.
     The same holds for ``rows=True`` (Burgers on [8192,200,512], nk = 10): SLOWER than that route - 2.56
     against 2.06 ms Nx-fastest, 3.34 against 2.25 ms Nt-fastest, 4.63 against 3.07 ms for a pair - and 4.4-4.9 times faster
-    than ten one-level calls of the joint rows screen."""
+    than ten one-level calls of the joint rows screen.  And for ``minus=`` with ``pair=True`` (nk = 10): SLOWER
+    than the paired residual pass followed by one ``CoverageLevels`` pass - 90.7 against 61.4 ms for NS momentum on two
+    Nt-fastest [512,3,64,512,512] sets, 4.4 against 3.3 ms for the wave residual on two [512,32,256,256] sets - and 5.3-6.7
+    times faster than ten one-level calls of the paired joint screen."""
     spec = _Spec(residual_method)
     crop = (0,) * spec.nd if boundary else (1,) * spec.nd
     shape, _, _ = _check_cells(spec, vars, qcells, modulation, minus, crop)
@@ -787,7 +826,7 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
         rows_nt = bool(rows) and spec.rows_kind is not None and vars.dim() == 3 and vars.stride(2) != 1 and vars.stride(1) == 1
         qcells = _pad_levels(qcells, full, vars.is_cuda and (rows_nt or spec.nt_fastest(vars)))
     s = ScreenCells(shape[0], qcells.shape[0], vars.device)
-    s.add_slab(spec, vars, qcells, modulation, crop=crop, minus=minus, rows=rows)
+    s.add_slab(spec, vars, qcells, modulation, crop=crop, minus=minus, rows=rows, pair=pair)
     out = s.finish()
     if not vars.is_cuda:                                     # (staged inputs: the verdicts come home, as elsewhere)
         out.score, out.inside = out.score.to(vars.device), out.inside.to(vars.device)

@@ -72,6 +72,20 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                without ``rows=True`` - one ``CoverageLevels`` pass per sample - next to (F) on that batch.  Lines go to
                profiles/screen1dcells/screen_bench_cells1d.jsonl unless --out says otherwise
 
+    c3_rank8_ntfast_cells_pair / c2_wave_cells_pair / c2_wave_ntfast_cells_pair
+               the per-cell screen of the data-driven score r(a) - r(b) (``screen.ScreenCells(...).add_slab(minus=, pair=True)``:
+               ``libcp_pre_screencellspair.so``) at nk = 10 level fields, no modulation: NS momentum on two sets of memory
+               [512,3,512,512,64] seen through ``permute(0,1,4,2,3)`` (the second the first plus noise; 206 GB of fields: --div 2
+               halves the batch), and the wave residual on two [512,32,256,256] sets, Ny-fastest and (memory [512,256,256,32])
+               Nt-fastest.  Routes, alternated call by
+               call: (F) the fused launch, once per library of ``--cellspair-libs label=path,...`` (build variants of the batch
+               sizes and the sample group, ``make SCREENCELLSPAIR_BATCH= SCREENCELLSPAIR_LATE= SCREENCELLSPAIR_GROUP=``;
+               default: the package's own library); (B) nk one-level calls of the paired joint screen, the level field as its
+               modulation; (A) the paired residual pass into a buffer plus ONE marginal ``CoverageLevels`` pass with per-cell
+               levels, totals only; (C) the paired joint screen at nk scalar levels, the floor.  Then, on a batch of its own
+               of ``--parent-batch`` samples, (P) the three-pass route the package takes without ``pair=True`` next to (F) on
+               that batch.  Lines go to profiles/screencellspair/screen_bench_cellspair.jsonl unless --out says otherwise
+
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
@@ -513,6 +527,144 @@ def run_cells1d(name, args, dev):
     return line
 
 
+CELLSPAIR_CASES = {"c3_rank8_ntfast_cells_pair": "c3_rank8_ntfast", "c2_wave_cells_pair": "c2_wave",
+                   "c2_wave_ntfast_cells_pair": "c2_wave"}
+
+
+def run_cellspair(name, args, dev):
+    """One per-cell case of the data-driven score: (F) per library, (B), (A), (C) alternated, then (P) on its own small
+    batch; one JSON line."""
+    from cp_pre_amd import _lib
+    method, v, crop, halo_x, _, fbytes = case(CELLSPAIR_CASES[name], args.div, dev)
+    if name == "c2_wave_ntfast_cells_pair":
+        v = v.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    n = v.shape[0]
+    nt_fast = v.stride(-1) != 1
+    # the second set: the first plus noise, in the same layout (sample by sample: no third batch-sized tensor)
+    w = torch.empty_like(v)
+    for i in range(n):
+        w[i] = v[i] + 0.05 * torch.randn(v[i].shape, device=dev)
+    fbytes *= 2
+    shape = (n,) + tuple(v.shape[-3:])
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    if nt_fast:
+        out = torch.empty((n,) + shape[2:] + shape[1:2], dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+    reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
+
+    def paired_into():
+        return method(v, boundary=True, out=out, minus=w)
+    # level fields in the fields' layout: level k about (k + 1) / nk of twice the mean |d|, scattered per cell by +-50 %
+    paired_into()
+    scale = float(out[:min(n, 8)].abs().mean())
+    qc = torch.rand((NK,) + shape[1:], device=dev) + 0.5
+    qc *= (2.0 * scale / NK) * torch.arange(1, NK + 1, device=dev, dtype=torch.float32).reshape(NK, 1, 1, 1)
+    if nt_fast:
+        qc = qc.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    qs = torch.linspace(0.2, 2.0, NK, device=dev) * scale
+    one = torch.ones(1, device=dev)
+    # the libraries of (F): handles loaded once, swapped into the loader's cache before each call
+    libs = {}
+    if args.cellspair_libs:
+        for item in args.cellspair_libs.split(","):
+            label, path = item.split("=", 1)
+            _lib._screencellspair, _lib.SCREENCELLSPAIR_SO_PATH = None, os.path.abspath(path)
+            libs[label] = _lib.load_screencellspair()
+    else:
+        libs["package"] = _lib.load_screencellspair()
+
+    def fused_with(label, nb=None):
+        vb, wb = (v, w) if nb is None else (v[:nb], w[:nb])
+
+        def fused():
+            _lib._screencellspair = libs[label]
+            s = screen.ScreenCells(vb.shape[0], NK, dev)
+            s.add_slab(method, vb, qc, None, crop=crop, minus=wb, pair=True)
+            return s
+        return fused
+
+    def trick():                                             # (B)
+        outs = []
+        for k in range(NK):
+            s = screen.Screen(n, 1, dev)
+            s.add_slab(method, v, one, qc[k], crop=crop, minus=w, pair=True)
+            outs.append(s)
+        return outs
+
+    def curve():                                             # (A)
+        paired_into()
+        cov = pipeline.CoverageLevels(n, NK, dev)
+        cov.add_slab(out[reg], qc[(slice(None),) + reg[1:]])
+        return cov
+
+    def joint():                                             # (C)
+        s = screen.Screen(n, NK, dev)
+        s.add_slab(method, v, qs, None, crop=crop, minus=w, pair=True)
+        return s
+
+    fns = {"fused_" + label: fused_with(label) for label in libs}
+    got = {}
+    for k, f in fns.items():
+        got[k] = f().finish()
+        assert screen.last_route().startswith("fused:") and "cells_pair_" in screen.last_route(), screen.last_route()
+    route = screen.last_route()
+    first = got[next(iter(got))]
+    cov = curve()
+    tr = trick()
+    trick_route = screen.last_route()
+    torch.cuda.synchronize()
+    totals = first.inside.sum(dim=1)
+    line = {"case": name, "shape": list(v.shape), "sets": 2, "nk": NK, "route": route, "trick_route": trick_route,
+            "libraries": {label: int(lib.pre_screencellspair_sample_group()) for label, lib in libs.items()},
+            "every_library_bit_identical": all(torch.equal(o.inside, first.inside) and
+                                               torch.equal(o.score.view(torch.int32), first.score.view(torch.int32)) for o in got.values()),
+            "totals_equal_to_coverage_levels": bool(torch.equal(totals, cov.acc.to(totals.dtype))),
+            "counts_equal_to_one_level_trick": bool(torch.equal(first.inside, torch.cat([t.finish().inside for t in tr]))),
+            "coverage_curve": [round(float(c), 4) for c in first.coverage_marginal()]}
+    del got, tr, cov
+    fns.update({"trick_B": trick, "curve_A": curve, "joint_C": joint})
+    if args.only == "fused":
+        pick = [k for k in fns if k.startswith("fused_")]
+    elif args.only is not None:
+        raise SystemExit("--only fused is the one single-route run of the per-cell cases")
+    else:
+        pick = list(fns)
+    res = blocks_of([fns[k] for k in pick], args.reps, args.blocks, args.warmup)
+    cells = 1
+    for d in shape:
+        cells *= d
+    line.update({"cells": cells, "field_bytes_per_cell": fbytes, "level_bytes_per_cell": 4 * NK})
+    for k, (med, lo, hi) in zip(pick, res):
+        line[k + "_ms"] = round(med, 4)
+        line[k + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
+        line[k + "_block_spread"] = round(hi / lo, 4)
+        if k.startswith("fused_"):
+            line[k + "_fraction_of_8TBps_fields"] = round(cells * fbytes / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+            line[k + "_fraction_of_8TBps_fields_and_levels"] = round(cells * (fbytes + 4 * NK) / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+    if args.only is None and args.parent_batch > 0:
+        # (P) the three-pass route the package takes without pair=True, on a batch of its own: two residual passes, the
+        # stored difference, one CoverageLevels pass per sample.  The figure is of THAT batch; nothing is scaled
+        nb = min(n, args.parent_batch)
+        last = list(libs)[-1]
+
+        def parent():
+            s = screen.ScreenCells(nb, NK, dev)
+            s.add_slab(method, v[:nb], qc, None, crop=crop, minus=w[:nb])
+            return s
+        fused_small = fused_with(last, nb)
+        p = parent().finish()
+        line["parent_route"] = screen.last_route()
+        f = fused_small().finish()
+        line["parent_batch"] = nb
+        line["bit_identical_to_parent_route"] = bool(torch.equal(p.inside, f.inside)) and \
+            bool(torch.equal(p.score.view(torch.int32), f.score.view(torch.int32)))
+        line["counts_differ_from_parent_route_by_at_most"] = int((p.inside - f.inside).abs().max())
+        (pm, plo, phi), (fm, flo, fhi) = blocks_of([parent, fused_small], 1, 3, 0)
+        line.update({"parent_P_ms_at_parent_batch": round(pm, 4), "parent_P_ms_blocks_min_max": [round(plo, 4), round(phi, 4)],
+                     "fused_ms_at_parent_batch": round(fm, 4), "fused_ms_at_parent_batch_blocks_min_max": [round(flo, 4), round(fhi, 4)],
+                     "fused_at_parent_batch_library": last})
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
@@ -527,8 +679,11 @@ def main():
                     help="per-cell cases: G=path,... of libcp_pre_screencells.so builds to time as (F) (default: the package's)")
     ap.add_argument("--cells1d-libs", default=None,
                     help="per-cell cases of the 1-D family: G=path,... of libcp_pre_screen1dcells.so builds to time as (F)")
+    ap.add_argument("--cellspair-libs", default=None,
+                    help="per-cell cases of the data-driven score: label=path,... of libcp_pre_screencellspair.so builds to time as (F)")
     ap.add_argument("--parent-batch", type=int, default=64,
-                    help="per-cell cases of the 1-D family: samples of the batch (P), the three-pass route, is timed on (0: not at all)")
+                    help="per-cell cases of the 1-D family and of the data-driven score: samples of the batch (P), the three-pass "
+                         "route, is timed on (0: not at all)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in args.cases.split(","):
@@ -536,6 +691,15 @@ def main():
             path = args.out or os.path.join(ROOT, "profiles", "screen1dcells", "screen_bench_cells1d.jsonl")
             os.makedirs(os.path.dirname(path), exist_ok=True)
             txt = json.dumps(run_cells1d(name, args, dev))
+            print(txt, flush=True)
+            with open(path, "a") as f:
+                f.write(txt + "\n")
+            torch.cuda.empty_cache()
+            continue
+        if name in CELLSPAIR_CASES:
+            path = args.out or os.path.join(ROOT, "profiles", "screencellspair", "screen_bench_cellspair.jsonl")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            txt = json.dumps(run_cellspair(name, args, dev))
             print(txt, flush=True)
             with open(path, "a") as f:
                 f.write(txt + "\n")
