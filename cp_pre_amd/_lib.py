@@ -400,6 +400,19 @@ SCREENCELLSPAIR_SIGNATURES.update({
     _name.replace("pre_screenpair_", "pre_screencellspair_"): [_CELLS_DESC.get(_a, _a) for _a in _sig]
     for _name, _sig in SCREENPAIR_SIGNATURES.items() if _sig})
 
+# libcp_pre_screenjorekcells.so (include/cp_pre_screenjorekcells.h): the two 2-D screens against per-cell sets for the
+# reduced-MHD (JOREK) residuals: each entry takes its twin's arguments in libcp_pre_screenjorek.so with the set descriptor
+# swapped for the per-cell one (PreScreenCells / PreScreenCellsFlat reused)
+SCREENJOREKCELLS_SO_PATH = os.path.join(_HERE, "libcp_pre_screenjorekcells.so")
+PRE_SCREENJOREKCELLS_ABI_VERSION = 1
+_cellstail = [c_int64] * 4 + [c_int, c_void_p]                          # B, T, X, Y, flags, stream
+SCREENJOREKCELLS_SIGNATURES = {
+    "pre_screenjorekcells_abi_version": [],
+    "pre_screenjorekcells_sample_group": [],
+    "pre_screenjorekcells_f32": _jrk + [POINTER(PreScreenCells)] + _cellstail,
+    "pre_screenjorekcells_flat_f32": _jrk + [POINTER(PreScreenCellsFlat)] + _cellstail,
+}
+
 # libcp_pre_vjpflatmhd.so (include/cp_pre_vjpflatmhd.h): the entries of libcp_pre_vjpmhd.so for Nt-fastest views (the march of
 # libcp_pre_vjpflat.so), argument for argument
 VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
@@ -453,8 +466,10 @@ _LIBS_MORE = {
     "screen1dcells": ("_screen1dcells", "SCREEN1DCELLS_", "pre_screen1dcells_abi_version", "PRE_SCREEN1DCELLS_ABI_VERSION", ()),
     "screencellspair": ("_screencellspair", "SCREENCELLSPAIR_", "pre_screencellspair_abi_version",
                         "PRE_SCREENCELLSPAIR_ABI_VERSION", ()),
+    "screenjorekcells": ("_screenjorekcells", "SCREENJOREKCELLS_", "pre_screenjorekcells_abi_version",
+                         "PRE_SCREENJOREKCELLS_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = _screenjorekcells = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -583,6 +598,10 @@ def load_screen1dcells():
 
 def load_screencellspair():
     return _screencellspair or _load("screencellspair")
+
+
+def load_screenjorekcells():
+    return _screenjorekcells or _load("screenjorekcells")
 
 
 def require_gpu():

@@ -1,5 +1,5 @@
 // screen_entries.h - the host side of the 2-D calibrated-set screens, stated once for screen_march.hip, screen_flat.hip,
-// screen_pair.hip, screen_cells.hip, screen_cells_pair.hip and screen_jorek.hip: what an entry does between its arguments and its launch.  An entry
+// screen_pair.hip, screen_cells.hip, screen_cells_pair.hip, screen_jorek.hip and screen_jorek_cells.hip: what an entry does between its arguments and its launch.  An entry
 // of those files assembles the views its residual reads and forwards to one of the five bodies below (stencil3d, linear2,
 // ns_momentum, mhd, jorek), which is templated on what differs between the libraries:
 //   Form   NyForm (Ny-fastest fields, screen_march.h) or FlatForm (Nt-fastest fields, screen_flat.h);
@@ -90,7 +90,7 @@ template <class Fn> using Single = Fn;
 
 // ---- what is built ----------------------------------------------------------------------------------------------------
 // Every (form, set policy, functor<tap structure>) is built but the ones below: an instantiation with scratch is not built,
-// its tap structure returns PRE_E_UNSUPPORTED and the caller takes its three-pass route (resources.sh on the six files:
+// its tap structure returns PRE_E_UNSUPPORTED and the caller takes its three-pass route (resources.sh on the seven files:
 // scratch 0 throughout).  All of them are general stars (<2>) but the y-fixed paired NS momentum.
 template <class Form, class Sets, class Fn> struct Built : std::true_type {};
 // Ny-fastest, nk levels: the energy functor does not fit 256 registers with the epilogue (24-28 bytes of scratch)
@@ -144,6 +144,14 @@ Views mhd_views(int eq, const pre_field_t *f)
     if (eq == 0) return {{&f[0], &f[1], &f[2]}, 3};
     if (eq == 3) return {{&f[1], &f[2], &f[4], &f[5]}, 4};
     return {{&f[0], &f[1], &f[2], &f[3], &f[4], &f[5]}, 6};
+}
+
+// what a JOREK equation reads (screen_jorek.hip, screen_jorek_cells.hip): continuity rho, Phi and the radius, temperature
+// rho, Phi, T and the radius (an eq out of range, which its body declines, as temperature)
+Views jorek_views(int eq, const pre_field_t *f, const pre_field_t *Rb)
+{
+    if (eq == 0) return {{&f[0], &f[1], Rb}, 3};
+    return {{&f[0], &f[1], &f[2], Rb}, 4};
 }
 
 // two field sets of F views each (screen_pair.hip, screen_cells_pair.hip): views [0, F) the set a, [F, 2F) the set b

@@ -4,7 +4,7 @@
 //
 // Nothing new runs on the device: the marches are screen_march.h's and screen_flat.h's, the functors star_march.h's
 // JorekContinuity / JorekTemperature, which take the radius R as one more field of which only the centre value is read (no
-// LDS slot, no halo row for it).  The host side is screen_entries.h's body jorek, which takes the kernels, the four scalars
+// LDS slot, no halo row for it).  The host side is screen_entries.h's body jorek on its jorek_views, which takes the kernels, the four scalars
 // and the choice of the tap structure as pre_residual_jorek_f32 does (star_march.h: jorek_params), with the set descriptor in
 // place of the output - so the residual in registers is the one that pass would have stored, given this object's flags are
 // star_march.o's (csrc/Makefile).
@@ -15,18 +15,6 @@
 #include "screen_flat.h"
 #include "../../include/cp_pre_screenjorek.h"
 #include "screen_entries.h"
-
-namespace {
-
-// continuity reads rho, Phi and the radius, temperature rho, Phi, T and the radius (an eq out of range, which the body
-// declines, as temperature)
-Views jorek_views(int eq, const pre_field_t *f, const pre_field_t *Rb)
-{
-    if (eq == 0) return {{&f[0], &f[1], Rb}, 3};
-    return {{&f[0], &f[1], &f[2], Rb}, 4};
-}
-
-}  // namespace
 
 extern "C" {
 

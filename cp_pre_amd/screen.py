@@ -42,9 +42,12 @@ The reduced-MHD residuals (``JOREK.residual_continuity`` / ``residual_temperatur
 ``Screen.add_slab(..., jorek=True)`` (``libcp_pre_screenjorek.so``, ``include/cp_pre_screenjorek.h``: both marches above with
 the functors of ``pre_residual_jorek_f32``).  ``vars`` is the script's ``[BS,F,Nx,Ny,Nt]``; every layout decision is taken on
 its ``unstack_fields`` views ``[BS,Nt,Nx,Ny]``: the dense tensor the script holds is Nt-fastest (route
-``fused:flat_jorek_<eq>``), a view of memory ``[BS,F,Nt,Nx,Ny]`` is Ny-fastest (``fused:jorek_<eq>``).  The equations are
-evaluated with ``norms=False`` (``norms=True`` of the continuity equation cannot be reached through a bound method);
-``halo_x`` raises, as for every method whose residual pass reads no halo.  Without the keyword JOREK keeps the three-pass
+``fused:flat_jorek_<eq>``), a view of memory ``[BS,F,Nt,Nx,Ny]`` is Ny-fastest (``fused:jorek_<eq>``).  A bound method is
+evaluated with ``norms=False``; ``norms=True`` of the continuity equation is handed over as in ``losses``:
+``functools.partial(jorek.residual_continuity, norms=True)`` (no positional arguments, no other keyword; the scalars are
+``JOREK._coef(eq, norms)``, the route names the same, and the three-pass route calls the partial, so both routes evaluate
+the same form; without ``dx, dy, dt`` it raises the method's ``ValueError``, on the temperature equation the reference's
+exception, before any launch).  ``halo_x`` raises, as for every method whose residual pass reads no halo.  Without the keyword JOREK keeps the three-pass
 route (``fallback:no fused screen for JOREK``) and the library is never loaded.
 
 The data-driven score ``d = r(vars) - r(minus)`` - what every ``Joint/`` script calibrates on first and then validates on
@@ -88,7 +91,7 @@ cell at ten alphas, and each is checked against the residual of every held-out p
 samples taken in groups (``sample_group()``) so that a group shares its level quads in an XCD's L2.  ``inside[k, b]`` counts
 ``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with one): ``emp_cov_levels``'s count with per-cell levels, per sample.
 Routes ``fused:cells_<kind>`` / ``fused:flat_cells_<kind>`` for the kinds of the first paragraph; the 1-D family (without
-``rows=True``, below), JOREK, ``minus=`` (without ``pair=True``, further below) and every reason above keep the three-pass route (one ``CoverageLevels`` pass per
+``rows=True``, below), JOREK (without ``jorek=True``, further below), ``minus=`` (without ``pair=True``, further below) and every reason above keep the three-pass route (one ``CoverageLevels`` pass per
 sample with the per-cell levels).  Without a call to these two the library is never loaded.
 
 The 1-D family has per-cell screens as well, asked for by ``rows=True`` on ``screen_cells`` / ``ScreenCells.add_slab``
@@ -119,6 +122,18 @@ one-sided test on ``d``) are that paragraph's, the level fields' layout and rim 
 ``pair=True`` a ``minus=`` call keeps ``fallback:minus=`` and the library is never loaded; ``pair=True`` without ``minus``
 has no effect, and ``rows=True`` with ``minus=`` is as before.
 
+Per-cell sets for the JOREK residuals - how ``Marginal/JOREK_residuals_CP.py:297-311`` ends: per-cell q-hats at ten alphas,
+then which cells of ``residual_temperature(pred)`` lie inside ``[-qhat, +qhat]`` at each - are screened in one launch only
+where the caller asks for it: ``screen_cells(method, vars, qcells, jorek=True)`` / ``ScreenCells.add_slab(..., jorek=True)``
+(``libcp_pre_screenjorekcells.so``, ``include/cp_pre_screenjorekcells.h``: both marches above with the JOREK functors AND the
+level quads; the samples in groups of ``sample_group_jorek()``).  ``vars`` is ``[BS,3,Nx,Ny,Nt]``, ``qcells`` ``[nk,Nt,Nx,Ny]``
+(with ``boundary=False`` also the cropped ``[nk,Nt-2,Nx-2,Ny-2]``); levels and modulation are re-laid to the fields'
+unit-stride axis.  Routes ``fused:flat_cells_jorek_<eq>`` (the dense tensor) and ``fused:cells_jorek_<eq>`` (Ny-fastest field
+views); the reasons that keep the three-pass route are those of ``screen(..., jorek=True)``, ``len(R) != Ny`` and ``halo_x``
+raise before any launch, and ``minus=`` keeps ``fallback:minus=`` (two temperature sets are 8 views against the march's 6).
+The method may be the ``norms`` partial of the paragraph on JOREK above.  ``jorek=True`` on any other method is a
+``TypeError``; without the keyword JOREK keeps ``fallback:no fused screen for JOREK`` and the library is never loaded.
+
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
@@ -129,6 +144,7 @@ and ``cells``).
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -221,6 +237,9 @@ _CELLS_ROWS_ENTRY = "pre_screen1dcells_"
 # the per-cell screens of the data-driven scores (opt-in, ``pair=True`` with ``minus=`` on ``screen_cells`` / ``ScreenCells``;
 # the kinds of ``_PAIR_KINDS``), one more library: form -> prefix of its entries
 _CELLS_PAIR_ENTRY = {"": "pre_screencellspair_", "flat": "pre_screencellspair_flat_"}
+# the per-cell screens of the JOREK residuals (opt-in, ``jorek=True`` on ``screen_cells`` / ``ScreenCells``), one more library:
+# form -> entry point
+_JOREK_CELLS_ENTRY = {"": "pre_screenjorekcells_f32", "flat": "pre_screenjorekcells_flat_f32"}
 
 
 def _pair_mode(pair, minus):
@@ -237,8 +256,13 @@ class _Spec(Method):
     itself), ``rows_kind`` - the fused screen of the 1-D family ('stencil2d', 'burgers'; None: none), which ``kind`` and
     ``why`` do not speak of; ``eq`` (the MHD and JOREK equations) and ``ratio`` (``linear2``) as the launches take them.
     ``jorek=True`` on a bound ``JOREK.residual_continuity`` / ``residual_temperature`` resolves the opt-in kinds
-    ``jorek_continuity`` / ``jorek_temperature`` (``norms=False``): ``ops`` are the object's five operators, ``fields`` its
-    ``unstack_fields`` views; on anything else it is a ``TypeError``.  Without it JOREK has no fused kind, as before."""
+    ``jorek_continuity`` / ``jorek_temperature``: ``ops`` are the object's five operators, ``fields`` its ``unstack_fields``
+    views; on anything else it is a ``TypeError``.  With it the method may also be ``functools.partial(<bound JOREK
+    equation>, norms=<bool>)`` - the rule of ``losses``: no positional arguments, keywords within ``{"norms"}`` - and
+    ``norms`` is what ``JOREK._coef`` folds into the scalars of the launch; ``method`` stays the partial, so the three-pass
+    route evaluates the same form.  ``norms=True`` raises here what the equation itself would raise: without ``dx, dy, dt``
+    its ``ValueError``, on the temperature equation the reference's exception.  Without ``jorek`` JOREK has no fused kind,
+    as before."""
     KIND = {"op3d": "stencil3d", "wave": "stencil3d", "ns_momentum": "ns_momentum", "ns_continuity": "linear2",
             "mhd_gauss": "linear2", **{k: k for k in _MHD_EQ}}
     ROWS_KIND = {"op2d": "stencil2d", "advection": "stencil2d", "burgers": "burgers"}
@@ -246,12 +270,21 @@ class _Spec(Method):
            **dict.fromkeys(ROWS_KIND, "1-D family: the marched axis is the batch")}
 
     def __init__(self, method, jorek=False):
-        super().__init__(method)
+        bound, self.norms = method, False
+        if jorek and isinstance(method, functools.partial) and not method.args and set(method.keywords) <= {"norms"} and \
+                isinstance(getattr(method.func, "__self__", None), R.JOREK):
+            bound, self.norms = method.func, bool(method.keywords.get("norms", False))      # (the one keyword of the equations)
+        super().__init__(bound)
+        self.method = method
         if jorek:
-            kind = "jorek_" + getattr(method, "__name__", "")[len("residual_"):]
+            kind = "jorek_" + getattr(bound, "__name__", "")[len("residual_"):]
             if self.row != "jorek" or kind not in _JOREK_EQ:
                 raise TypeError("jorek=True takes a bound JOREK.residual_continuity or JOREK.residual_temperature")
             self.kind, self.why, self.eq, self.ops = kind, None, _JOREK_EQ[kind], tuple(self.obj._ops())
+            if self.norms and self.eq == 1:
+                raise Exception("Norm not implemented yet")      # (as ``JOREK.residual_temperature`` and the reference)
+            if self.norms and (self.obj.dx is None or self.obj.dy is None or self.obj.dt is None):
+                raise ValueError("norms=True needs dx, dy, dt")  # (as ``JOREK.residual_continuity``)
         if self.kind == "linear2":
             self.ratio, = self.scalars()
         elif self.kind in _MHD_EQ:
@@ -264,7 +297,7 @@ class _Spec(Method):
 
     def scalars(self):
         if self.kind in _JOREK_EQ:
-            return (_lib.farr(self.obj._coef(self.eq)),)          # (norms=False: what a bound method evaluates)
+            return (_lib.farr(self.obj._coef(self.eq, self.norms)),)   # (norms: a ``functools.partial``'s, else False)
         return super().scalars()
 
     def view(self, x):
@@ -385,6 +418,8 @@ class _Spec(Method):
             return _CELLS_ROWS_ENTRY + ("pair_" if pair else "") + self.rows_kind + "_f32"
         if cells and pair:
             return _CELLS_PAIR_ENTRY[form] + self.kind + "_f32"
+        if cells and self.kind in _JOREK_EQ:
+            return _JOREK_CELLS_ENTRY[form]
         if cells:
             return _CELLS_ENTRY[form] + ("mhd" if self.kind in _MHD_EQ else self.kind) + "_f32"
         if pair:
@@ -406,7 +441,7 @@ class _Spec(Method):
         ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so`` for forms '' and 'flat',
         ``libcp_pre_screen1dpair.so`` for 'rows').  ``cells``: the per-cell screen (``libcp_pre_screencells.so`` for forms ''
         and 'flat', with ``minus`` ``libcp_pre_screencellspair.so``; ``libcp_pre_screen1dcells.so`` for 'rows', there with
-        ``minus`` too; ``st`` is then its set descriptor)."""
+        ``minus`` too, ``libcp_pre_screenjorekcells.so`` for the JOREK kinds; ``st`` is then its set descriptor)."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
         if minus is not None and form == "rows":
             sets = (_lib.ptr(x), _lib.iarr64(x.stride()), _lib.ptr(minus), _lib.iarr64(minus.stride()))
@@ -426,6 +461,8 @@ class _Spec(Method):
         kind = self.rows_kind if form == "rows" else self.kind
         if cells and form == "rows":
             lib = _lib.load_screen1dcells()
+        elif cells and kind in _JOREK_EQ:
+            lib = _lib.load_screenjorekcells()                   # (loaded on this route only)
         else:
             lib = _lib.load_screencells() if cells else getattr(_lib, "load_screenjorek" if kind in _JOREK_EQ else _FORMS[form][0])()
         if form == "rows":
@@ -682,6 +719,12 @@ def sample_group_pair():
     return int(_lib._load("screencellspair").pre_screencellspair_sample_group())
 
 
+def sample_group_jorek():
+    """Samples per group in the block order of the per-cell screens of the JOREK residuals
+    (``pre_screenjorekcells_sample_group``): speed only."""
+    return int(_lib.load_screenjorekcells().pre_screenjorekcells_sample_group())
+
+
 def _check_cells(spec, vars, qcells, modulation, minus, crop, nk=None):
     """``_check_inputs`` for level fields: every error before any device work.  Returns (uncropped residual shape, crop,
     counted cells per sample); ``qcells`` has the uncropped extents or (``cropped`` in the caller) the cropped ones."""
@@ -701,7 +744,7 @@ class ScreenCells(Screen):
     Accumulation, ``crop``, ``halo_x`` and ``finish`` are ``Screen``'s: slabs compose to the bits of the whole grid."""
 
     def add_slab(self, method, vars_slab, qcells_slab, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None,
-                 rows=False, pair=False):
+                 jorek=False, rows=False, pair=False):
         """``qcells_slab``: fp32 [nk, *uncropped residual extents of the slab] on the slab's device, shared by all samples
         (its values outside the counted region are never used); the other arguments as ``Screen.add_slab`` takes them.
         Level fields whose unit-stride axis is not the fields' are copied once into the matching layout, as the
@@ -709,9 +752,11 @@ class ScreenCells(Screen):
         screen of the data-driven score ``r(vars_slab) - r(minus)`` for the 2-D kinds with a paired screen (no effect
         without ``minus``; under ``halo_x`` both sets must be Ny-contiguous device views with rows -1 and X in memory;
         module docstring).  ``rows=True``: the opt-in per-cell screen of the 1-D family (``crop`` of two axes; with
-        ``minus`` its paired entries; module docstring); no effect on any other method."""
+        ``minus`` its paired entries; module docstring); no effect on any other method.  ``jorek=True``: the opt-in per-cell
+        screen of the JOREK residuals (``_Spec``; a method given as a ``_Spec`` has decided already): ``vars_slab``
+        [BS,3,Nx,Ny,Nt], ``qcells_slab`` [nk,Nt,Nx,Ny]; ``halo_x`` raises and ``minus`` keeps the three-pass route."""
         global _last_route
-        spec = method if isinstance(method, _Spec) else _Spec(method)
+        spec = method if isinstance(method, _Spec) else _Spec(method, jorek)
         rows = bool(rows) and spec.rows_kind is not None
         # (the paired entries of the rows form take ``minus``; the 2-D kinds take it where the caller asks with ``pair=True``)
         pair = "rows" if rows and minus is not None else spec.rows_kind is None and minus is not None and bool(pair)
@@ -726,6 +771,10 @@ class ScreenCells(Screen):
         if halo_x and pair is True and vars_slab.is_cuda:
             R._check_minus(vars_slab, minus, device_view=True)
         why, kernels = spec.prepare(vars_slab, minus, qcells_slab, modulation_slab, pair is True)
+        if spec.kind in _JOREK_EQ and minus is not None:
+            why = "minus="                                        # (two temperature sets are 8 views against the march's 6)
+        if halo_x and spec.kind in _JOREK_EQ:
+            why = why or "halo_x"                                 # (no pass of the JOREK residuals reads halo rows: raises below)
         if halo_x and not vars_slab.is_cuda:
             raise ValueError("halo_x needs a device-resident view of a larger grid (a staged copy has no halo rows)")
         if halo_x and why is not None and not spec.reads_halo():
@@ -735,6 +784,8 @@ class ScreenCells(Screen):
         flat = spec.kind is not None and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
         if flat:
             why, kernels = spec.prepare_flat(vars_slab, minus, qcells_slab, modulation_slab, pair is True)
+            if spec.kind in _JOREK_EQ and minus is not None:
+                why = "minus="
         if why is None:
             acc = self._buffers(vars_slab.device)
             mod, lev = modulation_slab, qcells_slab
@@ -782,7 +833,8 @@ class ScreenCells(Screen):
         self.cells += cells
 
 
-def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False, minus=None, rows=False, pair=False):
+def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False, minus=None, jorek=False, rows=False,
+                 pair=False):
     """Screen the predictions ``vars`` against the per-cell sets ``|r| <= qcells[k][cell]`` (``* modulation[cell]`` with a
     modulation) at every level k in one launch; the residual is never stored.  ``qcells``: fp32 ``[nk, *uncropped residual
     extents]`` on ``vars``' device, 1 <= nk <= 16.  ``boundary=False``: the counted cells are the interior ``[1:-1]`` of
@@ -814,8 +866,15 @@ def screen_cells(residual_method, vars, qcells, modulation=None, boundary=False,
     than ten one-level calls of the joint rows screen.  And for ``minus=`` with ``pair=True`` (nk = 10): SLOWER
     than the paired residual pass followed by one ``CoverageLevels`` pass - 90.7 against 61.4 ms for NS momentum on two
     Nt-fastest [512,3,64,512,512] sets, 4.4 against 3.3 ms for the wave residual on two [512,32,256,256] sets - and 5.3-6.7
-    times faster than ten one-level calls of the paired joint screen."""
-    spec = _Spec(residual_method)
+    times faster than ten one-level calls of the paired joint screen.
+    ``jorek=True``: the opt-in per-cell screen of ``JOREK.residual_continuity`` / ``residual_temperature`` (or the ``norms``
+    partial of either; ``vars`` [BS,3,Nx,Ny,Nt], ``qcells`` [nk,Nt,Nx,Ny] or the cropped [nk,Nt-2,Nx-2,Ny-2], ``modulation``
+    [Nt,Nx,Ny]; routes ``fused:flat_cells_jorek_<eq>`` / ``fused:cells_jorek_<eq>``; ``minus=`` keeps ``fallback:minus=``); on
+    any other method a ``TypeError``.  Measured ([96,3,256,256,40] dense, nk = 10): SLOWER than
+    ``pre_residual_jorek_f32`` followed by one ``CoverageLevels`` pass - 1.57 against 1.27 ms for the temperature equation,
+    1.45 against 1.09 ms for the continuity equation - and 6.6-6.7 times faster than ten one-level calls of ``screen(...,
+    jorek=True)``; the library takes the level quads in batches of 4, 26-28 % faster than all 16 held across the functor."""
+    spec = _Spec(residual_method, jorek)
     crop = (0,) * spec.nd if boundary else (1,) * spec.nd
     shape, _, _ = _check_cells(spec, vars, qcells, modulation, minus, crop)
     full, cropped = tuple(shape[1:]), tuple(n - 2 * c for n, c in zip(shape[1:], crop))

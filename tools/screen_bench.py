@@ -86,6 +86,17 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                of ``--parent-batch`` samples, (P) the three-pass route the package takes without ``pair=True`` next to (F) on
                that batch.  Lines go to profiles/screencellspair/screen_bench_cellspair.jsonl unless --out says otherwise
 
+    jorek_temperature_ntfast_cells / jorek_continuity_ntfast_cells
+               the per-cell screen of the JOREK residuals (``screen.ScreenCells(...).add_slab(jorek=True)``:
+               ``libcp_pre_screenjorekcells.so``) at the shape of the two cases above, nk = 10 level fields, no modulation.
+               Routes, alternated call by call: (F) the fused launch, once per library of ``--cellsjorek-libs
+               label=path,...`` (build variants of the batch size and the sample group, ``make SCREENJOREKCELLS_BATCH=
+               SCREENJOREKCELLS_GROUP=``; default: the package's own library); (B)
+               ``pre_residual_jorek_f32`` followed by ONE marginal ``CoverageLevels`` pass with per-cell levels, totals
+               only; (T) nk one-level calls of ``screen(..., jorek=True)``, the level field as its modulation, which
+               deliver the same per-sample answer.  Lines go to profiles/screenjorekcells/screen_bench_cellsjorek.jsonl
+               unless --out says otherwise
+
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
@@ -665,6 +676,97 @@ def run_cellspair(name, args, dev):
     return line
 
 
+CELLSJOREK_CASES = {"jorek_temperature_ntfast_cells": "jorek_temperature_ntfast",
+                    "jorek_continuity_ntfast_cells": "jorek_continuity_ntfast"}
+
+
+def run_cellsjorek(name, args, dev):
+    """One per-cell JOREK case: (F) per library, (B), (T) alternated; one JSON line."""
+    from cp_pre_amd import _lib
+    method, v, crop, _, residual_into, fbytes = case(CELLSJOREK_CASES[name], args.div, dev)
+    n = v.shape[0]
+    shape = (n, v.shape[4], v.shape[2], v.shape[3])          # the field views [BS,Nt,Nx,Ny] of vars [BS,F,Nx,Ny,Nt]
+    reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
+    # level fields in the fields' layout (memory [nk,Nx,Ny,Nt]): level k about (k + 1) / nk of twice the mean |r|, scattered
+    # per cell by +-50 %
+    scale = float(residual_into(None)[:min(n, 8)].abs().mean())
+    qc = torch.rand((NK,) + shape[1:], device=dev) + 0.5
+    qc *= (2.0 * scale / NK) * torch.arange(1, NK + 1, device=dev, dtype=torch.float32).reshape(NK, 1, 1, 1)
+    qc = qc.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    one = torch.ones(1, device=dev)
+    # the libraries of (F): handles loaded once, swapped into the loader's cache before each call
+    libs = {}
+    if args.cellsjorek_libs:
+        for item in args.cellsjorek_libs.split(","):
+            label, path = item.split("=", 1)
+            _lib._screenjorekcells, _lib.SCREENJOREKCELLS_SO_PATH = None, os.path.abspath(path)
+            libs[label] = _lib.load_screenjorekcells()
+    else:
+        libs["package"] = _lib.load_screenjorekcells()
+
+    def fused_with(label):
+        def fused():
+            _lib._screenjorekcells = libs[label]
+            s = screen.ScreenCells(n, NK, dev)
+            s.add_slab(method, v, qc, None, crop=crop, jorek=True)
+            return s
+        return fused
+
+    def curve():                                             # (B)
+        res = residual_into(None)
+        cov = pipeline.CoverageLevels(n, NK, dev)
+        cov.add_slab(res[reg], qc[(slice(None),) + reg[1:]])
+        return cov
+
+    def ten():                                               # (T)
+        outs = []
+        for k in range(NK):
+            s = screen.Screen(n, 1, dev)
+            s.add_slab(method, v, one, qc[k], crop=crop, jorek=True)
+            outs.append(s)
+        return outs
+
+    fns = {"fused_" + label: fused_with(label) for label in libs}
+    got = {}
+    for k, f in fns.items():
+        got[k] = f().finish()
+        assert screen.last_route().startswith("fused:flat_cells_jorek_"), screen.last_route()
+    route = screen.last_route()
+    first = got[next(iter(got))]
+    cov = curve()
+    tr = ten()
+    ten_route = screen.last_route()
+    torch.cuda.synchronize()
+    totals = first.inside.sum(dim=1)
+    line = {"case": name, "shape": list(v.shape), "nk": NK, "route": route, "ten_route": ten_route,
+            "libraries": {label: int(lib.pre_screenjorekcells_sample_group()) for label, lib in libs.items()},
+            "every_library_bit_identical": all(torch.equal(o.inside, first.inside) and
+                                               torch.equal(o.score.view(torch.int32), first.score.view(torch.int32)) for o in got.values()),
+            "totals_equal_to_coverage_levels": bool(torch.equal(totals, cov.acc.to(totals.dtype))),
+            "counts_equal_to_ten_one_level_calls": bool(torch.equal(first.inside, torch.cat([t.finish().inside for t in tr]))),
+            "coverage_curve": [round(float(c), 4) for c in first.coverage_marginal()]}
+    del got, tr, cov
+    fns.update({"residual_then_coverage_B": curve, "ten_one_level_T": ten})
+    if args.only == "fused":
+        pick = [k for k in fns if k.startswith("fused_")]
+    elif args.only is not None:
+        raise SystemExit("--only fused is the one single-route run of the per-cell cases")
+    else:
+        pick = list(fns)
+    res = blocks_of([fns[k] for k in pick], args.reps, args.blocks, args.warmup)
+    cells = 1
+    for d in shape:
+        cells *= d
+    line.update({"cells": cells, "field_bytes_per_cell": fbytes, "level_bytes_per_cell": 4 * NK})
+    for k, (med, lo, hi) in zip(pick, res):
+        line[k + "_ms"] = round(med, 4)
+        line[k + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
+        line[k + "_block_spread"] = round(hi / lo, 4)
+        if k.startswith("fused_"):
+            line[k + "_fraction_of_8TBps_fields"] = round(cells * fbytes / (med * 1e-3) / 1e12 / HBM_TBPS, 3)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
@@ -681,6 +783,8 @@ def main():
                     help="per-cell cases of the 1-D family: G=path,... of libcp_pre_screen1dcells.so builds to time as (F)")
     ap.add_argument("--cellspair-libs", default=None,
                     help="per-cell cases of the data-driven score: label=path,... of libcp_pre_screencellspair.so builds to time as (F)")
+    ap.add_argument("--cellsjorek-libs", default=None,
+                    help="per-cell JOREK cases: label=path,... of libcp_pre_screenjorekcells.so builds to time as (F)")
     ap.add_argument("--parent-batch", type=int, default=64,
                     help="per-cell cases of the 1-D family and of the data-driven score: samples of the batch (P), the three-pass "
                          "route, is timed on (0: not at all)")
@@ -691,6 +795,15 @@ def main():
             path = args.out or os.path.join(ROOT, "profiles", "screen1dcells", "screen_bench_cells1d.jsonl")
             os.makedirs(os.path.dirname(path), exist_ok=True)
             txt = json.dumps(run_cells1d(name, args, dev))
+            print(txt, flush=True)
+            with open(path, "a") as f:
+                f.write(txt + "\n")
+            torch.cuda.empty_cache()
+            continue
+        if name in CELLSJOREK_CASES:
+            path = args.out or os.path.join(ROOT, "profiles", "screenjorekcells", "screen_bench_cellsjorek.jsonl")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            txt = json.dumps(run_cellsjorek(name, args, dev))
             print(txt, flush=True)
             with open(path, "a") as f:
                 f.write(txt + "\n")
