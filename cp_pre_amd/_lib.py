@@ -413,6 +413,31 @@ SCREENJOREKCELLS_SIGNATURES = {
     "pre_screenjorekcells_flat_f32": _jrk + [POINTER(PreScreenCellsFlat)] + _cellstail,
 }
 
+# libcp_pre_screenstats.so (include/cp_pre_screenstats.h): per-sample statistics of the residual (sum r, sum |r|, sum r^2 in
+# float64, max |r|) in one launch that stores no residual: each entry takes its twin's arguments in libcp_pre_screen.so /
+# libcp_pre_screenflat.so / libcp_pre_screen1d.so with the set descriptor swapped for the statistics one
+SCREENSTATS_SO_PATH = os.path.join(_HERE, "libcp_pre_screenstats.so")
+PRE_SCREENSTATS_ABI_VERSION = 1
+PRE_SCREENSTATS_FORM = {"": 0, "flat": 1, "rows": 2}                   # form of the fused screen -> PRE_SCREENSTATS_FORM_*
+
+
+class PreScreenStats(ctypes.Structure):
+    """``pre_screenstats_t``: the crop, the accumulators (bits of max |r| [B], float64 sums [3][sum_ld]) and the workspace."""
+    _fields_ = [("ct", c_int), ("cx", c_int), ("cy", c_int), ("max_abs", c_void_p), ("sums", c_void_p), ("sum_ld", c_int64),
+                ("workspace", c_void_p), ("workspace_len", c_int64)]
+
+
+_STATS_DESC = {POINTER(PreScreen): POINTER(PreScreenStats), POINTER(PreScreenFlat): POINTER(PreScreenStats)}
+SCREENSTATS_SIGNATURES = {
+    "pre_screenstats_abi_version": [],
+    "pre_screenstats_workspace_len": [c_int] + [c_int64] * 4,
+    **{_name.replace(_old, _new): [_STATS_DESC.get(_a, _a) for _a in _sig]
+       for _sigs, _old, _new in ((SCREEN_SIGNATURES, "pre_screen_", "pre_screenstats_"),
+                                 (SCREENFLAT_SIGNATURES, "pre_screenflat_", "pre_screenstats_flat_"),
+                                 (SCREEN1D_SIGNATURES, "pre_screen1d_", "pre_screenstats_rows_"))
+       for _name, _sig in _sigs.items() if _sig},
+}
+
 # libcp_pre_vjpflatmhd.so (include/cp_pre_vjpflatmhd.h): the entries of libcp_pre_vjpmhd.so for Nt-fastest views (the march of
 # libcp_pre_vjpflat.so), argument for argument
 VJPFLATMHD_SO_PATH = os.path.join(_HERE, "libcp_pre_vjpflatmhd.so")
@@ -468,8 +493,10 @@ _LIBS_MORE = {
                         "PRE_SCREENCELLSPAIR_ABI_VERSION", ()),
     "screenjorekcells": ("_screenjorekcells", "SCREENJOREKCELLS_", "pre_screenjorekcells_abi_version",
                          "PRE_SCREENJOREKCELLS_ABI_VERSION", ()),
+    "screenstats": ("_screenstats", "SCREENSTATS_", "pre_screenstats_abi_version", "PRE_SCREENSTATS_ABI_VERSION",
+                    ("pre_screenstats_workspace_len",)),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = _screenjorekcells = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = _screenjorekcells = _screenstats = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -602,6 +629,10 @@ def load_screencellspair():
 
 def load_screenjorekcells():
     return _screenjorekcells or _load("screenjorekcells")
+
+
+def load_screenstats():
+    return _screenstats or _load("screenstats")
 
 
 def require_gpu():

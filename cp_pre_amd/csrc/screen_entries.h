@@ -118,6 +118,13 @@ template <class Form> struct Built<Form, CellSets, PairedMHDContinuity<2>> : std
 template <> struct Built<NyForm, CellSets, PairedNS<1>> : std::false_type {};
 template <> struct Built<FlatForm, CellSets, PairedNS<4>> : std::false_type {};
 
+// per-sample statistics (screen_stats.hip): no level and no modulation registers, but three fp64 accumulators per thread (six
+// registers, where the counts of the level screens sit in scalar ones), and the general stars of the two six-field functors do
+// not fit with them in either form: the momentum functor 12 bytes of scratch Ny-fastest (all three tiles) and 24 Nt-fastest,
+// the energy functor 44-52 and 88
+template <class Form> struct Built<Form, StatSets, MHDMomentum<2>> : std::false_type {};
+template <class Form> struct Built<Form, StatSets, MHDEnergy<2>> : std::false_type {};
+
 template <class Form, class Fn, class P, class Sets>
 int launch_built(typename Form::Geom &g, const P &prm, hipStream_t st, const Sets &sets)
 {

@@ -35,6 +35,7 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets
 {
     constexpr int F = Fn::F;
     constexpr bool CELLS = Sets::CELLS;
+    constexpr bool STATS = IsStats<Sets>::value;   // (per-sample statistics: no levels, no modulation, screen_plane.h)
     constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held across the functor ...
     constexpr int LL = CellsLate<Fn>::value;       //  ... and per batch fetched after it)
     static_assert(LB >= 1 && LB <= NKMAX && (LB == NKMAX || (LL >= 1 && (NKMAX - LB) % LL == 0)), "whole batches");
@@ -45,6 +46,7 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets
     __shared__ unsigned int red[NKMAX + 1][FLAT_NW];
     const int q = threadIdx.x;
     unsigned Lb = xcd_remap(blockIdx.x, gridDim.x);
+    [[maybe_unused]] const unsigned slot = Lb;     // (statistics: this workgroup's slot of the workspace)
     // per-cell sets: a group of CELLS_G samples is the fastest index, so the workgroups an XCD runs together (contiguous in
     // Lb) read the same level quads and find them in its L2; the last group is partial when B % CELLS_G != 0
     const int bl = CELLS ? Lb % CELLS_G : 0;
@@ -60,7 +62,11 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets
     // the planes this workgroup evaluates: its segment, less the planes outside the counted region
     const int t0 = max(ts * g.tSeg, g.cT);
     const int t1 = min(min(ts * g.tSeg + g.tSeg, g.T), g.T - g.cT);
-    if (t0 >= t1) return;                          // (workgroup-uniform: nothing of this segment is counted)
+    if (t0 >= t1) {                                // (workgroup-uniform: nothing of this segment is counted)
+        if constexpr (STATS)
+            if (q == 0) stats_store(sets, slot, 0.0, 0.0, 0.0);                 // (the second launch reads every slot)
+        return;
+    }
 
     const int m0 = ch * NT * 4, m = m0 + 4 * q;
     const bool inb = m < L;                        // (whole quads only: L % 4 == 0, checked by the host)
@@ -131,7 +137,9 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets
     // the modulation quad of plane t: only by threads with a counted cell and only for planes of this segment (a rim
     // cell that shares its quad with counted ones is masked by the select)
     auto load_mod = [&](int t, float4 &dst) __attribute__((always_inline)) {
-        if (g.mod && anykeep && t < t1) {
+        if constexpr (STATS) {
+            dst = f4(1.0f);                        // (no modulation under this policy: no registers for it either)
+        } else if (g.mod && anykeep && t < t1) {
             const float *p = g.mod + (long long)t * g.mT;
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
                 __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, -1, 0x00020000), (int)voff, 0, 0);
@@ -173,12 +181,13 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets
     unsigned int cnt[NKMAX];
 #pragma unroll
     for (int k = 0; k < NKMAX; ++k) {
-        if constexpr (CELLS) qk[k] = 0.f;
+        if constexpr (CELLS || STATS) qk[k] = 0.f;
         else qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
         cnt[k] = 0;
     }
     float smax = 0.f, sthr = 0.f;
     bool snan = false;
+    [[maybe_unused]] double sacc[3] = {0.0, 0.0, 0.0};      // (statistics: sum r, sum |r|, sum r^2 of this thread's cells)
 
     auto step = [&](int t, float4(&P)[F], float4(&C)[F], float4(&N)[F], float4(&D)[F], FlatHalo<F> &hc, FlatHalo<F> &hn,
                     float4 &mc, float4 &mn) __attribute__((always_inline)) {
@@ -232,7 +241,9 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets
             n[i].yp = make_float4(rok[0] ? C[i].y : 0.f, rok[1] ? C[i].z : 0.f, rok[2] ? C[i].w : 0.f, rok[3] ? rgt : 0.f);
         }
         const float4 r = Fn::eval(n, prm);
-        if constexpr (!CELLS) {
+        if constexpr (STATS) {
+            stats_plane(r, keep, sacc, smax, snan);
+        } else if constexpr (!CELLS) {
             screen_plane(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
         } else if constexpr (LB == NKMAX) {
             screen_plane_cells(r, mc, keep, g.nk, ql, cnt, smax, sthr, snan);
@@ -284,6 +295,29 @@ screen_flat_kernel(const FGeom g, const typename Fn::Params prm, const Sets sets
     for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o));
     const unsigned int ubits = __ballot(snan) ? 0x7fc00000u : __float_as_uint(smax);
     const int wv = q >> 6, nw = NT >> 6;
+    if constexpr (STATS) {
+        // statistics: the maximum as below; the sums by shuffles, then LDS in wave order, then ONE slot of the workspace
+        __shared__ double dred[3][FLAT_NW];
+        stats_wave(sacc);
+        if ((q & 63) == 0) {
+            red[0][wv] = ubits;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dred[j][wv] = sacc[j];
+        }
+        __syncthreads();
+        if (q == 0) {
+            unsigned int v = 0;
+            double s[3] = {0.0, 0.0, 0.0};
+            for (int w = 0; w < nw; ++w) {
+                v = max(v, red[0][w]);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) s[j] += dred[j][w];
+            }
+            if (v) atomicMax(g.score + b, v);
+            stats_store(sets, slot, s[0], s[1], s[2]);
+        }
+        return;
+    }
     if ((q & 63) == 0) {
         red[0][wv] = ubits;
 #pragma unroll
@@ -315,9 +349,20 @@ int launch_screen_flat(FGeom &g, const typename Fn::Params &prm, hipStream_t st,
     const long long nb = Sets::CELLS ? ((long long)g.B + CELLS_G - 1) / CELLS_G * CELLS_G : g.B;
     const int rc = flat_split(screen_flat_kernel<Fn, Sets>, nt, per_cu, g, nb * g.nCh, g.T, &grid);
     if (rc) return rc;
+    if constexpr (IsStats<Sets>::value)
+        if (!stats_room(sets, grid)) return PRE_E_NULL;                    // (never with the length the query entry gives)
     hipLaunchKernelGGL((screen_flat_kernel<Fn, Sets>), dim3(grid), dim3(nt), 0, st, g, prm, sets);
     PRE_LAUNCH_CHECK();
+    if constexpr (IsStats<Sets>::value) return stats_finish(sets, g.B, (long long)grid / g.B, st);
     return PRE_OK;
+}
+
+// statistics: an upper bound of the workgroups per sample of any launch_screen_flat on the logical (T, X, Y), from the shape
+// alone - chunks no narrower than 256 quads (flat_chunk) and marches of Nx no shorter than min(X, 8) planes (pick_tseg)
+inline long long stats_slots_flat(long long T, long long X, long long Y)
+{
+    const long long quads = (Y * T + 3) / 4;
+    return ((quads + 255) / 256) * ((X + 7) / 8);
 }
 
 // the tap structures an Nt-fastest view runs (relabeled_mode: the reference's construction, the y-fixed one, the general star)

@@ -28,6 +28,8 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
 {
     constexpr int F = Fn::F;
     constexpr bool CELLS = Sets::CELLS;
+    constexpr bool STATS = IsStats<Sets>::value;   // (per-sample statistics: no levels, no modulation, screen_plane.h)
+    constexpr bool LACC = STATS && StatsLdsAcc<Fn>::value;      // (... its accumulators in LDS between planes)
     constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held across the functor ...
     constexpr int LL = CellsLate<Fn>::value;       //  ... and per batch fetched after it)
     static_assert(LB >= 1 && LB <= NKMAX && (LB == NKMAX || (LL >= 1 && (NKMAX - LB) % LL == 0)), "whole batches");
@@ -40,6 +42,7 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
 
     const int q = threadIdx.x, ty = threadIdx.y;
     unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    [[maybe_unused]] const unsigned slot = L;      // (statistics: this workgroup's slot of the workspace)
     // per-cell sets: a group of CELLS_G samples is the fastest index, so the workgroups an XCD runs together (contiguous in
     // L) read the same level quads and find them in its L2; the last group is partial when B % CELLS_G != 0
     const int bl = CELLS ? L % CELLS_G : 0;
@@ -55,7 +58,11 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
     const int tc = (g.flags & PRE_FLAG_INTERIOR_T) ? max(g.ct, 1) : g.ct;
     const int t0 = max(ts * g.tSeg, tc);
     const int t1 = min(min(ts * g.tSeg + g.tSeg, g.T), g.T - tc);
-    if (t0 >= t1) return;                          // (workgroup-uniform: nothing of this segment is counted)
+    if (t0 >= t1) {                                // (workgroup-uniform: nothing of this segment is counted)
+        if constexpr (STATS)
+            if (q == 0 && ty == 0) stats_store(sets, slot, 0.0, 0.0, 0.0);      // (the second launch reads every slot)
+        return;
+    }
 
     const int x = xt * NR + ty, y = (yt * TYQ + q) * 4;
     const bool inb = (x < g.X) && (y < g.Y);       // (whole quads only: Y % 4 == 0, checked by the host)
@@ -132,7 +139,9 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
     // the modulation quad of plane t: only by threads with a counted cell and only for planes of this segment (its rim
     // is never touched along t and x; along y a rim cell shares its quad with counted ones and is masked by the select)
     auto load_mod = [&](int t, float4 &dst) __attribute__((always_inline)) {
-        if (g.mod && anykeep && t < t1) {
+        if constexpr (STATS) {
+            dst = f4(1.0f);                        // (no modulation under this policy: no registers for it either)
+        } else if (g.mod && anykeep && t < t1) {
             const float *p = g.mod + (long long)t * g.mT;
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
                 __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, -1, 0x00020000), (int)moff, 0, 0);
@@ -175,12 +184,20 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
     unsigned int cnt[NKMAX];
 #pragma unroll
     for (int k = 0; k < NKMAX; ++k) {
-        if constexpr (CELLS) qk[k] = 0.f;
+        if constexpr (CELLS || STATS) qk[k] = 0.f;
         else qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
         cnt[k] = 0;
     }
     float smax = 0.f, sthr = 0.f;
     bool snan = false;
+    [[maybe_unused]] double sacc[3] = {0.0, 0.0, 0.0};      // (statistics: sum r, sum |r|, sum r^2 of this thread's cells)
+    [[maybe_unused]] double *lacc = nullptr;                // (... or this thread's slot of them in LDS: lacc[j * NR * TYQ])
+    if constexpr (LACC) {
+        __shared__ double accs[3][NR * TYQ];
+        lacc = &accs[0][hl];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) lacc[j * NR * TYQ] = 0.0;      // (read and written by this thread only: no barrier)
+    }
 
     // One plane.  P,C,N hold planes t-1,t,t+1 of the own cells; D receives plane t+2; hc is the halo of plane t, hn
     // receives the halo of plane t+1; mc is the modulation of plane t, mn receives that of plane t+1.  The caller rotates
@@ -229,7 +246,14 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
             n[i].yp = make_float4(C[i].y, C[i].z, C[i].w, rgt);
         }
         const float4 r = Fn::eval(n, prm);
-        if constexpr (!CELLS) {
+        if constexpr (LACC) {
+            double pl[3] = {0.0, 0.0, 0.0};
+            stats_plane(r, keep, pl, smax, snan);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) lacc[j * NR * TYQ] += pl[j];
+        } else if constexpr (STATS) {
+            stats_plane(r, keep, sacc, smax, snan);
+        } else if constexpr (!CELLS) {
             screen_plane(r, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
         } else if constexpr (LB == NKMAX) {
             screen_plane_cells(r, mc, keep, g.nk, ql, cnt, smax, sthr, snan);
@@ -281,6 +305,34 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
     for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o));
     const unsigned int ubits = __ballot(snan) ? 0x7fc00000u : __float_as_uint(smax);
     const int wv = hl >> 6;
+    if constexpr (STATS) {
+        // statistics: the maximum as below; the sums by shuffles, then LDS in wave order, then ONE slot of the workspace
+        __shared__ double dred[3][NW];
+        if constexpr (LACC) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) sacc[j] = lacc[j * NR * TYQ];
+        }
+        stats_wave(sacc);
+        if ((hl & 63) == 0) {
+            red[0][wv] = ubits;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dred[j][wv] = sacc[j];
+        }
+        __syncthreads();
+        if (hl == 0) {
+            unsigned int v = 0;
+            double s[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                v = max(v, red[0][w]);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) s[j] += dred[j][w];
+            }
+            if (v) atomicMax(g.score + b, v);
+            stats_store(sets, slot, s[0], s[1], s[2]);
+        }
+        return;
+    }
     if ((hl & 63) == 0) {
         red[0][wv] = ubits;
 #pragma unroll
@@ -321,9 +373,21 @@ int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st
     g.nTSeg = (g.T + tSeg - 1) / tSeg;
     tiles *= g.nTSeg;
     if (tiles <= 0 || tiles * TYQ > 0xffffffffLL) return PRE_E_SHAPE;      // the dispatch packet counts work-items in 32 bits
+    if constexpr (IsStats<Sets>::value)
+        if (!stats_room(sets, tiles)) return PRE_E_NULL;                   // (never with the length the query entry gives)
     hipLaunchKernelGGL((screen_march_kernel<Fn, NR, TYQ, Sets>), dim3((unsigned)tiles), dim3(TYQ, NR), 0, st, g, prm, sets);
     PRE_LAUNCH_CHECK();
+    if constexpr (IsStats<Sets>::value) return stats_finish(sets, g.B, tiles / g.B, st);
     return PRE_OK;
+}
+
+// statistics: an upper bound of the workgroups per sample of any launch_screen on (T, X, Y), from the shape alone - the tiles
+// below, and marches no shorter than min(T, 8) planes (pick_tseg stops above 8, TFREE_TSEG is 8)
+inline long long stats_slots_ny(long long T, long long X, long long Y)
+{
+    static_assert(TFREE_TSEG == 0 || TFREE_TSEG >= 8, "marches of fewer than 8 planes: more workgroups than the bound");
+    const int NR = Y >= 192 ? 8 : Y >= 96 ? 16 : 32, W = Y >= 192 ? 256 : Y >= 96 ? 128 : 64;
+    return ((X + NR - 1) / NR) * ((Y + W - 1) / W) * ((T + 7) / 8);
 }
 
 template <class Fn, class Sets = ScalarSets>

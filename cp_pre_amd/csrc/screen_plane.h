@@ -2,6 +2,8 @@
 // screen_march.hip (libcp_pre_screen.so), screen_rows.hip (libcp_pre_screen1d.so) and screen_flat.hip
 // (libcp_pre_screenflat.so).  The crop is a select, the score uses the guarded divide of the joint score pass, hw = q_k * m
 // is one fp32 multiply with contraction off by pragma, the counts go compare -> wave mask -> population count -> scalar add.
+// Further down: the same end of a plane for per-cell level fields (CellSets), and the one of the per-sample statistics
+// (StatSets: fp64 sums and max |r| in place of score and counts; screen_stats.hip, screen_rows_stats.hip).
 #pragma once
 #include "star_march.h"
 #include "guarded_divide.h"
@@ -119,6 +121,96 @@ __device__ __forceinline__ void screen_plane_count(const float (&ac)[4], const f
             cnt[k0 + k] += c;
         }
     }
+}
+
+// ---- per-sample statistics of the residual (screen_stats.hip, screen_rows_stats.hip: libcp_pre_screenstats.so) ------------
+// StatSets, the third set policy of the three marches: no levels and no modulation.  A sample is reduced to sum r, sum |r|,
+// sum r^2 and max |r| over its counted cells.  The maximum goes where the score goes (integer atomicMax on the bit pattern).
+// The sums are fp64 from the first addition and see no atomic: a thread adds into three accumulators, a wave combines them by
+// shuffles, a workgroup by LDS in wave order, and the workgroup STORES its three partials into its own slot of a caller's
+// workspace, ws[slot][3] with slot the workgroup's logical index (the sample is its slowest part, so a sample's slots are
+// contiguous).  A second launch on the same stream (stats_finish) adds each sample's slots in index order into sums: the
+// same inputs and the same sequence of calls give the same bytes.  A workgroup with nothing to count stores zeros.
+struct StatSets {
+    static constexpr bool CELLS = false;
+    double *ws;                // device, [workgroups of the launch][3]
+    long long ws_len;          // doubles the caller provided
+    double *sums;              // device, [3][sum_ld]: sum r, sum |r|, sum r^2, add-accumulated across calls
+    long long sum_ld;
+};
+template <class Sets> struct IsStats { static constexpr bool value = false; };
+template <> struct IsStats<StatSets> { static constexpr bool value = true; };
+
+// Where a thread's three fp64 accumulators live between planes in screen_march_kernel: in registers, or (true) in a slot of
+// its own in LDS, read, added to and written back once per plane.  The NS momentum functor in the reference's tap structure
+// takes 129-131 registers with them where the level screen takes 125: one step past the 128 at which TWO of its 512-thread
+// workgroups fit a CU (holding the kernel to four waves by its launch bounds gives 12 bytes of scratch instead).  With the
+// accumulators in LDS - 12 KiB more per workgroup, still two per CU - it takes 125 (csrc/resources.sh; measured in DESIGN
+// 4.30).  The y-fixed structure stays above 128 either way (133 in registers, 129 in LDS; the level screen 127) and keeps
+// its registers.
+template <class Fn> struct StatsLdsAcc { static constexpr bool value = false; };
+template <> struct StatsLdsAcc<NSMomentum<0>> { static constexpr bool value = true; };
+
+// The end of a plane under StatSets.  A cell outside the counted region contributes exactly nothing (selects: 0 to the
+// maximum, +0.0 to the sums, whatever it holds).  Inside it the fp32 r is widened and every addition is fp64: (double) r,
+// its absolute value and its square, which is exact in fp64.  The maximum stays fp32 with a sticky NaN, the score's max with
+// m == 1 and no divide: bitwise what score_update(a, 1.0f, ...) keeps.
+__device__ __forceinline__ void stats_plane(const float4 &r, const bool (&keep)[4], double (&acc)[3], float &m, bool &nan)
+{
+    const float rv[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float a = keep[j] ? fabsf(rv[j]) : 0.0f;
+        if (a != a) nan = true;
+        else if (a > m) m = a;
+        const double d = keep[j] ? (double)rv[j] : 0.0;
+        acc[0] += d;
+        acc[1] += fabs(d);
+        acc[2] += d * d;
+    }
+}
+
+// the three accumulators of a wave in every lane: a butterfly, the same order on every run
+__device__ __forceinline__ void stats_wave(double (&acc)[3])
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[j] += __shfl_xor(acc[j], o);
+    }
+}
+
+// one thread of a workgroup: its slot of the workspace (plain stores)
+__device__ __forceinline__ void stats_store(const StatSets &sets, unsigned slot, double s0, double s1, double s2)
+{
+    double *p = sets.ws + 3ull * slot;
+    p[0] = s0; p[1] = s1; p[2] = s2;
+}
+
+// the second launch: thread (j, b) adds the S slots of sample b in index order into sums[j][b]
+template <class Sets>
+__global__ void __launch_bounds__(256) stats_finish_kernel(const Sets sets, int B, int S)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= 3ll * B) return;
+    const int j = (int)(i / B), b = (int)(i % B);
+    const double *p = sets.ws + 3ll * b * S + j;
+    double s = 0.0;
+    for (int k = 0; k < S; ++k) s += p[3ll * k];
+    sets.sums[(long long)j * sets.sum_ld + b] += s;
+}
+
+// host: does the workspace hold a launch of `wgs` workgroups?  (asked before the launch)
+inline bool stats_room(const StatSets &sets, long long wgs) { return 3 * wgs <= sets.ws_len; }
+
+// host: the second launch, after a march of S workgroups per sample (a template, as its kernel: only a unit that launches
+// a march under StatSets holds either)
+template <class Sets>
+int stats_finish(const Sets &sets, int B, long long S, hipStream_t st)
+{
+    hipLaunchKernelGGL((stats_finish_kernel<Sets>), dim3((unsigned)((3ll * B + 255) / 256)), dim3(256), 0, st, sets, B, (int)S);
+    PRE_LAUNCH_CHECK();
+    return PRE_OK;
 }
 
 // screen_plane with a level quad per k in place of the wave-uniform qk[]

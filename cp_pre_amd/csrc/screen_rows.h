@@ -103,6 +103,15 @@ RSplit rows_split(long long B, int R, int C, long long slots)
     return s;
 }
 
+// statistics: an upper bound of the workgroups per sample of rows_split on a plane of R rows x C columns, whatever `slots`:
+// rc is halved only from above 8 * NSEG, so it stays >= min(R, 5)
+inline long long stats_slots_rows(long long R, long long C)
+{
+    static_assert(ROWS_MINSEG >= 8, "shorter segments: more workgroups than the bound");
+    const long long strips = (C + 255) / 256, ws = strips >= 3 ? 4 : strips;
+    return ((strips + ws - 1) / ws) * ((R + 3) / 4);
+}
+
 // What the march evaluates per row: Fn::eval, except where the four unrolled row steps of the march would not round alike.
 // Under fma contraction the compiler is free to fuse either product of a sum of two products, and for Burgers<3> (Nt-fastest,
 // reference taps) it fused dx * D_t(u) + (dt * u) * D_x(u) as fma(dx, D_t, fl((dt u) D_x)) in the first step and as
@@ -137,6 +146,7 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm, const Sets sets
 {
     constexpr int NS = Fn::F;                      // field sets
     constexpr bool CELLS = Sets::CELLS;
+    constexpr bool STATS = IsStats<Sets>::value;   // (per-sample statistics: no levels, no modulation, screen_plane.h)
     constexpr int LB = CellsBatch<Fn>::value;      // (per-cell sets: level quads held at once)
     static_assert(NS >= 1 && NS <= ROWS_MAXSETS, "one field per set, one or two sets");
     static_assert(64 * ROWS_NW >= NKMAX + 1, "one thread per result in the combine step");
@@ -145,6 +155,7 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm, const Sets sets
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    [[maybe_unused]] const unsigned slot = L;      // (statistics: this workgroup's slot of the workspace)
     // per-cell sets: the sample of a group the fastest index; the last group is partial when B % ROWS_CELLS_G != 0
     const int bl = CELLS ? L % ROWS_CELLS_G : 0;
     if constexpr (CELLS) L /= ROWS_CELLS_G;
@@ -169,12 +180,13 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm, const Sets sets
     unsigned int cnt[NKMAX];
 #pragma unroll
     for (int k = 0; k < NKMAX; ++k) {
-        if constexpr (CELLS) qk[k] = 0.f;
+        if constexpr (CELLS || STATS) qk[k] = 0.f;
         else qk[k] = k < g.nk ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g.q[k]))) : 0.f;
         cnt[k] = 0;
     }
     float smax = 0.f, sthr = 0.f;
     bool snan = false;
+    [[maybe_unused]] double sacc[3] = {0.0, 0.0, 0.0};      // (statistics: sum r, sum |r|, sum r^2 of this lane's cells)
 
     if (r0 < r1 && strip * 256 < g.C) {            // (wave-uniform; no barrier in here)
         // column-halo duty: ONE edge scalar per lane and set (the column before the strip for the wave's first lane, the
@@ -209,7 +221,9 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm, const Sets sets
                 e[s] = (eload && r < r1) ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(row(s, r), voff + eoff4, 0, 0)) : 0.f;
         };
         auto load_mod = [&](int r, float4 &dst) __attribute__((always_inline)) {
-            if (g.mod && anykeep && r < r1) {
+            if constexpr (STATS) {
+                dst = f4(1.0f);                    // (no modulation under this policy: no registers for it either)
+            } else if (g.mod && anykeep && r < r1) {
                 const float *p = g.mod + (long long)r * g.mR;
                 const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
                     __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, -1, 0x00020000), voff, 0, 0);
@@ -262,7 +276,9 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm, const Sets sets
                 n[s].yp = make_float4(C[s].y, C[s].z, C[s].w, rgt);
             }
             const float4 res = RowsFn<Fn>::eval(n, prm);
-            if constexpr (!CELLS) {
+            if constexpr (STATS) {
+                stats_plane(res, keep, sacc, smax, snan);
+            } else if constexpr (!CELLS) {
                 screen_plane(res, mc, keep, g.nk, qk, cnt, smax, sthr, snan);
             } else {
                 float ac[4], sv[4];
@@ -300,6 +316,31 @@ screen_rows_kernel(const RGeom g, const typename Fn::Params prm, const Sets sets
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o));
     const unsigned int ubits = __ballot(snan) ? 0x7fc00000u : __float_as_uint(smax);
+    if constexpr (STATS) {
+        // statistics: the maximum as below; the sums by shuffles, then LDS in wave order, then ONE slot of the workspace (a
+        // wave that marched nothing holds zeros, so every workgroup stores its slot)
+        __shared__ double dred[3][ROWS_NW];
+        stats_wave(sacc);
+        if (lane == 0) {
+            red[0][wv] = ubits;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dred[j][wv] = sacc[j];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned int v = 0;
+            double s[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int w = 0; w < ROWS_NW; ++w) {
+                v = max(v, red[0][w]);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) s[j] += dred[j][w];
+            }
+            if (v) atomicMax(g.score + b, v);
+            stats_store(sets, slot, s[0], s[1], s[2]);
+        }
+        return;
+    }
     if (lane == 0) {
         red[0][wv] = ubits;
 #pragma unroll
@@ -328,8 +369,11 @@ int launch_rows(RGeom &g, const typename Fn::Params &prm, hipStream_t st, const 
     if constexpr (Sets::CELLS) nb = (nb + ROWS_CELLS_G - 1) / ROWS_CELLS_G * ROWS_CELLS_G;
     const long long wgs = nb * g.nChunk * g.nCT;
     if (wgs <= 0 || wgs * 64 * ROWS_NW > 0xffffffffLL) return PRE_E_SHAPE;      // the dispatch packet counts work-items in 32 bits
+    if constexpr (IsStats<Sets>::value)
+        if (!stats_room(sets, wgs)) return PRE_E_NULL;                          // (never with the length the query entry gives)
     hipLaunchKernelGGL((screen_rows_kernel<Fn, Sets>), dim3((unsigned)wgs), dim3(64 * ROWS_NW), 0, st, g, prm, sets);
     PRE_LAUNCH_CHECK();
+    if constexpr (IsStats<Sets>::value) return stats_finish(sets, g.B, wgs / g.B, st);
     return PRE_OK;
 }
 

@@ -134,6 +134,25 @@ raise before any launch, and ``minus=`` keeps ``fallback:minus=`` (two temperatu
 The method may be the ``norms`` partial of the paragraph on JOREK above.  ``jorek=True`` on any other method is a
 ``TypeError``; without the keyword JOREK keeps ``fallback:no fused screen for JOREK`` and the library is never loaded.
 
+Per-sample statistics of the residual - the 'PRE' acquisition of the active-learning loops, which orders the candidates by
+``torch.sort(torch.mean(torch.abs(pred_residual), axis=...))`` (``Active_Learning/Wave_AL_Joint.py:403-408``,
+``Active_Learning/Advection_AL_Joint.py:340-345``; the signed mean in ``Active_Learning/Burgers_AL_Joint.py:340-345``) - come
+from ``screen_stats(method, vars, boundary=False)`` / ``ScreenStats`` (``libcp_pre_screenstats.so``,
+``include/cp_pre_screenstats.h``): the three marches above with three float64 accumulators per thread in place of the counts,
+no levels and no modulation.  One launch evaluates the residual and stores nothing but a workgroup's partial sums into a
+cached per-device workspace; a second, tiny launch adds each sample's partials in a fixed order (no floating-point atomics:
+the same inputs give the same bytes on every run).  The result is a ``SampleStats``: ``sum``, ``sum_abs``, ``sum_sq``
+(float64 [n]), ``max_abs`` (float32 [n], bitwise the ``score`` of ``screen`` without a modulation), ``mean()``,
+``mean_abs()``, ``mean_sq()``, ``rms()``, ``order(by="mean_abs")`` - the scripts' ``sort_index`` - and ``take(k)``.  Routes
+``fused:stats_<kind>`` (Ny-fastest), ``fused:flat_stats_<kind>`` (Nt-fastest) and, for the 1-D family by default,
+``fused:rows_stats_<rows_kind>``.  Everything else stores the residual by the existing pass and reduces its counted region in
+float64, with ``fallback:<why>``: the reasons of the paragraphs above in their order (CPU inputs, no unit stride, widths that
+are no multiple of 4, ``Nt >= 96`` or rows that are not dense on an Nt-fastest view, a ``[BS,1,Nt,Nx]`` input, spectral
+operators, kernels off the star or requiring grad, ``fused=False``, fewer than six MHD channels, ``declined by the library``:
+the general-star tap structure of the MHD momentum and energy equations, which does not fit the register file next to the
+accumulators), and JOREK keeps ``fallback:no fused stats for JOREK``.  ``minus=`` is not accepted; ``halo_x`` raises where
+``Screen.add_slab`` raises.  Without a call to these two the library is never loaded, and they load no other screen library.
+
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
@@ -240,6 +259,9 @@ _CELLS_PAIR_ENTRY = {"": "pre_screencellspair_", "flat": "pre_screencellspair_fl
 # the per-cell screens of the JOREK residuals (opt-in, ``jorek=True`` on ``screen_cells`` / ``ScreenCells``), one more library:
 # form -> entry point
 _JOREK_CELLS_ENTRY = {"": "pre_screenjorekcells_f32", "flat": "pre_screenjorekcells_flat_f32"}
+# the per-sample statistics (``screen_stats`` / ``ScreenStats``), one more library for all three forms: the prefix of its
+# entries, followed by the form's route prefix
+_STATS_ENTRY = "pre_screenstats_"
 
 
 def _pair_mode(pair, minus):
@@ -411,9 +433,12 @@ class _Spec(Method):
         return minus.dim() == 3 and minus.stride(ax) != 1 and minus.stride(3 - ax) == 1
 
     # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
-    def entry(self, form, pair=False, cells=False):
+    def entry(self, form, pair=False, cells=False, stats=False):
         """The entry point of this method's fused screen in the library of ``form`` (``pair``: of its paired screen,
-        ``cells``: of its per-cell screen; form 'rows' has both at once)."""
+        ``cells``: of its per-cell screen; form 'rows' has both at once; ``stats``: of its per-sample statistics)."""
+        if stats:
+            kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
+            return _STATS_ENTRY + _FORMS[form][2] + kind + "_f32"
         if cells and form == "rows":
             return _CELLS_ROWS_ENTRY + ("pair_" if pair else "") + self.rows_kind + "_f32"
         if cells and pair:
@@ -429,19 +454,22 @@ class _Spec(Method):
         kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
         return _FORMS[form][1] + kind + "_f32"
 
-    def route(self, form, pair=False, cells=False):
+    def route(self, form, pair=False, cells=False, stats=False):
+        if stats:
+            return "fused:" + _FORMS[form][2] + "stats_" + (self.rows_kind if form == "rows" else self.kind)
         if cells and form == "rows":
             return "fused:rows_cells_" + ("pair_" if pair else "") + self.rows_kind
         if cells:
             return "fused:" + _FORMS[form][2] + "cells_" + ("pair_" if pair else "") + self.kind
         return "fused:" + _FORMS[form][2] + ("pair_" if pair else "") + (self.rows_kind if form == "rows" else self.kind)
 
-    def launch(self, kernels, x, st, flags, form="", minus=None, cells=False):
+    def launch(self, kernels, x, st, flags, form="", minus=None, cells=False, stats=False):
         """The fused launch of ``form`` on device views ``x`` ([BS,Nt,Nx] for 'rows'); returns the library's code.
         ``minus``: the paired screen of ``x`` and ``minus`` (``libcp_pre_screenpair.so`` for forms '' and 'flat',
         ``libcp_pre_screen1dpair.so`` for 'rows').  ``cells``: the per-cell screen (``libcp_pre_screencells.so`` for forms ''
         and 'flat', with ``minus`` ``libcp_pre_screencellspair.so``; ``libcp_pre_screen1dcells.so`` for 'rows', there with
-        ``minus`` too, ``libcp_pre_screenjorekcells.so`` for the JOREK kinds; ``st`` is then its set descriptor)."""
+        ``minus`` too, ``libcp_pre_screenjorekcells.so`` for the JOREK kinds; ``st`` is then its set descriptor).  ``stats``:
+        the per-sample statistics (``libcp_pre_screenstats.so``, all three forms; ``st`` is its descriptor)."""
         assert form == "" or not flags & _lib.PRE_FLAG_HALO_X    # (only the Ny-fastest march reads halo rows)
         if minus is not None and form == "rows":
             sets = (_lib.ptr(x), _lib.iarr64(x.stride()), _lib.ptr(minus), _lib.iarr64(minus.stride()))
@@ -459,7 +487,9 @@ class _Spec(Method):
             fn = getattr(_lib._load("screencellspair") if cells else _lib.load_screenpair(), self.entry(form, True, cells))
             return fn(*views, *kernels, *self.scalars(), ctypes.byref(st), *fa[0].shape, flags, _lib.stream())
         kind = self.rows_kind if form == "rows" else self.kind
-        if cells and form == "rows":
+        if stats:
+            lib = _lib.load_screenstats()                        # (loaded on this route only)
+        elif cells and form == "rows":
             lib = _lib.load_screen1dcells()
         elif cells and kind in _JOREK_EQ:
             lib = _lib.load_screenjorekcells()                   # (loaded on this route only)
@@ -481,8 +511,8 @@ class _Spec(Method):
                 views = [ctypes.byref(_lib.field(f)) for f in fs]
         if kind.startswith("stencil"):
             kernels = _dispatch.tap_args(*kernels)
-        return getattr(lib, self.entry(form, cells=cells))(*views, *kernels, *self.scalars(), ctypes.byref(st), *shape, flags,
-                                                           _lib.stream())
+        return getattr(lib, self.entry(form, cells=cells, stats=stats))(*views, *kernels, *self.scalars(), ctypes.byref(st),
+                                                                        *shape, flags, _lib.stream())
 
     def launch_flat(self, kernels, x, st, flags):
         return self.launch(kernels, x, st, flags, "flat")
@@ -904,4 +934,197 @@ def _pad_levels(qcells, full, nt_fastest):
     else:
         out = torch.full((nk,) + tuple(full), float("nan"), dtype=qcells.dtype, device=qcells.device)
     out[(slice(None),) + (slice(1, -1),) * len(full)] = qcells
+    return out
+
+
+# ------------------------------------------------------------------------------------------- per-sample statistics
+_STATS = ("mean", "mean_abs", "mean_sq", "rms", "max_abs", "sum", "sum_abs", "sum_sq")
+
+
+class SampleStats:
+    """Per-sample statistics of a residual over its counted cells: ``sum`` = sum r, ``sum_abs`` = sum |r|, ``sum_sq`` =
+    sum r^2 (float64 [n]), ``max_abs`` = max |r| (float32 [n], NaN sticky), ``cells`` counted cells per sample (host int).
+    All tensors are on the device of the input."""
+
+    def __init__(self, sum, sum_abs, sum_sq, max_abs, cells):
+        self.sum, self.sum_abs, self.sum_sq, self.max_abs, self.cells = sum, sum_abs, sum_sq, max_abs, int(cells)
+
+    def mean(self):
+        """float64 [n]: ``torch.mean(r, axis=...)`` per sample (the 'PRE' acquisition of ``Burgers_AL_Joint.py:340-345``)."""
+        return self.sum / float(self.cells)
+
+    def mean_abs(self):
+        """float64 [n]: ``torch.mean(torch.abs(r), axis=...)`` per sample (``Wave_AL_Joint.py:403-408``,
+        ``Advection_AL_Joint.py:340-345``)."""
+        return self.sum_abs / float(self.cells)
+
+    def mean_sq(self):
+        """float64 [n]: the per-sample mean of r^2, the per-sample term of ``PI_loss``."""
+        return self.sum_sq / float(self.cells)
+
+    def rms(self):
+        return torch.sqrt(self.mean_sq())
+
+    def _stat(self, by):
+        if by not in _STATS:
+            raise ValueError(f"by={by!r}: one of {_STATS}")
+        v = getattr(self, by)
+        return v() if callable(v) else v
+
+    def order(self, by="mean_abs", descending=False):
+        """int64 [n]: the indices of ``torch.sort(<statistic>, stable=True)`` - the ``sort_index`` of the three scripts."""
+        return torch.sort(self._stat(by), descending=descending, stable=True).indices
+
+    def take(self, k, by="mean_abs", largest=False):
+        """The first ``k`` of ``order(by, descending=largest)``."""
+        k = int(k)
+        if not 0 <= k <= self.sum.shape[0]:
+            raise ValueError(f"k = {k} of {self.sum.shape[0]} samples")
+        return self.order(by, descending=largest)[:k]
+
+
+def _check_stats(spec, vars, crop):
+    """Every shape, dtype and empty-batch error of a statistics call, raised before any device work (``_check_inputs``
+    without levels, modulation and ``minus``).  Returns (uncropped residual shape, crop, counted cells per sample)."""
+    if not isinstance(vars, torch.Tensor):
+        raise TypeError("vars must be a torch.Tensor")
+    if vars.dtype != torch.float32:
+        raise TypeError(f"vars has dtype {vars.dtype}: the screen takes float32 fields")
+    shape = spec.field_shape(vars)
+    if vars.numel() == 0:
+        raise ValueError("screen of an empty batch")
+    crop = tuple(int(c) for c in crop)
+    if len(crop) != len(shape) - 1 or any(c < 0 for c in crop):
+        raise ValueError(f"crop {crop}: one non-negative count per residual axis")
+    if any(n - 2 * c <= 0 for n, c in zip(shape[1:], crop)):
+        raise ValueError(f"crop {crop} leaves no cell of a {tuple(shape[1:])} residual")
+    cells = 1
+    for n, c in zip(shape[1:], crop):
+        cells *= n - 2 * c
+    if cells >= 1 << 32:
+        raise ValueError("cells per sample >= 2^32: screen the grid in slabs")
+    return shape, crop, cells
+
+
+# the workspace of the statistics launches: one float64 buffer per (device, stream), grown on demand, never handed out (its
+# contents mean nothing between calls: every slot a launch reads it has written before)
+_stats_ws = {}
+_F32 = torch.empty(0, dtype=torch.float32)        # (stands in for the levels in ``_input_declined``: there are none)
+
+
+def _stats_workspace(device, n):
+    key = _dev_key(device) + (torch.cuda.current_stream(device).cuda_stream,)
+    ws = _stats_ws.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _stats_ws[key] = torch.empty(max(int(n), 1), dtype=torch.float64, device=device)
+    return ws
+
+
+class ScreenStats:
+    """Accumulating per-sample statistics of ``n_local`` samples: ``add_slab`` once per slab of the grid (x-slabs with
+    ``halo_x``, t-slabs with their halo planes, row slabs of the 1-D family - what slabs mean for ``Screen.add_slab``),
+    ``finish`` -> ``SampleStats``.  The maximum composes exactly: the slabs of a grid give the bits of the whole grid's
+    ``max_abs``; the float64 sums are those of the whole grid to the rounding of another order of the same terms."""
+
+    def __init__(self, n_local, device):
+        if n_local < 1:
+            raise ValueError(f"ScreenStats needs n_local >= 1 (got {n_local})")
+        self.n_local, self.device = int(n_local), torch.device(device)
+        self.mx = self.sums = None     # int32 [n_local]: the bits of max |r|; float64 [3, n_local]; made at the first slab
+        self.cells = 0
+
+    def _buffers(self, device):
+        if self.mx is None:
+            self.mx = torch.zeros(self.n_local, dtype=torch.int32, device=device)
+            self.sums = torch.zeros(3, self.n_local, dtype=torch.float64, device=device)
+        return self.mx, self.sums
+
+    def add_slab(self, method, vars_slab, crop=(1, 1, 1), halo_x=False):
+        """``vars_slab``: the method's input on a slab of the grid (all local samples); ``crop`` cells per side of each
+        residual axis are left out (two axes for the 1-D family); ``halo_x``: the slab's rows -1 and X lie in the same
+        memory (raises where ``Screen.add_slab`` raises).  There is no ``minus``: the 'PRE' acquisition has no paired form."""
+        global _last_route
+        spec = method if isinstance(method, _Spec) else _Spec(method)
+        shape, crop, cells = _check_stats(spec, vars_slab, crop)
+        if shape[0] != self.n_local:
+            raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
+        if _dev_key(vars_slab.device) != _dev_key(self.device):
+            raise ValueError(f"slab on {vars_slab.device}, this ScreenStats was made for {self.device}")
+        why, kernels = spec.prepare(vars_slab, None, _F32, None)
+        if spec.row == "jorek":
+            why = "no fused stats for JOREK"
+        if halo_x and not vars_slab.is_cuda:
+            raise ValueError("halo_x needs a device-resident view of a larger grid (a staged copy has no halo rows)")
+        if halo_x and why is not None and not spec.reads_halo():
+            # (before any device work: this slab would be evaluated against zero padding and counted as if it were right)
+            raise RuntimeError(f"halo_x: the fused statistics cannot run ({why}) and no other pass of this method reads the halo rows")
+        rows = spec.rows_kind is not None                     # (the 1-D family: its rows route by default; halo_x has raised)
+        if rows:
+            why, kernels = spec.prepare_rows(vars_slab, None, _F32, None)
+        flat = not rows and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
+        if flat:
+            why, kernels = spec.prepare_flat(vars_slab, None, _F32, None)
+        if why is None:
+            mx, sums = self._buffers(vars_slab.device)
+            form = "rows" if rows else "flat" if flat else ""
+            with torch.no_grad(), torch.cuda.device(vars_slab.device):
+                need = int(_lib.load_screenstats().pre_screenstats_workspace_len(
+                    _lib.PRE_SCREENSTATS_FORM[form], *shape, *((1,) if rows else ())))
+                ws = _stats_workspace(vars_slab.device, need)
+                st = _lib.PreScreenStats(crop[0], crop[1], 0 if rows else crop[2], ctypes.c_void_p(mx.data_ptr()),
+                                         ctypes.c_void_p(sums.data_ptr()), sums.stride(0), ctypes.c_void_p(ws.data_ptr()),
+                                         ws.numel())
+                rc = spec.launch(kernels, vars_slab, st, _lib.PRE_FLAG_HALO_X if halo_x and form == "" else 0, form, stats=True)
+            if rc == _lib.PRE_E_UNSUPPORTED:
+                why = "declined by the library"
+                if halo_x and not spec.reads_halo():
+                    raise RuntimeError("halo_x: the library declined and no other pass of this method reads the halo rows")
+            else:
+                _lib.check(rc, spec.entry(form, stats=True))
+                _last_route = spec.route(form, stats=True)
+                self.cells += cells
+                return
+        _last_route = "fallback:" + why
+        self._fallback(spec, vars_slab, crop, halo_x)
+        self.cells += cells
+
+    def _fallback(self, spec, vars, crop, halo_x):
+        """What a caller writes today: the stored residual by the existing pass with ``boundary=True``, then float64
+        reductions of the counted region, where the residual lives."""
+        res = spec.full(vars, None, halo_x)
+        mx, sums = self._buffers(res.device)
+        sl = (slice(None),) + tuple(slice(c, n - c) for c, n in zip(crop, res.shape[1:]))
+        r32 = res[sl].reshape(res.shape[0], -1)
+        r64 = r32.double()
+        sums[0] += r64.sum(dim=1)
+        sums[1] += r64.abs().sum(dim=1)
+        sums[2] += (r64 * r64).sum(dim=1)
+        a = r32.abs().max(dim=1).values
+        a = torch.where(r32.isnan().any(dim=1), torch.full_like(a, float("nan")), a)
+        # unsigned maximum of the bit patterns (non-negative values, the NaN pattern 0x7fc00000 above +inf)
+        bits = torch.where(a.isnan(), torch.full_like(mx, 0x7fc00000), a.contiguous().view(torch.int32))
+        torch.maximum(mx, bits, out=mx)
+
+    def finish(self):
+        if self.mx is None or self.cells == 0:
+            raise ValueError("ScreenStats.finish() before any slab")
+        return SampleStats(self.sums[0].clone(), self.sums[1].clone(), self.sums[2].clone(), self.mx.view(torch.float32).clone(),
+                           self.cells)
+
+
+def screen_stats(residual_method, vars, boundary=False):
+    """Per-sample statistics of the residual of ``vars`` - sum r, sum |r|, sum r^2 in float64 and max |r| - from ONE
+    streaming launch that stores no residual (followed by a tiny launch that adds the workgroups' partial sums; no
+    floating-point atomics: the same inputs give the same bytes on every run).  ``boundary=False``: the counted cells are
+    the interior ``[1:-1]`` of every residual axis; ``boundary=True``: every cell.  Returns a :class:`SampleStats`:
+    ``stats.order()`` is the ``sort_index`` of ``torch.sort(torch.mean(torch.abs(residual), axis=...))``,
+    ``stats.order("mean")`` that of the signed form.  There is no ``minus=``: the 'PRE' acquisition has no paired form."""
+    spec = _Spec(residual_method)
+    crop = (0,) * spec.nd if boundary else (1,) * spec.nd
+    shape, _, _ = _check_stats(spec, vars, crop)
+    s = ScreenStats(shape[0], vars.device)
+    s.add_slab(spec, vars, crop=crop)
+    out = s.finish()
+    if not vars.is_cuda:                                     # (staged inputs: the statistics come home, as elsewhere)
+        out.sum, out.sum_abs, out.sum_sq, out.max_abs = (t.to(vars.device) for t in (out.sum, out.sum_abs, out.sum_sq, out.max_abs))
     return out

@@ -97,6 +97,15 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                deliver the same per-sample answer.  Lines go to profiles/screenjorekcells/screen_bench_cellsjorek.jsonl
                unless --out says otherwise
 
+    c2_wave_ntfast_stats / c5_burgers_stats_nx / c5_burgers_stats_nt / c3_rank8_ntfast_stats / c3_xslab_stats
+               the per-sample statistics (``screen.ScreenStats(...).add_slab``: ``libcp_pre_screenstats.so``): the wave
+               residual on memory [512,256,256,32] seen through ``permute(0,3,1,2)`` (the view
+               ``Active_Learning/Wave_AL_Joint.py`` passes), and the fields of the cases of those names above.  Routes,
+               alternated call by call: (F) the statistics launch; (J) the joint screen on the same view with nk = 1 and no
+               modulation, which reads the same bytes; (P) the stored residual, then ``.abs().mean(dims)``.  (--only fused /
+               parent / three runs F / J / P alone.)  Lines go to profiles/screenstats/screen_bench_stats.jsonl unless --out
+               says otherwise
+
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
@@ -767,6 +776,80 @@ def run_cellsjorek(name, args, dev):
     return line
 
 
+# ---- per-sample statistics (screen.screen_stats / ScreenStats, libcp_pre_screenstats.so) ------------------------------------
+# case -> the case whose fields and method it takes; c2_wave_ntfast_stats is the view Active_Learning/Wave_AL_Joint.py passes
+STATS_CASES = {"c2_wave_ntfast_stats": None, "c5_burgers_stats_nx": "c5_burgers_nx", "c5_burgers_stats_nt": "c5_burgers_nt",
+               "c3_rank8_ntfast_stats": "c3_rank8_ntfast", "c3_xslab_stats": "c3_xslab"}
+
+
+def run_stats(name, args, dev):
+    """Three routes alternated call by call in one process: (F) the statistics launch, (J) the joint screen on the same view
+    with nk = 1 and no modulation - the parent's code, which reads the same bytes -, (P) what a caller writes today: the
+    stored residual, then ``.abs().mean(dims)``."""
+    if STATS_CASES[name] is None:
+        w = R.PRE_Wave(0.01, 0.02, device=dev)
+        g = torch.Generator(device=dev).manual_seed(0)
+        v = (torch.rand(max(512 // args.div, 1), 256, 256, 32, device=dev, generator=g) + 0.5).permute(0, 3, 1, 2)
+        method, crop, halo_x, fbytes = w.residual, (1, 1, 1), False, 4
+        residual_into = lambda out: w.residual(v, boundary=True, out=out)  # noqa: E731
+    else:
+        method, v, crop, halo_x, residual_into, fbytes = case(STATS_CASES[name], args.div, dev)
+    n, one_d = v.shape[0], len(crop) == 2
+    shape = (n,) + tuple(v.shape[-len(crop):])
+    nt_fast = not one_d and v.stride(-1) != 1
+    out = None if one_d else torch.empty(shape, dtype=torch.float32, device=dev)
+    if nt_fast:
+        out = torch.empty((n,) + shape[2:] + shape[1:2], dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+    reg = (slice(None),) + tuple(slice(c, s - c) for c, s in zip(crop, shape[1:]))
+    dims = tuple(range(1, len(shape)))
+    q1 = torch.ones(1, device=dev)
+
+    def stats():
+        s = screen.ScreenStats(n, dev)
+        s.add_slab(method, v, crop=crop, halo_x=halo_x)
+        return s
+
+    def joint():
+        s = screen.Screen(n, 1, dev)
+        s.add_slab(method, v, q1, None, crop=crop, halo_x=halo_x)
+        return s
+
+    def stored():
+        res = residual_into(out) if one_d else (residual_into(out), out)[1]
+        return res[reg].abs().mean(dim=dims)
+
+    s = stats()
+    route = screen.last_route()
+    j = joint()
+    route_j = screen.last_route()
+    p = stored()
+    torch.cuda.synchronize()
+    got, gj = s.finish(), j.finish()
+    max_same = bool(torch.equal(got.max_abs.view(torch.int32), gj.score.view(torch.int32)))
+    rel = float(((got.mean_abs() - p.double()).abs() / p.double()).max())
+    fns = {"fused": stats, "parent": joint, "three": stored}
+    pick = [args.only] if args.only in fns else ["fused", "parent", "three"]
+    res = blocks_of([fns[k] for k in pick], args.reps, args.blocks, args.warmup)
+    cells = 1
+    for d in shape:
+        cells *= d
+    line = {"case": name, "shape": list(v.shape), "route": route, "route_J": route_j, "max_abs_bits_equal_J_score": max_same,
+            "mean_abs_rel_diff_to_P": rel, "cells": cells, "field_bytes_per_cell": fbytes}
+    for k, (med, lo, hi) in zip(pick, res):
+        label = {"fused": "F", "parent": "J", "three": "P"}[k]
+        line[label + "_ms"] = round(med, 4)
+        line[label + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
+    if "F_ms" in line:
+        line["F_TBps_of_fields"] = round(cells * fbytes / (line["F_ms"] * 1e-3) / 1e12, 3)
+    if "F_ms" in line and "J_ms" in line:
+        spread = line["J_ms_blocks_min_max"][1] - line["J_ms_blocks_min_max"][0]
+        line["F_over_J"] = round(line["F_ms"] / line["J_ms"], 4)
+        line["F_no_worse_than_J_beyond_its_spread"] = bool(line["F_ms"] <= line["J_ms"] + spread)
+    if "F_ms" in line and "P_ms" in line:
+        line["F_over_P"] = round(line["F_ms"] / line["P_ms"], 4)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
@@ -791,6 +874,15 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in args.cases.split(","):
+        if name in STATS_CASES:
+            path = args.out or os.path.join(ROOT, "profiles", "screenstats", "screen_bench_stats.jsonl")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            txt = json.dumps(run_stats(name, args, dev))
+            print(txt, flush=True)
+            with open(path, "a") as f:
+                f.write(txt + "\n")
+            torch.cuda.empty_cache()
+            continue
         if name in CELLS1D_CASES:
             path = args.out or os.path.join(ROOT, "profiles", "screen1dcells", "screen_bench_cells1d.jsonl")
             os.makedirs(os.path.dirname(path), exist_ok=True)
