@@ -455,6 +455,29 @@ VJPJOREK_SIGNATURES = {
     "pre_vjpjorek_flat_f32": [c_int, _fld, POINTER(PreField), _fld, POINTER(PreField)] + [POINTER(c_float)] * 6 + _mhdtail,
 }
 
+# libcp_pre_bcres.so (include/cp_pre_bcres.h): the fused residuals under boundary conditions on the x-y rim: each entry takes
+# its zero-pad twin's arguments in libcp_pre_hip.so with a pre_bc_t (PreBC) before the extents; the 1-D linear entry takes a
+# dense 3x3 kernel in place of a tap list
+BCRES_SO_PATH = os.path.join(_HERE, "libcp_pre_bcres.so")
+PRE_BCRES_ABI_VERSION = 1
+PRE_BC_CONSTANT, PRE_BC_REPLICATE, PRE_BC_PERIODIC, PRE_BC_REFLECT = 0, 1, 2, 3
+
+
+def _with_bc(sig, n_tail):
+    """A zero-pad entry's signature with the boundary conditions before its last ``n_tail`` arguments (extents, flags, stream)."""
+    return sig[:-n_tail] + [POINTER(PreBC)] + sig[-n_tail:]
+
+
+BCRES_SIGNATURES = {
+    "pre_bcres_abi_version": [],
+    "pre_bcres_linear1_f32": [_fld, _fld, POINTER(c_float), POINTER(PreBC)] + [c_int64] * 4 + [c_int, c_void_p],
+    "pre_bcres_linear2_f32": _with_bc(SIGNATURES["pre_residual_linear2_f32"], 6),
+    "pre_bcres_ns_momentum_f32": _with_bc(SIGNATURES["pre_residual_ns_momentum_f32"], 6),
+    "pre_bcres_mhd_f32": _with_bc(SIGNATURES["pre_residual_mhd_f32"], 6),
+    "pre_bcres_burgers_f32": _with_bc(SIGNATURES["pre_residual_burgers_f32"], 5),
+    "pre_bcres_linear1_rows_f32": [_fp, _i64p, _fp, _i64p, POINTER(c_float), POINTER(PreBC)] + [c_int64] * 3 + [c_int, c_void_p],
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -495,8 +518,9 @@ _LIBS_MORE = {
                          "PRE_SCREENJOREKCELLS_ABI_VERSION", ()),
     "screenstats": ("_screenstats", "SCREENSTATS_", "pre_screenstats_abi_version", "PRE_SCREENSTATS_ABI_VERSION",
                     ("pre_screenstats_workspace_len",)),
+    "bcres": ("_bcres", "BCRES_", "pre_bcres_abi_version", "PRE_BCRES_ABI_VERSION", ()),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = _screenjorekcells = _screenstats = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = _screenjorekcells = _screenstats = _bcres = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -633,6 +657,11 @@ def load_screenjorekcells():
 
 def load_screenstats():
     return _screenstats or _load("screenstats")
+
+
+def load_bcres():
+    """Loaded on the first residual with ``bc=``, never otherwise."""
+    return _bcres or _load("bcres")
 
 
 def require_gpu():

@@ -131,6 +131,8 @@ class Method:
         does not differentiate; ``kernel_trains``: a kernel that requires grad is the caller's to train."""
         if getattr(self.obj, "fused", True) is False:
             return "fused=False"
+        if getattr(self.obj, "bc", None) is not None:
+            return "bc= (no fused screen or backward under boundary conditions on the x-y rim)"
         if yy is not None and yy.requires_grad and torch.is_grad_enabled():
             return "yy requires grad"
         if not kernel_trains and _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):

@@ -121,8 +121,11 @@ def _fused(name, call, sets, absolute, out=None, skip_t_rim=False, halo_x=False,
 class _Residual2D:
     """Shared plumbing: the operator set of ``Marginal/NS_Residuals_CP.py:213-219``."""
 
-    def __init__(self, device='cpu', fused=True, y_axis_fix=False):
+    def __init__(self, device='cpu', fused=True, y_axis_fix=False, bc=None):
+        """``bc``: boundary conditions on the x-y rim for every ``residual*`` of this object (``_BC``: 'wrap', a type name, a
+        dict side -> type | (type, value), a ``BoundaryManager``); None = the zero padding of the reference."""
         self.fused = fused
+        self.bc = None if bc is None else _BC(bc)
         self.D_t = ConvOperator2D(domain='t', order=1, device=device)
         self.D_x = ConvOperator2D(domain='x', order=1, device=device)
         self.D_y = ConvOperator2D(domain='y', order=1, device=device, y_axis_fix=y_axis_fix)
@@ -147,6 +150,14 @@ class _Residual2D:
         ``vector_convops.linear2`` (which keeps the result differentiable itself, operator kernels included), two in one
         pass of ``pre_pair_linear2_f32``."""
         sets = ((vars[:, i], vars[:, j]),)
+        if self.bc is not None:
+            if minus is not None:
+                _check_minus(vars, minus)
+            return _bc_residual("linear2", self.bc, 3, sets[0], None if minus is None else (minus[:, i], minus[:, j]), composed,
+                                (self.D_x, self.D_y), lambda d, o, ks, st, flags: _lib.load_bcres().pre_bcres_linear2_f32(
+                                    _fld(d[0]), _fld(d[1]), _fld(o), *ks, float(ratio), ctypes.byref(st), *o.shape, flags,
+                                    _lib.stream()), boundary, absolute, fused=self.fused)
+        _no_bc()
         if minus is None:
             if self._want_fused(vars):
                 from .vector_convops import linear2
@@ -283,6 +294,21 @@ class NavierStokes(_Residual2D):
             res_y = D_t(v)*dx*dy + u*D_x(v)*dt*dx + v*D_y(v)*dt*dy - nu*D_xx_yy(v)*dt + D_y(p)*dt*dx
             return res_x + res_y
         interior_out = skip_t_rim and out is not None and out.dim() == 4 and vars.dim() == 5 and out.shape[1] == vars.shape[2] - 2
+        if self.bc is not None:
+            # (the x-y rim is valid under ``bc``; ``boundary=False`` crops the time rim only.  ``skip_t_rim`` is honoured:
+            # PRE_FLAG_INTERIOR_T)
+            if halo_x or interior_out:
+                raise ValueError("bc with halo_x=True / an interior-plane out: an x-slab with a wrapped x, or a t-slab "
+                                 "buffer, is not served under boundary conditions")
+            if minus is not None:
+                _check_minus(vars, minus)
+            scal = (float(dt), float(dx), float(dy), float(nu))
+            return _bc_residual("ns_momentum", self.bc, 3, sets[0], None if minus is None else (minus[:, 0], minus[:, 1], minus[:, 2]),
+                                composed, (D_t, D_x, D_y, D_xx_yy),
+                                lambda d, o, ks, st, flags: _lib.load_bcres().pre_bcres_ns_momentum_f32(
+                                    *[_fld(t) for t in d + [o]], *ks, *scal, ctypes.byref(st), *o.shape, flags, _lib.stream()),
+                                boundary, absolute, out, self.fused, _lib.PRE_FLAG_INTERIOR_T if skip_t_rim else 0)
+        _no_bc()
         pair = None
         if minus is not None:
             _check_minus(vars, minus, device_view=halo_x or interior_out)
@@ -392,6 +418,22 @@ class MHD(_Residual2D):
         single-set fused pass of ``vars`` into the result (``out`` if given), that of ``minus`` into one scratch buffer, an
         in-place subtract (or |.|) - else the composed difference."""
         sets = (tuple(vars[:, i] for i in idx),)
+        if self.bc is not None:
+            if halo_x:
+                raise ValueError("bc with halo_x=True: an x-slab with a wrapped x is not served under boundary conditions")
+            if minus is not None:
+                _check_minus(vars, minus)
+            # (the entry takes the six views whatever the equation reads; with fewer the fields of the equation compose)
+            six = vars.dim() == 5 and vars.shape[1] >= 6
+            pick = (lambda *f: composed(*[f[i] for i in idx])) if six else composed
+            views = lambda v: tuple(v[:, i] for i in (range(6) if six else idx))
+            return _bc_residual("mhd_" + eq, self.bc, 3, views(vars), None if minus is None else views(minus), pick,
+                                (self.D_t, self.D_x, self.D_y),
+                                lambda d, o, ks, st, flags: _lib.load_bcres().pre_bcres_mhd_f32(
+                                    _MHD_EQ[eq], _arr(d), _fld(o), *ks, float(self.gamma), ctypes.byref(st), *o.shape, flags,
+                                    _lib.stream()) if six else _lib.PRE_E_UNSUPPORTED,
+                                boundary, absolute, out, self.fused)
+        _no_bc()
         if minus is None:
             return _tail(self._fused(eq, vars, absolute, halo_x, out), sets, composed, boundary, _CROP3, absolute)
         _check_minus(vars, minus, device_view=halo_x)
@@ -531,6 +573,7 @@ class JOREK:
     def _residual(self, eq, fa, composed, coef, method, vars, minus, boundary, absolute):
         """How both equations end.  ``minus``: r(vars) - r(minus), TWO-PASS: the single-set fused pass of each set, then an
         in-place subtract (or |.|)."""
+        _no_bc()
         if minus is None:
             return _tail(self._fused(eq, fa, coef, absolute), (fa,), composed, boundary, _CROP3, absolute)
         _check_minus(vars, minus)
@@ -589,7 +632,8 @@ class PRE_Wave:
     """``Other_UQ/Evaluation/PRE_estimations.py:5-21`` / ``Marginal/Wave_Residuals_CP.py:170-184``:
     ONE additive kernel ``D_tt - (c dt/dx)^2 D_xx_yy`` applied in one pass."""
 
-    def __init__(self, dt, dx, c=1.0, device='cpu'):
+    def __init__(self, dt, dx, c=1.0, device='cpu', bc=None):
+        self.bc = None if bc is None else _BC(bc)
         D_tt = ConvOperator2D('t', 2, device=device)
         D_xx_yy = ConvOperator2D(('x', 'y'), 2, device=device)
         self.D = ConvOperator2D()
@@ -607,6 +651,12 @@ class PRE_Wave:
             _check_minus(uu, minus, device_view=halo_x)
             minus = minus[:, 0] if minus.dim() == 5 else minus
         uu = uu[:, 0] if uu.dim() == 5 else uu
+        if self.bc is not None:
+            if halo_x:
+                raise ValueError("bc with halo_x=True: an x-slab with a wrapped x is not served under boundary conditions")
+            return _bc_residual("linear1", self.bc, 3, (uu,), None if minus is None else (minus,), lambda u: self.D(u), (self.D,),
+                                _bc_linear1, boundary, absolute, out)
+        _no_bc()
         flags = (_lib.PRE_FLAG_ABS if absolute else 0) | (_lib.PRE_FLAG_HALO_X if halo_x else 0)
         if minus is not None:
             return self._minus(uu, minus, boundary, absolute, halo_x, out, flags)
@@ -641,7 +691,8 @@ class PRE_Wave:
 class Advection:
     """``Marginal/Advection_Residuals_CP.py:156-164,234-235``: ``D_t + (v disc dt/dx) D_x`` on [BS,Nt,Nx]."""
 
-    def __init__(self, v, dt, dx, disc=2, device='cpu'):
+    def __init__(self, v, dt, dx, disc=2, device='cpu', bc=None):
+        self.bc = None if bc is None else _BC(bc)
         D_t = ConvOperator1D(domain='t', order=1, device=device)
         D_x = ConvOperator1D(domain='x', order=1, device=device)
         self.D = ConvOperator1D()
@@ -649,6 +700,13 @@ class Advection:
 
     def residual(self, uu, boundary=False, absolute=False, minus=None):
         """``minus``: r(uu) - r(minus) in one pass of both fields (``pre_pair_stencil2d_f32``)."""
+        if self.bc is not None:
+            if minus is not None:
+                _check_minus(uu, minus)
+            sq = lambda x: x[:, 0] if x is not None and x.dim() == 4 and x.shape[1] == 1 else x
+            return _bc_residual("linear1_rows", self.bc, 2, (sq(uu),), None if minus is None else (sq(minus),),
+                                lambda u: self.D(u), (self.D,), _bc_linear1_rows, boundary, absolute)
+        _no_bc()
         if minus is not None:
             _check_minus(uu, minus)
             res = None
@@ -666,8 +724,9 @@ class Burgers:
     """``Joint/Burgers_Residuals_CP.py:171-187``:
     ``dx*D_t(u) + dt*u*D_x(u) - nu*D_xx(u)*(2*dt/dx)`` on [BS,Nt,Nx]."""
 
-    def __init__(self, dx, dt, nu, device='cpu', fused=True):
+    def __init__(self, dx, dt, nu, device='cpu', fused=True, bc=None):
         self.fused = fused
+        self.bc = None if bc is None else _BC(bc)
         self.D_t = ConvOperator1D(domain='t', order=1, device=device)
         self.D_x = ConvOperator1D(domain='x', order=1, device=device)
         self.D_xx = ConvOperator1D(domain='x', order=2, device=device)
@@ -680,6 +739,17 @@ class Burgers:
         def composed(uu):
             dxd, dtd, nud = (c.to(uu.device) for c in (dx, dt, nu))
             return dxd * self.D_t(uu) + dtd * uu * self.D_x(uu) - nud * self.D_xx(uu) * (2 * dtd / dxd)
+        if self.bc is not None:
+            if minus is not None:
+                _check_minus(uu, minus)
+            sq = lambda x: x[:, 0] if x is not None and x.dim() == 4 and x.shape[1] == 1 else x
+            scal = (float(dx), float(dt), float(nu), float(2 * dt / dx))           # (2 dt / dx in fp32 like the reference)
+            return _bc_residual("burgers", self.bc, 2, (sq(uu),), None if minus is None else (sq(minus),), composed,
+                                (self.D_t, self.D_x, self.D_xx),
+                                lambda d, o, ks, st, flags: _lib.load_bcres().pre_bcres_burgers_f32(
+                                    _lib.ptr(d[0]), _lib.iarr64(d[0].stride()), _lib.ptr(o), _lib.iarr64(o.stride()), *ks, *scal,
+                                    ctypes.byref(st), *o.shape, flags, _lib.stream()), boundary, absolute, fused=self.fused)
+        _no_bc()
         # (the fused entries take [BS,Nt,Nx] only: a [BS,1,Nt,Nx] field composes)
         fused = self.fused and uu.numel() > 0 and uu.dim() == 3 and \
             not _dispatch.needs_grad(self.D_t.kernel, self.D_x.kernel, self.D_xx.kernel)
@@ -696,3 +766,213 @@ class Burgers:
                 *[x for t in [s[0] for s in d] + [o] for x in (_lib.ptr(t), _lib.iarr64(t.stride()))], *tail, *o.shape, flags,
                 _lib.stream()), sets, absolute)
         return _tail(res, sets, composed, boundary, _CROP2, absolute, pair)
+
+
+# ======================================================================= boundary conditions on the x-y rim (bc=)
+# r_bc(fields) = r_zero_pad(pad(f) for f in fields)[..., :, 1:-1, 1:-1]: ``pad`` is ``BoundaryManager(3).pad_signal`` on each
+# [BS,Nt,Nx,Ny] field (Utils/boundary_conditions.py; Nt rides as the channel axis), the time axis keeps its zero padding.
+# FUSED: one pass of ``libcp_pre_bcres.so`` (include/cp_pre_bcres.h) - the march and the functors of the zero-pad passes,
+# the out-of-domain neighbour of a rim cell mapped by the kernel, no padded copy.  COMPOSED (the fallback, and the
+# recomputation under autograd): pad every field, the composed operators on the padded grid, crop.  ``last_route()`` says
+# which ran and why.
+_route = None
+
+
+def last_route():
+    """The route of the last residual call in this process: ``'fused:bc_<kind>'``, ``'fallback:<why>'``, or None when that
+    call had no ``bc``."""
+    return _route
+
+
+def _no_bc():
+    global _route
+    _route = None
+
+
+class _BC:
+    """A normalised ``bc=``: ``'wrap'`` (true periodicity on all four sides, ``F.pad(mode='circular')``; opt-in and no
+    parity claim, like ``y_axis_fix``), or the reference's ``pad_signal`` semantics given as a ``BoundaryManager`` (held, not
+    copied: later changes of its sides count), a type name for all four sides, or a dict ``side -> type | (type, value)``
+    (sides left out are 'periodic', the manager's default).  A list / tuple with one such entry per field is accepted and
+    always composes (the fused entries take one condition for every field)."""
+
+    def __init__(self, bc):
+        from .boundary_conditions import BoundaryManager
+        self.wrap, self.manager, self.per_field = False, None, None
+        if isinstance(bc, _BC):
+            self.wrap, self.manager, self.per_field = bc.wrap, bc.manager, bc.per_field
+        elif isinstance(bc, str) and bc == 'wrap':
+            self.wrap = True
+        elif isinstance(bc, (list, tuple)):
+            self.per_field = [_BC(b) for b in bc]
+        elif isinstance(bc, str):
+            self.manager = BoundaryManager(3)
+            self.manager.set_all_boundaries(bc)
+        elif isinstance(bc, dict):
+            self.manager = BoundaryManager(3)
+            for side, v in bc.items():
+                t, value = v if isinstance(v, (tuple, list)) else (v, 0.0)
+                self.manager.set_boundary_type(side, t, value)
+        elif hasattr(bc, 'pad_signal') and hasattr(bc, 'boundary_types') and hasattr(bc, 'boundary_values'):
+            self.manager = bc
+        else:
+            raise TypeError("bc must be 'wrap', a boundary type name, a dict side -> type | (type, value), or a BoundaryManager")
+        m = self.manager
+        if m is not None and not (m.pad_left == m.pad_right == m.pad_top == m.pad_bottom == 1):
+            raise ValueError("bc: the residual stencils have radius 1, the BoundaryManager must pad one cell per side "
+                             "(kernel_size=3)")
+
+    def _rows(self):
+        """The manager of the 1-D family: left / right act on Nx, the rows (time) keep the zero padding."""
+        from .boundary_conditions import BoundaryManager
+        m = BoundaryManager((1, 3))
+        for s in ('left', 'right'):
+            m.boundary_types[s], m.boundary_values[s] = self.manager.boundary_types[s], self.manager.boundary_values[s]
+        return m
+
+    def pad(self, f, nd, i=0):
+        """Field i padded by one cell per side of x and y (``nd == 3``, [BS,Nt,Nx,Ny]) or of x (``nd == 2``, [BS,Nt,Nx])."""
+        if self.per_field is not None:
+            return self.per_field[i].pad(f, nd)
+        if self.wrap:
+            return torch.nn.functional.pad(f, (1, 1, 1, 1) if nd == 3 else (1, 1), mode='circular')
+        if nd == 3:
+            return self.manager.pad_signal(f)
+        return self._rows().pad_signal(f[:, None])[:, 0]
+
+    def struct(self, nd):
+        """(``pre_bc_t``, None) or (None, why the fused entries cannot take this condition)."""
+        from .vector_convops_spatial import _bc_struct
+        if self.per_field is not None:
+            return None, "per-field boundary conditions"
+        if self.wrap:
+            return _lib.PreBC((ctypes.c_int * 4)(*([_lib.PRE_BC_PERIODIC] * 4)), (ctypes.c_float * 4)()), None
+        m = self.manager
+        if nd == 2:
+            m = self._rows()
+            m.pad_top = m.pad_bottom = 1                           # (for _bc_struct only: the rows are the constant 0)
+            m.boundary_types.update(top='dirichlet', bottom='dirichlet')
+        if 'free_slip' in m.boundary_types.values():
+            return None, "'free_slip' has no padding rule"
+        st = _bc_struct(m)
+        if st is None:
+            return None, "mixed condition without a fused mapping"
+        return st, None
+
+
+def _bc_kernels(ops, dense):
+    """(the dense kernels of ``ops`` as the entries take them, None) or (None, why not)."""
+    if any(getattr(o, "kernel", None) is None for o in ops):
+        return None, "operator without a kernel"
+    if _dispatch.needs_grad(*[o.kernel for o in ops]):
+        return None, "operator kernel requires grad"
+    ks = [dense(o.kernel) for o in ops]
+    if any(k is None for k in ks):
+        return None, "operator kernel off the 7-point star"
+    for o in ops:
+        _, off = _dispatch.taps_of(_dispatch.host_kernel(o.kernel))
+        if not _dispatch.is_star(off):
+            return None, "operator kernel off the 7-point star"
+    return ks, None
+
+
+def _bc_single(kind, spec, nd, fields, composed, ops, launch, absolute, out, fused, flags0=0, force=None):
+    """One field set under ``spec``: the result [BS,Nt,Nx(,Ny)] (uncropped in t) where the fields live.  ``launch(devs, out,
+    ks, st, flags)`` runs the fused entry and returns its code; ``composed(*fields)`` is the zero-pad expression from single
+    operators.  ``force``: a reason to compose whatever the inputs."""
+    global _route
+    for f in fields:
+        _dispatch._check_field(f)
+
+    def padded(*f):
+        r = composed(*[spec.pad(x, nd, i) for i, x in enumerate(f)])
+        return r[..., 1:-1, 1:-1] if nd == 3 else r[..., 1:-1]
+    f0 = fields[0]
+    ax = "Ny" if nd == 3 else "Nx"
+    ks = st = None
+    why = force
+    if why is None and not fused:
+        why = "fused=False"
+    if why is None:
+        st, why = spec.struct(nd)
+    if why is None:
+        ks, why = _bc_kernels(ops, _dispatch.dense27 if nd == 3 else _dispatch.dense9)
+    if why is None and f0.numel() == 0:
+        why = "empty batch"
+    if why is None and f0.shape[-1] % 4 != 0:
+        why = f"{ax} % 4 != 0"
+    if why is None and any(f.stride(-1) != 1 for f in fields):
+        why = f"no unit stride on {ax}"
+    if why is None and not all(f.is_cuda for f in fields):
+        why = "CPU inputs"
+    given = out is not None
+    if given and not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(f0.shape) and
+                      out.stride(-1) == 1 and not _dispatch.needs_grad(*fields)):
+        raise ValueError(f"out with bc must be an fp32 device tensor of the field shape with unit stride on {ax}, no autograd")
+    if why is None:
+        with torch.no_grad():
+            res = out if given else torch.empty(tuple(f0.shape), dtype=torch.float32, device=f0.device)
+            with torch.cuda.device(f0.device):
+                rc = launch(list(fields), res, ks, st, flags0 | (_lib.PRE_FLAG_ABS if absolute else 0))
+        if rc == _lib.PRE_E_UNSUPPORTED:
+            why = "the library declines (layout, or a tap structure that is not built)"
+        else:
+            _lib.check(rc, "pre_bcres_" + kind)
+            _route = "fused:bc_" + kind
+            return _attach(res, (tuple(fields),), padded, absolute)
+    _route = "fallback:" + why
+    res = padded(*fields)               # (pure data movement where the fields live; each operator stages its own input)
+    if absolute:
+        res = res.abs()
+    if given:
+        out.copy_(res)
+        res = out
+    return res
+
+
+def _bc_residual(kind, spec, nd, fields, minus, composed, ops, launch, boundary, absolute, out=None, fused=True, flags0=0):
+    """How every residual under ``bc`` ends.  ``minus``: the second field set - r(fields) - r(minus) as two passes and an
+    in-place subtract, composed when a field requires grad.  ``boundary=False`` crops the time rim only: the x-y rim is
+    valid."""
+    run = lambda f, a, o, force=None: _bc_single(kind, spec, nd, f, composed, ops, launch, a, o, fused, flags0, force)
+    if minus is None:
+        res = run(fields, absolute, out)
+    elif _dispatch.needs_grad(*fields, *minus):
+        if out is not None:
+            raise ValueError("out with bc and minus= needs fields without autograd")
+        res = run(fields, False, None, "minus= with a field that requires grad") - \
+            run(minus, False, None, "minus= with a field that requires grad")
+        res = res.abs() if absolute else res
+    else:
+        res = run(fields, False, out)
+        b = run(minus, False, None)
+        with torch.no_grad():
+            res.sub_(b.to(res.device))
+            if absolute:
+                res.abs_()
+    return res if boundary else res[:, 1:-1]
+
+
+def _fld(t):
+    return ctypes.byref(_lib.field(t))
+
+
+def _bc_linear1(d, o, ks, st, flags):
+    return _lib.load_bcres().pre_bcres_linear1_f32(_fld(d[0]), _fld(o), ks[0], ctypes.byref(st), *o.shape, flags, _lib.stream())
+
+
+def _bc_linear1_rows(d, o, ks, st, flags):
+    return _lib.load_bcres().pre_bcres_linear1_rows_f32(_lib.ptr(d[0]), _lib.iarr64(d[0].stride()), _lib.ptr(o),
+                                                        _lib.iarr64(o.stride()), ks[0], ctypes.byref(st), *o.shape, flags,
+                                                        _lib.stream())
+
+
+def apply_bc(D, field, bc):
+    """A bare operator under boundary conditions: ``D(pad(field))`` cropped back to the field's shape - ``D`` a
+    ``convops_2d.ConvOperator`` on [BS,Nt,Nx,Ny] (any star kernel, taps along Nt included) or a ``convops_1d.ConvOperator``
+    on [BS,Nt,Nx].  ``ConvOperator.__call__`` itself stays the zero-padded operator."""
+    nd = field.dim() - 1
+    if nd not in (2, 3):
+        raise RuntimeError(f"expected a [BS,Nt,Nx] or [BS,Nt,Nx,Ny] field, got {tuple(field.shape)}")
+    return _bc_residual("linear1" if nd == 3 else "linear1_rows", _BC(bc), nd, (field,), None, lambda u: D(u), (D,),
+                        _bc_linear1 if nd == 3 else _bc_linear1_rows, True, False)
