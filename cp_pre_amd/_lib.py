@@ -478,6 +478,19 @@ BCRES_SIGNATURES = {
     "pre_bcres_linear1_rows_f32": [_fp, _i64p, _fp, _i64p, POINTER(c_float), POINTER(PreBC)] + [c_int64] * 3 + [c_int, c_void_p],
 }
 
+# libcp_pre_screenbc.so (include/cp_pre_screenbc.h): the screen and the per-sample statistics of the 2-D residuals under
+# boundary conditions on the x-y rim: each entry takes its zero-pad twin's arguments in libcp_pre_screen.so /
+# libcp_pre_screenstats.so (Ny-fastest form) with a pre_bc_t (PreBC) before the extents
+SCREENBC_SO_PATH = os.path.join(_HERE, "libcp_pre_screenbc.so")
+PRE_SCREENBC_ABI_VERSION = 1
+SCREENBC_SIGNATURES = {
+    "pre_screenbc_abi_version": [],
+    "pre_screenbc_stats_workspace_len": [c_int64] * 4,
+    **{_name.replace("pre_screen_", "pre_screenbc_"): _with_bc(_sig, 6) for _name, _sig in SCREEN_SIGNATURES.items() if _sig},
+    **{_name.replace("pre_screen_", "pre_screenbc_stats_"): _with_bc(SCREENSTATS_SIGNATURES[_name.replace("pre_screen_", "pre_screenstats_")], 6)
+       for _name, _sig in SCREEN_SIGNATURES.items() if _sig},
+}
+
 PRE_FFT_ABI_VERSION = 1        # include/cp_pre_fft.h (pre_fft_abi_version)
 
 # One row per shared object: (module attribute that caches the handle, prefix of <P>SO_PATH / <P>SIGNATURES, version
@@ -519,8 +532,10 @@ _LIBS_MORE = {
     "screenstats": ("_screenstats", "SCREENSTATS_", "pre_screenstats_abi_version", "PRE_SCREENSTATS_ABI_VERSION",
                     ("pre_screenstats_workspace_len",)),
     "bcres": ("_bcres", "BCRES_", "pre_bcres_abi_version", "PRE_BCRES_ABI_VERSION", ()),
+    "screenbc": ("_screenbc", "SCREENBC_", "pre_screenbc_abi_version", "PRE_SCREENBC_ABI_VERSION",
+                 ("pre_screenbc_stats_workspace_len",)),
 }
-_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = _screenjorekcells = _screenstats = _bcres = None
+_lib = _fft = _dist = _cov = _ode = _setprop = _pair = _bounds = _vjp = _screen = _screen1d = _screenflat = _vjpflat = _wgrad = _cns = _cnsvjp = _vjpmhd = _screenjorek = _vjpflatmhd = _vjpjorek = _screenpair = _screen1dpair = _screencells = _screen1dcells = _screencellspair = _screenjorekcells = _screenstats = _bcres = _screenbc = None
 _BUILD_HINT = "`python -c 'import __graft_entry__ as g; g.build()'`"
 
 
@@ -657,6 +672,11 @@ def load_screenjorekcells():
 
 def load_screenstats():
     return _screenstats or _load("screenstats")
+
+
+def load_screenbc():
+    """libcp_pre_screenbc.so: loaded only by a screen or statistics call with ``bc=`` (``screen``)."""
+    return _screenbc or _load("screenbc")
 
 
 def load_bcres():

@@ -126,13 +126,17 @@ class Method:
         return _SCALARS[self.row](self.obj) if self.row in _SCALARS else ()
 
     # -------- can a fused launch run?
-    def declined(self, x, yy=None, kernel_trains=False):
+    def declined(self, x, yy=None, kernel_trains=False, bc=None):
         """What keeps a fused launch from running whatever the layout (no download), or None.  ``yy``: data the launch
-        does not differentiate; ``kernel_trains``: a kernel that requires grad is the caller's to train."""
+        does not differentiate; ``kernel_trains``: a kernel that requires grad is the caller's to train; ``bc``: the
+        ``residuals._BC`` of a caller whose launch evaluates the x-y rim under it (the screens' ``bc=``) - an object with
+        ``bc`` then does not decline, what keeps the condition from the fused entries does."""
         if getattr(self.obj, "fused", True) is False:
             return "fused=False"
-        if getattr(self.obj, "bc", None) is not None:
+        if bc is None and getattr(self.obj, "bc", None) is not None:
             return "bc= (no fused screen or backward under boundary conditions on the x-y rim)"
+        if bc is not None and bc.struct(3)[1] is not None:
+            return bc.struct(3)[1]
         if yy is not None and yy.requires_grad and torch.is_grad_enabled():
             return "yy requires grad"
         if not kernel_trains and _dispatch.needs_grad(*[getattr(o, "kernel", None) for o in self.ops]):

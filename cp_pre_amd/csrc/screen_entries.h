@@ -2,7 +2,8 @@
 // screen_pair.hip, screen_cells.hip, screen_cells_pair.hip, screen_jorek.hip and screen_jorek_cells.hip: what an entry does between its arguments and its launch.  An entry
 // of those files assembles the views its residual reads and forwards to one of the five bodies below (stencil3d, linear2,
 // ns_momentum, mhd, jorek), which is templated on what differs between the libraries:
-//   Form   NyForm (Ny-fastest fields, screen_march.h) or FlatForm (Nt-fastest fields, screen_flat.h);
+//   Form   NyForm (Ny-fastest fields, screen_march.h) or FlatForm (Nt-fastest fields, screen_flat.h); screen_bc.hip states a
+//          third of its own, NyBCForm (NyForm under boundary conditions on the x-y rim), with its rows of Built;
 //   W      the functor wrapper: Single (one field set) or Paired (paired_functor.h: d = r(a) - r(b) of two sets);
 //   Sets   the set policy of screen_plane.h: ScalarSets (nk levels) or CellSets (nk level fields);
 // the set descriptor's type follows from Form and Sets (prepare_sets).  Every body checks in one order: kernel and tap-list

@@ -22,9 +22,26 @@ struct SGeom {
     int ct, cx, cy, nk;
 };
 
-template <class Fn, int NR, int TYQ, class Sets = ScalarSets>
-__global__ void __launch_bounds__(NR *TYQ, MinWaves<Fn>::value)
-screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets sets)
+// Waves per SIMD the register allocator must leave room for: MinWaves<Fn>, and for the BC form under the level policies what
+// the functor asks for it (Fn::SCREEN_BC_MIN_WAVES, optional).  The statistics policy never takes that request: its fp64
+// accumulators sit next to the functor, and where a functor needs the request it costs scratch there
+// (profiles/screenbc/resources.txt).
+template <class Fn, class = void> struct ScreenBCMinWaves { static constexpr int value = MinWaves<Fn>::value; };
+template <class Fn> struct ScreenBCMinWaves<Fn, std::void_t<decltype(Fn::SCREEN_BC_MIN_WAVES)>> {
+    static constexpr int value = Fn::SCREEN_BC_MIN_WAVES;
+};
+template <class Fn, class Sets, bool BC> struct MarchMinWaves {
+    static constexpr int value = (BC && !IsStats<Sets>::value) ? ScreenBCMinWaves<Fn>::value : MinWaves<Fn>::value;
+};
+
+// BC: boundary conditions on the x-y rim, as march_kernel<Fn, NR, TYQ, BC> of star_march.h takes them (BCInfo, host_checks.h):
+// the halo row beyond the grid is the mapped row or the side's constant, the row x == X of a partial last tile is a ghost row
+// that loads its mapped row and never counts, the last quad of a row keeps a second edge scalar (Halo::yr).  What is counted,
+// the modulation, the levels, the accumulators and the combine step do not know of it.
+template <class Fn, int NR, int TYQ, class Sets = ScalarSets, bool BC = false>
+__global__ void __launch_bounds__(NR *TYQ, (MarchMinWaves<Fn, Sets, BC>::value))
+screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets sets,
+                    const typename std::conditional<BC, BCInfo, NoBC>::type bc)
 {
     constexpr int F = Fn::F;
     constexpr bool CELLS = Sets::CELLS;
@@ -67,7 +84,17 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
     const int x = xt * NR + ty, y = (yt * TYQ + q) * 4;
     const bool inb = (x < g.X) && (y < g.Y);       // (whole quads only: Y % 4 == 0, checked by the host)
     // PRE_FLAG_HALO_X, partial last tile: row X is real data and the x+ neighbour of row X-1 (loaded, never counted)
-    const bool ldown = inb || ((g.flags & PRE_FLAG_HALO_X) && x == g.X && y < g.Y);
+    bool ldown = inb || ((g.flags & PRE_FLAG_HALO_X) && x == g.X && y < g.Y);
+    // BC (never with PRE_FLAG_HALO_X): that row is a ghost row, which loads the row the side maps to, or holds its constant
+    // (a side's constant is a kernel argument, hence a scalar register: a thread keeps the predicate that it applies - gconst,
+    // hclo / hchi, lconst, rconst below - and selects the scalar after the load, where a per-thread fill value would be one
+    // more vector register each, live across the plane loop)
+    int xl = x;
+    [[maybe_unused]] bool gconst = false;
+    if constexpr (BC) {
+        ldown = inb;
+        if (x == g.X && y < g.Y) { xl = bc.xhi; ldown = bc.xhi >= 0; gconst = bc.xhi < 0; }
+    }
     const bool kx = inb && x >= g.cx && x < g.X - g.cx;
     const bool keep[4] = {kx && y >= g.cy && y < g.Y - g.cy, kx && y + 1 >= g.cy && y + 1 < g.Y - g.cy,
                           kx && y + 2 >= g.cy && y + 2 < g.Y - g.cy, kx && y + 3 >= g.cy && y + 3 < g.Y - g.cy};
@@ -81,22 +108,39 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
     const bool hduty = COOP ? hl < 8 * TYQ : (ty == 0 || ty == NR - 1), hbot = COOP ? hl >= 4 * TYQ : ty == NR - 1;
     const int hcol = COOP ? hl & (4 * TYQ - 1) : 4 * q;
     const int hy = yt * (4 * TYQ) + hcol;
-    const int hx = hbot ? xt * NR + NR : xt * NR - 1;
+    int hx = hbot ? xt * NR + NR : xt * NR - 1;
     const bool halox = (g.flags & PRE_FLAG_HALO_X) != 0;
-    const bool hrow = hduty && (halox ? (hx >= -1 && hx <= g.X) : (hx >= 0 && hx < g.X)) && (hy < g.Y);
+    bool hrow = hduty && (halox ? (hx >= -1 && hx <= g.X) : (hx >= 0 && hx < g.X)) && (hy < g.Y);
     const int hslot = hbot ? NR + 1 : 0;
     // y-halo duty: ONE edge scalar per lane (y- for a wave's first lane, y+ for a wave's / tile's last lane)
     const bool ledge = ((q & 63) == 0);
-    const bool redge = ((q & 63) == 63) || (q == TYQ - 1);
-    const bool eload = ledge ? (inb && y > 0) : (redge && inb && y + 4 < g.Y);
-    const int eoff4 = 4 * (ledge ? -1 : 4);
+    bool redge = ((q & 63) == 63) || (q == TYQ - 1);
+    bool eload = ledge ? (inb && y > 0) : (redge && inb && y + 4 < g.Y);
+    int eoff4 = 4 * (ledge ? -1 : 4);
+    // BC: the row beyond the grid and the cells beyond a row's ends by BCInfo, as march_kernel; `ye` is then the y- scalar of
+    // every lane that needs one and `yr` the y+ scalar (the last quad of a row is a right edge wherever it lies in its wave)
+    [[maybe_unused]] bool hclo = false, hchi = false, lconst = false, rconst = false, rload = false;
+    [[maybe_unused]] int yroff4 = 16;
+    if constexpr (BC) {
+        if (hduty && hy < g.Y && (hx == -1 || hx == g.X)) {
+            const int m = hx < 0 ? bc.xlo : bc.xhi;
+            hclo = hx < 0 && m < 0;
+            hchi = hx >= 0 && m < 0;
+            hrow = m >= 0;
+            hx = m >= 0 ? m : 0;
+        }
+        eload = ledge && inb && y > 0;
+        rload = redge && inb && y + 4 < g.Y;
+        if (inb && y == 0) { eload = bc.ylo >= 0; eoff4 = 4 * bc.ylo; lconst = bc.ylo < 0; }
+        if (inb && y + 4 >= g.Y) { redge = true; rload = bc.yhi >= 0; yroff4 = 4 * (bc.yhi - y); rconst = bc.yhi < 0; }
+    }
 
     // Addresses as in march_kernel: a plane of a field of this sample is a wave-uniform buffer descriptor based one row
     // BEFORE row 0, a thread's place in it a 32-bit byte offset (the host has checked that every offset fits)
     unsigned int voff[F], hoff[F];
 #pragma unroll
     for (int i = 0; i < F; ++i) {
-        voff[i] = (unsigned int)(((long long)(x + 1) * g.sX[i] + y) * 4);
+        voff[i] = (unsigned int)(((long long)(xl + 1) * g.sX[i] + y) * 4);
         hoff[i] = (unsigned int)(((long long)(hx + 1) * g.sX[i] + hy) * 4);
     }
     const unsigned int moff = (unsigned int)(((long long)x * g.mX + y) * 4);
@@ -117,9 +161,11 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
             } else {
                 dst[i] = f4(0.f);
             }
+            if constexpr (BC)
+                if (gconst) dst[i] = f4(bc.vxhi);
         }
     };
-    auto load_halo = [&](int t, Halo<F, false, COOP> &h) __attribute__((always_inline)) {
+    auto load_halo = [&](int t, Halo<F, BC, COOP> &h) __attribute__((always_inline)) {
         const bool okt = (t >= tlo) && (t < thi);
 #pragma unroll
         for (int i = 0; i < F; ++i) {
@@ -127,13 +173,26 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
                 if constexpr (COOP) h.row[i] = 0.f; else h.row[i] = f4(0.f);
             } else if constexpr (COOP) {
                 h.row[i] = (hrow && okt) ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(plane(i, t), (int)hoff[i], 0, 0)) : 0.f;
+                if constexpr (BC) {
+                    if (hclo) h.row[i] = bc.vxlo;
+                    if (hchi) h.row[i] = bc.vxhi;
+                }
             } else if (hrow && okt) {
                 const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(plane(i, t), (int)hoff[i], 0, 0);
                 h.row[i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
             } else {
                 h.row[i] = f4(0.f);
+                if constexpr (BC) {
+                    if (hclo) h.row[i] = f4(bc.vxlo);
+                    if (hchi) h.row[i] = f4(bc.vxhi);
+                }
             }
             h.ye[i] = (eload && okt) ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(plane(i, t), (int)voff[i] + eoff4, 0, 0)) : 0.f;
+            if constexpr (BC) {
+                h.yr[i] = (rload && okt) ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(plane(i, t), (int)voff[i] + yroff4, 0, 0)) : 0.f;
+                if (lconst) h.ye[i] = bc.vylo;
+                if (rconst) h.yr[i] = bc.vyhi;
+            }
         }
     };
     // the modulation quad of plane t: only by threads with a counted cell and only for planes of this segment (its rim
@@ -203,7 +262,7 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
     // receives the halo of plane t+1; mc is the modulation of plane t, mn receives that of plane t+1.  The caller rotates
     // the roles instead of moving registers.
     auto step = [&](int t, float4(&P)[F], float4(&C)[F], float4(&N)[F], float4(&D)[F],
-                    Halo<F, false, COOP> &hc, Halo<F, false, COOP> &hn, float4 &mc, float4 &mn) __attribute__((always_inline)) {
+                    Halo<F, BC, COOP> &hc, Halo<F, BC, COOP> &hn, float4 &mc, float4 &mn) __attribute__((always_inline)) {
         const int bi = (t - t0) & 1;
         // per-cell sets: this plane's first LB level quads go out BEFORE the field loads below, so the wait for them at the
         // end of the plane (vmcnt retires in issue order) leaves the loads of the coming planes in flight
@@ -241,7 +300,7 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
             float lft = lane_below(C[i].w);
             float rgt = lane_above(C[i].x);
             lft = ledge ? hc.ye[i] : lft;
-            rgt = redge ? hc.ye[i] : rgt;
+            rgt = redge ? (BC ? hc.yr[i] : hc.ye[i]) : rgt;
             n[i].ym = make_float4(lft, C[i].x, C[i].y, C[i].z);
             n[i].yp = make_float4(C[i].y, C[i].z, C[i].w, rgt);
         }
@@ -281,7 +340,7 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
         }
     };
 
-    Halo<F, false, COOP> h0, h1;
+    Halo<F, BC, COOP> h0, h1;
     float4 w0[F], w1[F], w2[F], w3[F], m0, m1;
     load_own(t0 - 1, w0);
     load_own(t0, w1);
@@ -351,8 +410,8 @@ screen_march_kernel(const SGeom g, const typename Fn::Params prm, const Sets set
 }
 
 // ------------------------------------------------------------------ host side
-template <class Fn, int NR, int TYQ, class Sets>
-int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets)
+template <class Fn, int NR, int TYQ, class Sets, bool BC = false>
+int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets, const BCInfo *bc = nullptr)
 {
     static_assert(2 * Staged<Fn>::FX * (NR + 2) * TYQ * 16 + (NKMAX + 1) * (NR * TYQ / 64) * 4 <= 160 * 1024, "tile does not fit the 160 KiB LDS");
     g.nXT = (g.X + NR - 1) / NR;
@@ -366,7 +425,7 @@ int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st
         if (sets.qX < 0 || ((long long)(g.X + NR) * sets.qX + g.Y + 8) * 4 >= (1LL << 32)) return PRE_E_SHAPE;
     }
     long long tiles = nb * g.nXT * g.nYT;
-    static const int per_cu = resident_per_cu(screen_march_kernel<Fn, NR, TYQ, Sets>, NR * TYQ);
+    static const int per_cu = resident_per_cu(screen_march_kernel<Fn, NR, TYQ, Sets, BC>, NR * TYQ);
     int tSeg = pick_tseg(tiles, g.T, (long long)per_cu * chip_cus());
     if (TFREE_TSEG > 0 && g.tfree && tSeg > TFREE_TSEG) tSeg = TFREE_TSEG;     // (segments cost no window prologue then)
     g.tSeg = tSeg;
@@ -375,7 +434,11 @@ int launch_screen_tiled(SGeom &g, const typename Fn::Params &prm, hipStream_t st
     if (tiles <= 0 || tiles * TYQ > 0xffffffffLL) return PRE_E_SHAPE;      // the dispatch packet counts work-items in 32 bits
     if constexpr (IsStats<Sets>::value)
         if (!stats_room(sets, tiles)) return PRE_E_NULL;                   // (never with the length the query entry gives)
-    hipLaunchKernelGGL((screen_march_kernel<Fn, NR, TYQ, Sets>), dim3((unsigned)tiles), dim3(TYQ, NR), 0, st, g, prm, sets);
+    if constexpr (BC) {
+        hipLaunchKernelGGL((screen_march_kernel<Fn, NR, TYQ, Sets, true>), dim3((unsigned)tiles), dim3(TYQ, NR), 0, st, g, prm, sets, *bc);
+    } else {
+        hipLaunchKernelGGL((screen_march_kernel<Fn, NR, TYQ, Sets, false>), dim3((unsigned)tiles), dim3(TYQ, NR), 0, st, g, prm, sets, NoBC{});
+    }
     PRE_LAUNCH_CHECK();
     if constexpr (IsStats<Sets>::value) return stats_finish(sets, g.B, tiles / g.B, st);
     return PRE_OK;
@@ -390,13 +453,13 @@ inline long long stats_slots_ny(long long T, long long X, long long Y)
     return ((X + NR - 1) / NR) * ((Y + W - 1) / W) * ((T + 7) / 8);
 }
 
-template <class Fn, class Sets = ScalarSets>
-int launch_screen(SGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets = Sets())
+template <class Fn, class Sets = ScalarSets, bool BC = false>
+int launch_screen(SGeom &g, const typename Fn::Params &prm, hipStream_t st, const Sets &sets = Sets(), const BCInfo *bc = nullptr)
 {
     // the tiles of star_march.h's launch()
-    if (g.Y >= 192) return launch_screen_tiled<Fn, 8, 64>(g, prm, st, sets);
-    if (g.Y >= 96) return launch_screen_tiled<Fn, 16, 32>(g, prm, st, sets);
-    return launch_screen_tiled<Fn, 32, 16>(g, prm, st, sets);
+    if (g.Y >= 192) return launch_screen_tiled<Fn, 8, 64, Sets, BC>(g, prm, st, sets, bc);
+    if (g.Y >= 96) return launch_screen_tiled<Fn, 16, 32, Sets, BC>(g, prm, st, sets, bc);
+    return launch_screen_tiled<Fn, 32, 16, Sets, BC>(g, prm, st, sets, bc);
 }
 
 template <template <int> class FnT, class P, class Sets = ScalarSets>

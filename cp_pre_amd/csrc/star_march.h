@@ -138,6 +138,9 @@ struct NSMomentum {    // Marginal/NS_Residuals_CP.py:231-240
     // (146 VGPRs, 17 dwords spilled) was -30 %: scratch traffic inside the plane loop.
     static constexpr int MIN_WAVES = MODE >= 3 ? 4 : 1;
     static constexpr bool HALO_LEAD = MODE == 0;        // (the one tap structure it was measured on: 116 VGPRs, no scratch)
+    // the screen's BC form (screen_march.h) under the level policy: with the request 128 VGPRs on all three tiles and no scratch,
+    // two workgroups per CU as without BC; 129 on the 32 x 16 tile without it
+    static constexpr int SCREEN_BC_MIN_WAVES = MODE == 0 ? 4 : MIN_WAVES;
     static constexpr unsigned XMASK = xmask_of<MODE>(O_DT | O_DX | O_DY | O_LAP, O_DT | O_DX | O_DY | O_LAP, O_DX | O_DY);
     using Params = NSParams;
     static __device__ __forceinline__ float4 eval(const Nbr (&n)[3], const Params &p)

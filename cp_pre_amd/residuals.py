@@ -840,6 +840,16 @@ class _BC:
             return self.manager.pad_signal(f)
         return self._rows().pad_signal(f[:, None])[:, 0]
 
+    def free_slip(self, nd=3):
+        """Does a side the residuals of ``nd`` axes pad (all four; left / right for the 1-D family), of any field's condition,
+        have 'free_slip'?  The reference pads nothing there: the residual under it has not the field's extents."""
+        if self.per_field is not None:
+            return any(b.free_slip(nd) for b in self.per_field)
+        if self.manager is None:
+            return False
+        sides = ('left', 'right', 'top', 'bottom') if nd == 3 else ('left', 'right')
+        return any(str(self.manager.boundary_types[s]).lower() == 'free_slip' for s in sides)
+
     def struct(self, nd):
         """(``pre_bc_t``, None) or (None, why the fused entries cannot take this condition)."""
         from .vector_convops_spatial import _bc_struct

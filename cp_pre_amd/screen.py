@@ -153,6 +153,29 @@ the general-star tap structure of the MHD momentum and energy equations, which d
 accumulators), and JOREK keeps ``fallback:no fused stats for JOREK``.  ``minus=`` is not accepted; ``halo_x`` raises where
 ``Screen.add_slab`` raises.  Without a call to these two the library is never loaded, and they load no other screen library.
 
+Residuals under boundary conditions on the x-y rim (``bc=`` on the constructors of ``residuals``: ``r_bc(fields) =
+r_zero_pad(pad(f) for f in fields)[..., :, 1:-1, 1:-1]``, the time axis zero-padded) are screened and reduced in one launch
+only where the caller asks for it: ``screen(method, vars, qhats, modulation, bc=True)`` / ``Screen.add_slab(..., bc=True)`` /
+``screen_stats(method, vars, bc=True)`` / ``ScreenStats.add_slab(..., bc=True)`` on a method of ``NavierStokes`` / ``PRE_NS``,
+``MHD`` / ``PRE_MHD`` or ``PRE_Wave`` whose object was built with ``bc=`` (the object's condition is used, read anew on every
+call; without one, or on JOREK, a ``TypeError``), and ``bc=<condition>`` - anything ``residuals._BC`` takes - on a bare
+``convops_2d.ConvOperator``, where the screened quantity is ``residuals.apply_bc(D, field, bc)`` (any other value on a bound
+method is a ``TypeError``).  ``libcp_pre_screenbc.so`` (``include/cp_pre_screenbc.h``): the Ny-fastest march above with the
+halo row beyond the grid, the ghost row of a partial last tile and the cells beyond a row's ends read from the mapped
+in-domain cell or taken as the side's constant.  With ``bc`` set, ``boundary=False`` of ``screen`` / ``screen_stats`` counts
+``crop=(1, 0, 0)`` - the time rim only, as ``residual*(..., boundary=False)`` crops under ``bc`` - and ``boundary=True`` every
+cell; ``add_slab`` keeps its explicit ``crop``; ``modulation`` keeps the uncropped extents.  Routes ``fused:bc_<kind>`` /
+``fused:bc_stats_<kind>`` for the kinds ``stencil3d``, ``linear2``, ``ns_momentum``, ``mhd_<eq>``.  The three-pass route runs on
+the bc residual (``_Spec.full`` calls the method with ``boundary=True``) for, in this order: ``minus=``, ``input on the CPU``,
+float64 levels; ``no fused screen under bc for the 1-D family``; ``Nt-fastest view: the merged-row march has no BC form``; no
+unit stride on Ny, a width that is no multiple of 4; ``fused=False``; what ``_BC.struct`` says of the condition (per-field
+conditions, a mixed condition without a fused mapping); a kernel that requires grad or lies off the 7-point star; ``declined
+by the library`` (the general stars of MHD momentum and energy).  A ``'free_slip'`` side - in the condition, or in any
+member of a per-field list (``residuals._BC.free_slip``) - raises ``ValueError`` before any device work: the reference pads nothing there, so the residual under it has not the field's extents and neither a cell count
+nor a modulation would fit it.  ``halo_x=True`` with ``bc`` raises ``ValueError``, as the residuals do; per-cell sets, ``pair=`` and the 1-D family
+have no fused form under ``bc``.  Without the keyword an object with ``bc`` keeps ``fallback:bc= (...)`` and the library is never
+loaded.
+
 Sharding is by the batch axis: each rank screens its own samples, nothing is exchanged.
 
 Host side: what a method is, what it reads and what declines a fused launch whatever the layout is resolved in
@@ -262,6 +285,9 @@ _JOREK_CELLS_ENTRY = {"": "pre_screenjorekcells_f32", "flat": "pre_screenjorekce
 # the per-sample statistics (``screen_stats`` / ``ScreenStats``), one more library for all three forms: the prefix of its
 # entries, followed by the form's route prefix
 _STATS_ENTRY = "pre_screenstats_"
+# the screens and statistics under boundary conditions on the x-y rim (opt-in, ``bc=``), one more library, Ny-fastest views only
+_BC_ENTRY = "pre_screenbc_"
+_BC_HALO_X = "bc with halo_x=True: an x-slab with a wrapped x is not served under boundary conditions"
 
 
 def _pair_mode(pair, minus):
@@ -291,7 +317,7 @@ class _Spec(Method):
     WHY = {"spectral": "spectral operator", "jorek": "no fused screen for JOREK",
            **dict.fromkeys(ROWS_KIND, "1-D family: the marched axis is the batch")}
 
-    def __init__(self, method, jorek=False):
+    def __init__(self, method, jorek=False, bc=False):
         bound, self.norms = method, False
         if jorek and isinstance(method, functools.partial) and not method.args and set(method.keywords) <= {"norms"} and \
                 isinstance(getattr(method.func, "__self__", None), R.JOREK):
@@ -311,6 +337,24 @@ class _Spec(Method):
             self.ratio, = self.scalars()
         elif self.kind in _MHD_EQ:
             self.eq = _MHD_EQ[self.kind]
+        # ``bc``: the opt-in screens of the residual under boundary conditions on the x-y rim.  None: not asked for (an
+        # object with ``bc`` then keeps its three-pass route); else the ``residuals._BC`` the launches read, each time anew
+        self.bc = None
+        if bc is not False and bc is not None:
+            if jorek or self.row in ("jorek", "jorek_any"):
+                raise TypeError("bc= takes no JOREK method: its residuals have no boundary conditions on the x-y rim")
+            if self.is_op:
+                if bc is True or self.row == "spectral":
+                    raise TypeError("bc=True takes a bound residual method of an object built with bc=; a bare ConvOperator "
+                                    "takes the condition itself, bc=<condition> (residuals.apply_bc)")
+                self.bc = R._BC(bc)
+            else:
+                if bc is not True:
+                    raise TypeError("bc=<condition> takes a bare ConvOperator; a bound residual method takes bc=True and "
+                                    "uses the condition of its object")
+                if getattr(self.obj, "bc", None) is None:
+                    raise TypeError(f"bc=True on a {type(self.obj).__name__} built without bc=")
+                self.bc = self.obj.bc
 
     def fields(self, x):
         if self.kind in _JOREK_EQ:
@@ -342,8 +386,9 @@ class _Spec(Method):
             if halo_x:
                 kw["halo_x"] = True
             if self.is_op:
-                r = self.method(x)
-                return r if minus is None else r - self.method(minus)
+                op = self.method if self.bc is None else (lambda f: R.apply_bc(self.method, f, self.bc))
+                r = op(x)
+                return r if minus is None else r - op(minus)
             return self.method(x, boundary=True, **kw)
 
     # -------- can a fused screen run?  input, then layout, then what declines whatever the layout, then the kernels
@@ -374,10 +419,33 @@ class _Spec(Method):
             why = "not three JOREK channels"                     # (the residual methods unstack exactly rho, phi, T)
         return (why, ()) if why is not None else self.star_kernels(kind, points)
 
+    def declined(self, x, yy=None, kernel_trains=False):
+        """``Method.declined``, under this spec's ``bc`` where one was asked for."""
+        return super().declined(x, yy, kernel_trains, bc=self.bc)
+
+    def prepare_bc(self, x, minus, qhats, modulation):
+        """``prepare`` with ``bc`` asked for: (why, kernels), the reasons in the order of the module docstring."""
+        # (before anything else, and before any device work: the reference pads nothing on a 'free_slip' side, so the residual
+        # under it has not the field's extents - there is no rim to count, and no cell count or modulation that would fit)
+        if self.bc.free_slip(self.nd):                           # (per-field conditions included)
+            raise ValueError("bc= with a 'free_slip' side: it has no padding rule, the residual under it does not cover the "
+                             "x-y plane and no screen of it is defined")
+        why = _input_declined(x, minus, qhats, modulation)
+        if why is None and (self.rows_kind is not None or self.nd == 2):
+            why = "no fused screen under bc for the 1-D family"
+        if why is None and self.nt_fastest(x):
+            why = "Nt-fastest view: the merged-row march has no BC form"
+        why = why or self._layout(self.view(x)) or self.declined(x)
+        if why is None and self.kind in _MHD_EQ and x.shape[1] < 6:
+            why = "fewer than six MHD channels"
+        return (why, ()) if why is not None else self.star_kernels(self.kind, 7)
+
     def prepare(self, x, minus, qhats, modulation, pair=False):
         """(why, kernels): ``why`` is None if the fused screen can run; host checks and one download of the operator
         kernels (``_dispatch.host_kernel`` on every call: a screen applies the kernels its operators hold now).  ``pair``
         with a ``minus``: the same question of the paired screen, of both sets."""
+        if self.bc is not None:
+            return self.prepare_bc(x, minus, qhats, modulation)
         if self.kind is None:
             pair = _pair_mode(pair, minus)
             return (pair and self.pair_declined(pair == "rows")) or self.why, ()
@@ -435,7 +503,10 @@ class _Spec(Method):
     # -------- the launches: one body, three forms ('': Ny-fastest views, 'flat': Nt-fastest views, 'rows': the 1-D family)
     def entry(self, form, pair=False, cells=False, stats=False):
         """The entry point of this method's fused screen in the library of ``form`` (``pair``: of its paired screen,
-        ``cells``: of its per-cell screen; form 'rows' has both at once; ``stats``: of its per-sample statistics)."""
+        ``cells``: of its per-cell screen; form 'rows' has both at once; ``stats``: of its per-sample statistics).  With
+        ``bc`` asked for: of ``libcp_pre_screenbc.so``, form '' only."""
+        if self.bc is not None:
+            return _BC_ENTRY + ("stats_" if stats else "") + ("mhd" if self.kind in _MHD_EQ else self.kind) + "_f32"
         if stats:
             kind = self.rows_kind if form == "rows" else "mhd" if self.kind in _MHD_EQ else self.kind
             return _STATS_ENTRY + _FORMS[form][2] + kind + "_f32"
@@ -455,6 +526,8 @@ class _Spec(Method):
         return _FORMS[form][1] + kind + "_f32"
 
     def route(self, form, pair=False, cells=False, stats=False):
+        if self.bc is not None:
+            return "fused:bc_" + ("stats_" if stats else "") + self.kind
         if stats:
             return "fused:" + _FORMS[form][2] + "stats_" + (self.rows_kind if form == "rows" else self.kind)
         if cells and form == "rows":
@@ -487,7 +560,12 @@ class _Spec(Method):
             fn = getattr(_lib._load("screencellspair") if cells else _lib.load_screenpair(), self.entry(form, True, cells))
             return fn(*views, *kernels, *self.scalars(), ctypes.byref(st), *fa[0].shape, flags, _lib.stream())
         kind = self.rows_kind if form == "rows" else self.kind
-        if stats:
+        tail = ()                                                # (what follows the set descriptor: under ``bc`` the conditions)
+        if self.bc is not None:
+            assert form == "" and not cells and not flags & _lib.PRE_FLAG_HALO_X
+            lib = _lib.load_screenbc()                           # (loaded on this route only)
+            tail = (ctypes.byref(self.bc.struct(3)[0]),)         # (``prepare_bc`` has found that the condition has one)
+        elif stats:
             lib = _lib.load_screenstats()                        # (loaded on this route only)
         elif cells and form == "rows":
             lib = _lib.load_screen1dcells()
@@ -512,7 +590,7 @@ class _Spec(Method):
         if kind.startswith("stencil"):
             kernels = _dispatch.tap_args(*kernels)
         return getattr(lib, self.entry(form, cells=cells, stats=stats))(*views, *kernels, *self.scalars(), ctypes.byref(st),
-                                                                        *shape, flags, _lib.stream())
+                                                                        *tail, *shape, flags, _lib.stream())
 
     def launch_flat(self, kernels, x, st, flags):
         return self.launch(kernels, x, st, flags, "flat")
@@ -589,16 +667,19 @@ class Screen:
         return self.acc
 
     def add_slab(self, method, vars_slab, qhats, modulation_slab=None, crop=(1, 1, 1), halo_x=False, minus=None, jorek=False,
-                 pair=False):
+                 pair=False, bc=False):
         """``vars_slab``: the method's input on a slab of the grid (all local samples); ``modulation_slab`` [T,X,Y] of the
         slab's uncropped residual extents, or None (m == 1); ``crop`` cells per side of each residual axis are left out
         (``JointCalibration.add_slab``'s meaning); ``halo_x``: the slab's rows -1 and X lie in the same memory; ``jorek``: the
         opt-in fused screen of the JOREK residuals (``_Spec``; a method given as a ``_Spec`` has decided already); ``pair``:
         the opt-in paired screen of ``vars_slab`` and ``minus`` (no effect without ``minus``; under ``halo_x`` both sets
         must be Ny-contiguous device views with rows -1 and X in memory); ``pair="rows"``: the same, and the paired rows
-        screen for the 1-D family (module docstring)."""
+        screen for the 1-D family (module docstring); ``bc``: the opt-in screen of the residual under boundary conditions
+        on the x-y rim (module docstring; ``crop`` stays the caller's: ``(ct, 0, 0)`` counts the whole plane)."""
         global _last_route
-        spec = method if isinstance(method, _Spec) else _Spec(method, jorek)
+        spec = method if isinstance(method, _Spec) else _Spec(method, jorek, bc)
+        if spec.bc is not None and halo_x:
+            raise ValueError(_BC_HALO_X)
         pair = _pair_mode(pair, minus)
         shape, crop, cells = _check_inputs(spec, vars_slab, qhats, modulation_slab, minus, crop, self.nk)
         if shape[0] != self.n_local:
@@ -615,11 +696,11 @@ class Screen:
         if halo_x and why is not None and not spec.reads_halo():
             # (before any device work: this slab would be evaluated against zero padding and counted as if it were right)
             raise RuntimeError(f"halo_x: the fused screen cannot run ({why}) and no other pass of this method reads the halo rows")
-        rows = spec.rows_kind is not None                     # (the 1-D family: halo_x has raised above)
+        rows = spec.rows_kind is not None and spec.bc is None     # (the 1-D family: halo_x has raised above)
         if rows:
             why, kernels = spec.prepare_rows(vars_slab, minus, qhats, modulation_slab, pair)
         # Nt-fastest views of the 2-D residuals: the flat route (halo_x keeps the behaviour it had: the flat form pads x)
-        flat = not rows and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
+        flat = not rows and spec.bc is None and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
         if flat:
             why, kernels = spec.prepare_flat(vars_slab, minus, qhats, modulation_slab, pair)
         if why is None:
@@ -711,17 +792,27 @@ class Screen:
         return Screened(self.acc[0].view(torch.float32).clone(), self.acc[1:].to(torch.int64) & 0xffffffff, self.cells)
 
 
-def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=None, jorek=False, pair=False):
+def _whole_crop(spec, boundary):
+    """The crop of ``screen`` / ``screen_stats``: nothing with ``boundary=True``; else one cell per side of every residual
+    axis - with ``bc`` asked for of the time axis only, as ``residual*(..., boundary=False)`` crops under ``bc``."""
+    if boundary:
+        return (0,) * spec.nd
+    return (1,) + (0,) * (spec.nd - 1) if spec.bc is not None else (1,) * spec.nd
+
+
+def screen(residual_method, vars, qhats, modulation=None, boundary=False, minus=None, jorek=False, pair=False, bc=False):
     """Screen the predictions ``vars`` against the sets ``|r| <= qhats[k] * modulation``.  ``boundary=False``: the counted
     cells are the interior ``[1:-1]`` of every residual axis, as the reference crops its residuals (``modulation`` keeps
     the uncropped extents: its rim is never used); ``boundary=True``: every cell.  ``jorek=True``: the opt-in fused screen
     of ``JOREK.residual_continuity`` / ``residual_temperature`` (``vars`` [BS,F,Nx,Ny,Nt], ``modulation`` [Nt,Nx,Ny]; the
     equations with ``norms=False``).  ``minus``: the data-driven score, ``d = r(vars) - r(minus)`` in place of the residual;
     ``pair=True`` with it: the opt-in paired screen (one launch over both sets; module docstring), ``pair="rows"``: the
-    same, and for the 1-D family its paired rows screen; without ``minus`` the keyword has no effect.  Returns a
+    same, and for the 1-D family its paired rows screen; without ``minus`` the keyword has no effect.  ``bc``: the opt-in
+    screen of the residual under boundary conditions on the x-y rim (``True`` on a method of an object built with ``bc=``,
+    the condition itself on a bare ``ConvOperator``); ``boundary=False`` then crops the time rim only.  Returns a
     :class:`Screened`."""
-    spec = _Spec(residual_method, jorek)
-    crop = (0,) * spec.nd if boundary else (1,) * spec.nd
+    spec = _Spec(residual_method, jorek, bc)
+    crop = _whole_crop(spec, boundary)
     shape, _, _ = _check_inputs(spec, vars, qhats, modulation, minus, crop)
     s = Screen(shape[0], qhats.shape[0], vars.device)
     s.add_slab(spec, vars, qhats, modulation, crop=crop, minus=minus, pair=pair)
@@ -787,6 +878,8 @@ class ScreenCells(Screen):
         [BS,3,Nx,Ny,Nt], ``qcells_slab`` [nk,Nt,Nx,Ny]; ``halo_x`` raises and ``minus`` keeps the three-pass route."""
         global _last_route
         spec = method if isinstance(method, _Spec) else _Spec(method, jorek)
+        if spec.bc is not None:
+            raise TypeError("per-cell sets have no screen under bc: a _Spec made with bc= goes to Screen / ScreenStats")
         rows = bool(rows) and spec.rows_kind is not None
         # (the paired entries of the rows form take ``minus``; the 2-D kinds take it where the caller asks with ``pair=True``)
         pair = "rows" if rows and minus is not None else spec.rows_kind is None and minus is not None and bool(pair)
@@ -1039,12 +1132,15 @@ class ScreenStats:
             self.sums = torch.zeros(3, self.n_local, dtype=torch.float64, device=device)
         return self.mx, self.sums
 
-    def add_slab(self, method, vars_slab, crop=(1, 1, 1), halo_x=False):
+    def add_slab(self, method, vars_slab, crop=(1, 1, 1), halo_x=False, bc=False):
         """``vars_slab``: the method's input on a slab of the grid (all local samples); ``crop`` cells per side of each
         residual axis are left out (two axes for the 1-D family); ``halo_x``: the slab's rows -1 and X lie in the same
-        memory (raises where ``Screen.add_slab`` raises).  There is no ``minus``: the 'PRE' acquisition has no paired form."""
+        memory (raises where ``Screen.add_slab`` raises); ``bc``: the opt-in statistics of the residual under boundary
+        conditions on the x-y rim (module docstring).  There is no ``minus``: the 'PRE' acquisition has no paired form."""
         global _last_route
-        spec = method if isinstance(method, _Spec) else _Spec(method)
+        spec = method if isinstance(method, _Spec) else _Spec(method, bc=bc)
+        if spec.bc is not None and halo_x:
+            raise ValueError(_BC_HALO_X)
         shape, crop, cells = _check_stats(spec, vars_slab, crop)
         if shape[0] != self.n_local:
             raise ValueError(f"slab of {shape[0]} samples, expected n_local = {self.n_local}")
@@ -1058,18 +1154,21 @@ class ScreenStats:
         if halo_x and why is not None and not spec.reads_halo():
             # (before any device work: this slab would be evaluated against zero padding and counted as if it were right)
             raise RuntimeError(f"halo_x: the fused statistics cannot run ({why}) and no other pass of this method reads the halo rows")
-        rows = spec.rows_kind is not None                     # (the 1-D family: its rows route by default; halo_x has raised)
+        rows = spec.rows_kind is not None and spec.bc is None     # (the 1-D family: its rows route by default; halo_x has raised)
         if rows:
             why, kernels = spec.prepare_rows(vars_slab, None, _F32, None)
-        flat = not rows and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
+        flat = not rows and spec.bc is None and not halo_x and vars_slab.is_cuda and spec.nt_fastest(vars_slab)
         if flat:
             why, kernels = spec.prepare_flat(vars_slab, None, _F32, None)
         if why is None:
             mx, sums = self._buffers(vars_slab.device)
             form = "rows" if rows else "flat" if flat else ""
             with torch.no_grad(), torch.cuda.device(vars_slab.device):
-                need = int(_lib.load_screenstats().pre_screenstats_workspace_len(
-                    _lib.PRE_SCREENSTATS_FORM[form], *shape, *((1,) if rows else ())))
+                if spec.bc is not None:
+                    need = int(_lib.load_screenbc().pre_screenbc_stats_workspace_len(*shape))
+                else:
+                    need = int(_lib.load_screenstats().pre_screenstats_workspace_len(
+                        _lib.PRE_SCREENSTATS_FORM[form], *shape, *((1,) if rows else ())))
                 ws = _stats_workspace(vars_slab.device, need)
                 st = _lib.PreScreenStats(crop[0], crop[1], 0 if rows else crop[2], ctypes.c_void_p(mx.data_ptr()),
                                          ctypes.c_void_p(sums.data_ptr()), sums.stride(0), ctypes.c_void_p(ws.data_ptr()),
@@ -1112,15 +1211,16 @@ class ScreenStats:
                            self.cells)
 
 
-def screen_stats(residual_method, vars, boundary=False):
+def screen_stats(residual_method, vars, boundary=False, bc=False):
     """Per-sample statistics of the residual of ``vars`` - sum r, sum |r|, sum r^2 in float64 and max |r| - from ONE
     streaming launch that stores no residual (followed by a tiny launch that adds the workgroups' partial sums; no
     floating-point atomics: the same inputs give the same bytes on every run).  ``boundary=False``: the counted cells are
     the interior ``[1:-1]`` of every residual axis; ``boundary=True``: every cell.  Returns a :class:`SampleStats`:
     ``stats.order()`` is the ``sort_index`` of ``torch.sort(torch.mean(torch.abs(residual), axis=...))``,
-    ``stats.order("mean")`` that of the signed form.  There is no ``minus=``: the 'PRE' acquisition has no paired form."""
-    spec = _Spec(residual_method)
-    crop = (0,) * spec.nd if boundary else (1,) * spec.nd
+    ``stats.order("mean")`` that of the signed form.  There is no ``minus=``: the 'PRE' acquisition has no paired form.
+    ``bc``: as in ``screen`` (``boundary=False`` then crops the time rim only)."""
+    spec = _Spec(residual_method, bc=bc)
+    crop = _whole_crop(spec, boundary)
     shape, _, _ = _check_stats(spec, vars, crop)
     s = ScreenStats(shape[0], vars.device)
     s.add_slab(spec, vars, crop=crop)

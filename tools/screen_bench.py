@@ -106,6 +106,15 @@ Shapes (``--div N`` divides every batch by N; the default runs them whole):
                parent / three runs F / J / P alone.)  Lines go to profiles/screenstats/screen_bench_stats.jsonl unless --out
                says otherwise
 
+    bc_ns / bc_wave / bc_induction
+               the screen (one level, with a modulation) and the statistics under ``bc='wrap'`` (``libcp_pre_screenbc.so``) at
+               the shapes of DESIGN 4.31's table: NS momentum [64,3,64,512,512], wave [512,32,256,256], MHD induction
+               [64,6,64,256,256].  Routes, alternated call by call: (a) the fused launch with ``bc=True``, crop (1,0,0); (b) the
+               zero-pad fused launch of the same functor on an object without ``bc``, crop (1,1,1); (c) the call on the ``bc``
+               object without the keyword (the three-pass route on the stored bc residual; for the statistics the float64
+               reductions).  (a) and (b) are first compared bit for bit on crop (1,1,1).  Two lines per case go to
+               profiles/screenbc/screenbc_bench.jsonl unless --out says otherwise
+
     python tools/screen_bench.py [--cases ns_rank,c2_wave,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast] [--div 8] [--reps 3] [--blocks 5]
     rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/screen_bench.py --cases ns_rank --only fused --blocks 1 --reps 1
         (HBM bytes by the counters, a run of its own with nothing else traced; --only residual for the launch it replaces)
@@ -850,6 +859,83 @@ def run_stats(name, args, dev):
     return line
 
 
+# ---- the screens and statistics under boundary conditions on the x-y rim (``bc='wrap'``), at the shapes of DESIGN 4.31's table
+BC_CASES = {"bc_ns": ("ns_momentum", (64, 3, 64, 512, 512)), "bc_wave": ("wave", (512, 32, 256, 256)),
+            "bc_induction": ("mhd_induction", (64, 6, 64, 256, 256))}
+
+
+def run_bc(name, args, dev):
+    """Two lines, the screen (one level, with a modulation) and the statistics, each with three routes alternated call by call
+    in one process on the same tensors: (a) the fused launch under ``bc=True``, crop (1, 0, 0); (b) the zero-pad fused launch of
+    the same functor on an object without ``bc``, crop (1, 1, 1); (c) the call on the ``bc`` object without the keyword - what
+    the parent commit does: the stored bc residual, then the score and a ``CoverageLevels`` pass per sample, or the float64
+    reductions.  Before timing: (a) equals (b) bit for bit on crop (1, 1, 1)."""
+    kind, shape = BC_CASES[name]
+    n = max(shape[0] // args.div, 1)
+    g = torch.Generator(device=dev).manual_seed(0)
+    v = torch.rand((n,) + shape[1:], device=dev, generator=g) + 0.5      # (Ny-fastest: the form the BC march takes)
+    if kind == "wave":
+        make = lambda **kw: R.PRE_Wave(0.01, 0.02, device=dev, **kw).residual  # noqa: E731
+    elif kind == "ns_momentum":
+        make = lambda **kw: R.NavierStokes(0.01, 1 / 64, 1 / 64, device=dev, **kw).residual_momentum  # noqa: E731
+    else:
+        make = lambda **kw: R.MHD(device=dev, **kw).residual_induction  # noqa: E731
+    m_bc, m_zero = make(bc="wrap"), make()
+    rshape = (n,) + tuple(v.shape[-3:])
+    mod = torch.rand(rshape[1:], device=dev, generator=g) + 0.5
+    q = torch.full((1,), 5.0, device=dev)
+    nfields = {"wave": 1, "ns_momentum": 3, "mhd_induction": 4}[kind]
+    cells = 1
+    for d in rshape:
+        cells *= d
+
+    def screen_of(m, crop, **kw):
+        def f():
+            s = screen.Screen(n, 1, dev)
+            s.add_slab(m, v, q, mod, crop=crop, **kw)
+            return s
+        return f
+
+    def stats_of(m, crop, **kw):
+        def f():
+            s = screen.ScreenStats(n, dev)
+            s.add_slab(m, v, crop=crop, **kw)
+            return s
+        return f
+
+    lines = []
+    for what, of in (("screen", screen_of), ("stats", stats_of)):
+        a, b, c = of(m_bc, (1, 0, 0), bc=True), of(m_zero, (1, 1, 1)), of(m_bc, (1, 0, 0))
+        ga = of(m_bc, (1, 1, 1), bc=True)().finish()
+        route_a = screen.last_route()
+        gb = b().finish()
+        route_b = screen.last_route()
+        c()
+        route_c = screen.last_route()
+        torch.cuda.synchronize()
+        if what == "screen":
+            same = bool(torch.equal(ga.score.view(torch.int32), gb.score.view(torch.int32)) and torch.equal(ga.inside, gb.inside))
+        else:
+            same = bool(torch.equal(ga.max_abs.view(torch.int32), gb.max_abs.view(torch.int32)))
+        if not same:
+            raise SystemExit(f"{name} {what}: (a) and (b) differ on crop (1, 1, 1)")
+        res = blocks_of([a, b, c], args.reps, args.blocks, args.warmup)
+        line = {"case": name, "what": what, "kind": kind, "shape": list(v.shape), "bc": "wrap", "route_a": route_a, "route_b": route_b,
+                "route_c": route_c, "a_equals_b_bits_on_crop_111": same, "cells": cells, "field_bytes_per_cell": 4 * nfields}
+        if what == "stats":
+            rel = ((ga.sum_abs - gb.sum_abs).abs() / gb.sum_abs).max()
+            line["sum_abs_rel_diff_a_b_on_crop_111"] = float(rel)
+        for k, (med, lo, hi) in zip("abc", res):
+            line[k + "_ms"] = round(med, 4)
+            line[k + "_ms_blocks_min_max"] = [round(lo, 4), round(hi, 4)]
+        line["a_TBps_of_fields"] = round(cells * 4 * nfields / (line["a_ms"] * 1e-3) / 1e12, 3)
+        line["a_over_b"] = round(line["a_ms"] / line["b_ms"], 4)
+        line["a_over_c"] = round(line["a_ms"] / line["c_ms"], 4)
+        line["a_slowest_block_faster_than_c_fastest"] = bool(line["a_ms_blocks_min_max"][1] < line["c_ms_blocks_min_max"][0])
+        lines.append(line)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="ns_rank,c3_xslab,c4_mhd,c2_wave,c5_burgers_nx,c5_burgers_nt,c3_rank8_ntfast,c4_induction_ntfast")
@@ -874,6 +960,16 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in args.cases.split(","):
+        if name in BC_CASES:
+            path = args.out or os.path.join(ROOT, "profiles", "screenbc", "screenbc_bench.jsonl")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            for line in run_bc(name, args, dev):
+                txt = json.dumps(line)
+                print(txt, flush=True)
+                with open(path, "a") as f:
+                    f.write(txt + "\n")
+            torch.cuda.empty_cache()
+            continue
         if name in STATS_CASES:
             path = args.out or os.path.join(ROOT, "profiles", "screenstats", "screen_bench_stats.jsonl")
             os.makedirs(os.path.dirname(path), exist_ok=True)
